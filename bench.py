@@ -709,6 +709,79 @@ def shard_probe(scene, sw, tensors, local_rank, N, steps=200):
     return res
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BYTES = 60_000_000   # the arrays written under --dump-outputs, at most (with the .npy headers: under 64 MB, 10^6 or 2^20)
+DUMP_SEED = 0             # the trajectory sample of the per-pair outputs: the same rows in every run of one batch size
+
+
+def dump_outputs(out, path):
+    """What the last timed step handed its caller (the SweepResult of PlanningStep.run / MetricSweep.run) as
+    ``path/<name>.npy``, float64 (float32 where the step stores float32), so that two builds can be compared output for
+    output.  Per-trajectory outputs (cost, safe, cost_all) are written whole while they fit in a quarter of DUMP_BYTES; the
+    per-pair outputs (pair_f, pair_i, lists: every agent slot) on a seeded sample of the trajectories that fits the rest.
+    ``rows_<name>`` / ``rows_pair`` hold the trajectory indices of each array.  Every file is finite: the outputs that
+    carry NaN / inf by definition (cost, cost_all, pair_f, lists: metrics not evaluated, no collision, inactive agent
+    slots) hold 0 there, and ``<name>_nonfinite`` (float32, same shape) says what stood there: 0 finite, 1 NaN, 2 +inf,
+    3 -inf.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    coded = ("cost", "cost_all", "pair_f", "lists")             # (written with a _nonfinite companion of 4 B per entry)
+
+    def rows(n, bytes_per_row, budget):
+        k = min(n, budget // (bytes_per_row + 8))     # (+8: the index itself)
+        if k >= n:
+            return np.arange(n)
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+    def take(t, r):         # the rows r of the last (trajectory) axis, on the host
+        return t.index_select(t.dim() - 1, torch.as_tensor(r, dtype=torch.long, device=t.device)).cpu().numpy()
+
+    def entry_bytes(name, dtype):     # what one entry of an output costs in the files
+        return (4 if dtype in (torch.float32, torch.uint8) else 8) + (4 if name in coded else 0)
+
+    arrays = {}
+    per_traj = {"cost": out.cost.t(), "safe": out.safe}           # (cost [M, 16] taken as [16, M], written back as [M, 16])
+    if out.cost_all is not None:
+        per_traj["cost_all"] = out.cost_all.t()                   # (every rank's rows: its own sample)
+    for name, t in per_traj.items():
+        n = int(t.shape[-1])
+        r = rows(n, t.numel() // max(n, 1) * entry_bytes(name, t.dtype), DUMP_BYTES // 4 // len(per_traj))
+        a = take(t, r)
+        arrays[name] = a.astype(np.float32) if a.dtype == np.uint8 else a.T.astype(np.float64)
+        arrays["rows_" + name] = r.astype(np.float64)
+    per_pair = {}
+    if out.pair_f is not None:
+        per_pair["pair_f"] = [out.pair_f]                         # [NPF, A, M] float64
+        per_pair["pair_i"] = [out.pair_i]                         # [NPI, A, M] int32 -> float64 (exact)
+    if out.lists_raw is not None:
+        per_pair["lists"] = out.list_views()                      # 5 x [A, T-1, M] float32 or float64 -> [5, A, T-1, M]
+    M = int(out.cost.shape[0])
+    if per_pair and M > 0:
+        row_bytes = sum(q.numel() // M * entry_bytes(name, q.dtype) for name, v in per_pair.items() for q in v)
+        used = sum(a.nbytes + (a.size * 4 if name in coded else 0) for name, a in arrays.items())
+        r = rows(M, row_bytes, DUMP_BYTES - used)
+        arrays["rows_pair"] = r.astype(np.float64)
+        for name, v in per_pair.items():
+            a = np.stack([take(q, r) for q in v]) if name == "lists" else take(v[0], r)
+            arrays[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    for name in [n for n in coded if n in arrays]:
+        a = arrays[name]
+        code = np.zeros(a.shape, np.float32)
+        code[np.isnan(a)], code[a == np.inf], code[a == -np.inf] = 1, 2, 3
+        arrays[name] = np.where(code == 0, a, 0).astype(a.dtype)
+        arrays[name + "_nonfinite"] = code
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_BYTES:
+        raise AssertionError(f"--dump-outputs: {total} B over the {DUMP_BYTES} B budget")
+    bad = [name for name, a in arrays.items() if not np.isfinite(a).all()]
+    if bad:
+        raise AssertionError(f"--dump-outputs: non-finite entries left in {bad}")
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -735,6 +808,10 @@ def main():
     ap.add_argument("--order", default="sampler", choices=["sampler", "random"],
                     help="row order of the synthetic trajectories (synthetic.make_trajectories)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (cost, safe, per-pair outputs on a seeded "
+                         "trajectory sample) as DIR/<name>.npy, float32 / float64, finite (NaN / inf entries coded in <name>_nonfinite.npy), "
+                         "at most 64 MB in all")
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic in this run (the default N = 1 run of the "
                          "headline workload does; the committed summary of the loaded library is the fallback)")
@@ -1023,6 +1100,8 @@ def main():
             res["config"]["gate_pair_frac"] = float((out.pair_f[N.PF["max_collision_probability"]] > 0).double().mean())
             res["config"]["collision_pair_frac"] = float((out.pair_f[N.PF["dce"]] == 0).double().mean())
             res["config"]["safe_traj_frac"] = float(out.safe.double().mean())
+        if args.dump_outputs and out is not None:
+            res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(out, args.dump_outputs)}
         if world == 1 and not args.no_cpu_baseline:
             # oracle on EVERY pair: parity of the last timed step's buffers + the CPU baselines (before the extras below
             # reuse the context)

@@ -68,7 +68,9 @@ def main():
     # (1) the plugin surface: replicated evaluate_scenario, sharded batch assessment
     fo.evaluate_scenario({}, ego[:2], float(ego[2]), (0.0, 0.0), float(ego[3]), 0, None)
     dev_coll = torch.device("cuda", local) if args.backend == "nccl" else torch.device("cpu")
-    cg = D.CostGather(args.M, device=dev_coll)
+    # over RCCL the collective runs at any world size (one rank on a one-GPU box: through RCCL all the same)
+    force = args.backend == "nccl"
+    cg = D.CostGather(args.M, device=dev_coll, force=force)
     assert (cg.world, cg.rank) == (world, rank)
     ptrs = (cg.mine.data_ptr(), cg.gathered.data_ptr())
     for _ in range(3):                                       # repeated steps reuse the two blocks of the collective
@@ -84,7 +86,7 @@ def main():
     # (2) the one-call planning step with the split inside
     t = lambda k: torch.as_tensor(traj[k]).to(torch.device("cuda", local))
     ps = PlanningStep(fo.sensor_model, fo.spawn_locator, fo.metrics.sweep, t("x"), t("y"), t("theta"), t("v"), t("a"),
-                      mode="reduced", shard=D.CostGather(args.M, device=dev_coll))
+                      mode="reduced", shard=D.CostGather(args.M, device=dev_coll, force=force))
     for _ in range(2):
         o = ps.run(ego[:2], float(ego[2]), float(ego[3]))
     torch.cuda.synchronize()

