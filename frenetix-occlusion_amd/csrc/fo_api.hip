@@ -117,6 +117,8 @@ int fo_step_run(fo_ctx *ctx, const fo_step_t *p, void *stream) {
       (cells && p->max_agents < 1) || p->T_agents < 1 ||
       (rules && (p->max_rule_points < 1 || !p->d_rule_points || !p->d_n_rule_points || !p->d_path6 || !p->d_pos0 || !p->d_yaw0)))
     return fo_fail(ctx, FO_E_ARG, "fo_step_run: bad arguments");
+  if (rules && p->rule.frame != 0 && p->rule.frame != 1)
+    return fo_fail(ctx, FO_E_ARG, "fo_step_run: rule.frame = %d (0 the polyline frame, 1 the caller's frame)", p->rule.frame);
   if ((rc = fo_sweep_set_list_format(ctx, p->list_format))) return rc;   // the format is an argument of the run
   if ((rc = fo_step_stage_obstacles_(ctx, p, (hipStream_t)stream))) return rc;
   rc = fo_step_body_(ctx, p, stream, stages, cells, rules, slots, slot0, cell_agents);

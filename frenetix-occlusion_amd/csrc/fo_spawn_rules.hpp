@@ -13,7 +13,9 @@
 //   point.buffer(r).within(road)      -> every cell square the disc touches is road
 //   area.buffer(b).exterior & line    -> samples where "disc of radius b touches the area" flips along the line
 // The curvilinear frame is the polyline frame of the ego's reference path (utils/curvilinear.PolylineCS; the table
-// [n][6] = x, y, s, segment length, unit tangent is built on the host once per reference path).
+// [n][6] = x, y, s, segment length, unit tangent is built on the host once per reference path) or, with
+// fo_spawn_rule_params_t::frame = 1, a table sampled from the caller's own frame object (x, y, s, polyline arc length, vertex normal:
+// rl_cf_* below; the host builds it once per object, SpawnLocator._frame_setup).
 // Checked against oracle/fo_spawn_rules_ref.py (an independent NumPy restatement of the same definitions).
 //
 // Launch shape: one workgroup for the turn rule + one per obstacle (static rule: a wave; dynamic rule: 1 024 threads and
@@ -89,8 +91,9 @@ struct RuleView {
   int n_inter;
   const int32_t *inter_off, *inter_lanelet;
   const uint8_t *inter_kind;
-  const double *path;       // [n_path][6] x, y, s, segment length, tangent x, tangent y
+  const double *path;       // [n_path][6] x, y, s, segment length, tangent x, tangent y (frame 0) | x, y, s, arc length, normal x, y (frame 1)
   int n_path;
+  int frame;                // 0 polyline frame, 1 the caller's frame (fo_spawn_rule_params_t::frame)
 };
 
 __device__ inline int rl_class_at(const RuleView &v, double x, double y) {
@@ -283,7 +286,7 @@ __device__ inline bool rl_to_curv(const RuleView &v, double x, double y, double 
 // the same projection by a whole wave (every lane must call it with the same point): lane l takes the segments l, l + 64,
 // ...; the wave keeps the smallest (distance, segment index) -- the first minimum of the sequential scan -- and every
 // lane returns it.  (The sequential form is a chain of ~n_path dependent trips to the table in HBM.)
-__device__ inline bool rl_to_curv_wave(const RuleView &v, double x, double y, double &s, double &d) {
+__device__ inline bool rl_pl_to_curv_wave(const RuleView &v, double x, double y, double &s, double &d) {
   const int ns = v.n_path - 1, lane = threadIdx.x & 63;
   double best = INFINITY, bt = 0.0, btc = 0.0;
   int k = 0x7fffffff;
@@ -314,7 +317,7 @@ __device__ inline bool rl_to_curv_wave(const RuleView &v, double x, double y, do
 // (A projection alone is six exchange steps of LDS-crossbar latency: one after the other, the five of an obstacle's centre
 // and corners cost the static rule 10 us.)
 template <int N>
-__device__ inline unsigned rl_to_curv_wave_n(const RuleView &v, const double *x, const double *y, double *s, double *d) {
+__device__ inline unsigned rl_pl_to_curv_wave_n(const RuleView &v, const double *x, const double *y, double *s, double *d) {
   const int ns = v.n_path - 1, lane = threadIdx.x & 63;
   double best[N], bt[N], btc[N];
   int k[N];
@@ -356,7 +359,7 @@ __device__ inline unsigned rl_to_curv_wave_n(const RuleView &v, const double *x,
   }
   return ok;
 }
-__device__ inline bool rl_to_cart(const RuleView &v, double s, double d, double &x, double &y) {
+__device__ inline bool rl_pl_to_cart(const RuleView &v, double s, double d, double &x, double &y) {
   const int n = v.n_path;
   if (s < v.path[2] || s > v.path[6 * (size_t)(n - 1) + 2]) return false;
   int lo = 0, hi = n;   // searchsorted(s_table, s, side = 'right'): first index with table > s
@@ -369,6 +372,133 @@ __device__ inline bool rl_to_cart(const RuleView &v, double s, double d, double 
   x = q[0] + (s - q[2]) * q[4] + d * (-q[5]);
   y = q[1] + (s - q[2]) * q[5] + d * q[4];
   return true;
+}
+
+// ---- the caller's frame (fo_spawn_rule_params_t::frame = 1; DESIGN.md section 6, "The caller's frame"): a row per vertex
+// x, y (the base point b_i), the caller's s_i, the polyline arc length of the vertex (read by the turn rule only), the caller's
+// normal n_i (not unit); the step of segment i is s_{i+1} - s_i of column 2.  On segment i, lambda in
+// [0, 1]: b = b_i + lambda (b_{i+1} - b_i), n = n_i + lambda (n_{i+1} - n_i), the point b + d n.  Same operations in the same
+// order as tests/test_caller_frame_cpu.py's InterpolatedNormalFrame (the scene stage builds with -ffp-contract=off).
+// rl_cf_segment: the roots of cross(q - b(lambda), n(lambda)) = 0 in [-1e-12, 1 + 1e-12], clamped to [0, 1], on segment i (row r, the next row r + 6); a root
+// nearer to the point than `best` (squared distance to b) becomes the candidate -- the smaller root first, so that ties keep it
+__device__ __forceinline__ void rl_cf_segment(const double *r, int i, double x, double y, double &best, double &blam, int &k) {
+  const double wx = x - r[0], wy = y - r[1];
+  const double ex = r[6] - r[0], ey = r[7] - r[1], fx = r[10] - r[4], fy = r[11] - r[5];
+  const double a = fx * ey - fy * ex;                                  // cross(dn, db)
+  const double b = (wx * fy - wy * fx) - (ex * r[5] - ey * r[4]);      // cross(w, dn) - cross(db, n_i)
+  const double c = wx * r[5] - wy * r[4];                              // cross(w, n_i)
+  double l0, l1 = NAN;
+  if (fabs(a) <= 1e-12 * fabs(b)) {
+    l0 = -c / b;
+  } else {
+    const double disc = b * b - 4.0 * a * c;
+    if (!(disc >= 0.0)) return;
+    const double sq = sqrt(disc);
+    const double t = -0.5 * (b + (b >= 0.0 ? sq : -sq));
+    l0 = t / a;
+    l1 = c / t;
+    if (l1 < l0) { const double u = l0; l0 = l1; l1 = u; }
+  }
+  // (a root within 1e-12 of [0, 1] counts, clamped: a vertex that ends the path comes out at 1 + a rounding error)
+  if (l0 >= -1e-12 && l0 <= 1.0 + 1e-12) {
+    l0 = fmin(fmax(l0, 0.0), 1.0);
+    const double px = x - (r[0] + l0 * ex), py = y - (r[1] + l0 * ey), d2 = px * px + py * py;
+    if (d2 < best) { best = d2; blam = l0; k = i; }
+  }
+  if (l1 >= -1e-12 && l1 <= 1.0 + 1e-12) {
+    l1 = fmin(fmax(l1, 0.0), 1.0);
+    const double px = x - (r[0] + l1 * ex), py = y - (r[1] + l1 * ey), d2 = px * px + py * py;
+    if (d2 < best) { best = d2; blam = l1; k = i; }
+  }
+}
+// (s, d) of the point at lambda on segment k
+__device__ __forceinline__ void rl_cf_sd(const RuleView &v, int k, double lam, double x, double y, double &s, double &d) {
+  const double *r = v.path + 6 * (size_t)k;
+  const double bx = r[0] + lam * (r[6] - r[0]), by = r[1] + lam * (r[7] - r[1]);
+  const double nx = r[4] + lam * (r[10] - r[4]), ny = r[5] + lam * (r[11] - r[5]);
+  const double px = x - bx, py = y - by;
+  d = (px * nx + py * ny) / (nx * nx + ny * ny);
+  s = r[2] + lam * (r[8] - r[2]);
+}
+// rl_pl_to_curv_wave's shape: lane l takes the segments l, l + 64, ...; the smallest (distance, segment) over the wave
+__device__ inline bool rl_cf_to_curv_wave(const RuleView &v, double x, double y, double &s, double &d) {
+  const int ns = v.n_path - 1, lane = threadIdx.x & 63;
+  double best = INFINITY, blam = 0.0;
+  int k = 0x7fffffff;
+  for (int i = lane; i < ns; i += 64) rl_cf_segment(v.path + 6 * (size_t)i, i, x, y, best, blam, k);
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+    const double b2 = __shfl_xor(best, off), l2 = __shfl_xor(blam, off);
+    const int k2 = __shfl_xor(k, off);
+    if (b2 < best || (b2 == best && k2 < k)) { best = b2; k = k2; blam = l2; }
+  }
+  if (k == 0x7fffffff) return false;   // no segment has a root: outside the projection domain
+  rl_cf_sd(v, k, blam, x, y, s, d);
+  return true;
+}
+// rl_pl_to_curv_wave_n's shape: N points share the pass over the segments
+template <int N>
+__device__ inline unsigned rl_cf_to_curv_wave_n(const RuleView &v, const double *x, const double *y, double *s, double *d) {
+  const int ns = v.n_path - 1, lane = threadIdx.x & 63;
+  double best[N], blam[N];
+  int k[N];
+#pragma unroll
+  for (int n = 0; n < N; ++n) { best[n] = INFINITY; blam[n] = 0.0; k[n] = 0x7fffffff; }
+  for (int i = lane; i < ns; i += 64) {
+    const double *r = v.path + 6 * (size_t)i;
+#pragma unroll
+    for (int n = 0; n < N; ++n) rl_cf_segment(r, i, x[n], y[n], best[n], blam[n], k[n]);
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+      const double b2 = __shfl_xor(best[n], off);
+      const int k2 = __shfl_xor(k[n], off);
+      if (b2 < best[n] || (b2 == best[n] && k2 < k[n])) { best[n] = b2; k[n] = k2; }
+    }
+  }
+  unsigned ok = 0u;
+#pragma unroll
+  for (int n = 0; n < N; ++n) {
+    if (k[n] == 0x7fffffff) continue;
+    const double lam = __shfl(blam[n], k[n] & 63);   // (segment i's candidate lives in lane i mod 64)
+    rl_cf_sd(v, k[n], lam, x[n], y[n], s[n], d[n]);
+    ok |= 1u << n;
+  }
+  return ok;
+}
+__device__ inline bool rl_cf_to_cart(const RuleView &v, double s, double d, double &x, double &y) {
+  const int n = v.n_path;
+  if (s < v.path[2] || s > v.path[6 * (size_t)(n - 1) + 2]) return false;
+  int lo = 0, hi = n;   // the segment as in rl_pl_to_cart
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (v.path[6 * (size_t)mid + 2] <= s) lo = mid + 1; else hi = mid;
+  }
+  const int k = min(lo - 1, n - 2);
+  const double *r = v.path + 6 * (size_t)k;
+  const double lam = (s - r[2]) / (r[8] - r[2]);
+  const double bx = r[0] + lam * (r[6] - r[0]), by = r[1] + lam * (r[7] - r[1]);
+  const double nx = r[4] + lam * (r[10] - r[4]), ny = r[5] + lam * (r[11] - r[5]);
+  x = bx + d * nx;
+  y = by + d * ny;
+  return true;
+}
+
+// the frame the rules project through: v.frame is a kernel argument, the branch is uniform over the wave
+__device__ inline bool rl_to_curv_wave(const RuleView &v, double x, double y, double &s, double &d) {
+  if (v.frame) return rl_cf_to_curv_wave(v, x, y, s, d);
+  return rl_pl_to_curv_wave(v, x, y, s, d);
+}
+template <int N>
+__device__ inline unsigned rl_to_curv_wave_n(const RuleView &v, const double *x, const double *y, double *s, double *d) {
+  if (v.frame) return rl_cf_to_curv_wave_n<N>(v, x, y, s, d);
+  return rl_pl_to_curv_wave_n<N>(v, x, y, s, d);
+}
+__device__ inline bool rl_to_cart(const RuleView &v, double s, double d, double &x, double &y) {
+  if (v.frame) return rl_cf_to_cart(v, s, d, x, y);
+  return rl_pl_to_cart(v, s, d, x, y);
 }
 
 // distance between segment ab and a convex quadrilateral c [4][2] (0 if they touch or the segment starts / ends inside)
@@ -443,12 +573,13 @@ __device__ __forceinline__ void rl_turn_rule(const RuleView &v, const RuleParams
   if (nw < 2) return;
   if (nw > RL_TURNW) { if (lane == 0) rec[0] = -1.0; return; }   // (refused by the host entry already; -1: out of table space, see the selection kernel)
   const bool left = pr.intention == 1;
-  // the line: the reference window, for a left turn shifted 3 m to the left (spawn_locator.py:510-518)
+  // the line: the reference window, for a left turn shifted 3 m to the left (spawn_locator.py:510-518) -- at the POLYLINE arc
+  // lengths of the window's vertices (`reference_s`, :683), which the caller's table holds in column 3
   bool ok = true;
   for (int i = lane; i < nw; i += 64) {
     const double *q = v.path + 6 * (size_t)(pr.win_i0 + i);
     double x = q[0], y = q[1];
-    if (left) ok = rl_to_cart(v, q[2], 3.0, x, y) && ok;
+    if (left) ok = rl_to_cart(v, v.frame ? q[3] : q[2], 3.0, x, y) && ok;
     lx[i] = x;
     ly[i] = y;
   }
@@ -1720,6 +1851,8 @@ int fo_scene_spawn_rules(fo_ctx *ctx, const uint8_t *d_cls, int win_ix0, int win
   if (!m->d_poly_off) return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rules: the map holds no lanelet polygons");
   if (params->win_i0 < 0 || params->win_i1 > n_path || params->win_i1 < params->win_i0)
     return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: reference window [%d, %d) outside the path", params->win_i0, params->win_i1);
+  if (params->frame != 0 && params->frame != 1)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: frame = %d (0 the polyline frame, 1 the caller's frame)", params->frame);
   // table space the host can see (what only the device can -- a sampled line longer than RL_MAXSAMP cells / 8 -- comes back as
   // *d_n_out = -1): a rule that ran short would leave out a point the reference finds, unnoticed
   if (params->behind_turn && params->intention != 0 && params->win_i1 - params->win_i0 > RL_TURNW)
@@ -1754,7 +1887,7 @@ int fo_scene_spawn_rules(fo_ctx *ctx, const uint8_t *d_cls, int win_ix0, int win
   v.P = m->P; v.poly_off = m->d_poly_off; v.poly_xy = m->d_poly_xy; v.poly_box = m->d_poly_box;
   v.left0 = m->d_left0; v.pred0 = m->d_pred0; v.adj_left = m->d_adj_left;
   v.n_inter = m->n_inter; v.inter_off = m->d_inter_off; v.inter_lanelet = m->d_inter_lanelet; v.inter_kind = m->d_inter_kind;
-  v.path = d_path6; v.n_path = n_path;
+  v.path = d_path6; v.n_path = n_path; v.frame = params->frame;
   RuleParams pr{};
   pr.ego_x = params->ego_x; pr.ego_y = params->ego_y; pr.ego_yaw = params->ego_yaw; pr.ego_s = params->ego_s; pr.ego_d = params->ego_d;
   pr.s_threshold = params->s_threshold; pr.ped_width = params->ped_width; pr.ped_length = params->ped_length;

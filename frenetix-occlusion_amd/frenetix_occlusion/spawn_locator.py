@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from .utils.curvilinear import pathlength
 
 
 MIN_AHEAD = 3.0            # spawn_locator.py:234,381 "ahead by >= 3 m"
@@ -44,6 +45,61 @@ def intention_from_curvature(k) -> int:
     curvature of the window exceeds 0.10 1/m, else 2 right turn if the smallest is below -0.10, else 0 straight ahead
     (pinned to the reference's own method: tests/golden/relevant_lanelets.npz)"""
     return 1 if k.max() > 0.10 else 2 if k.min() < -0.10 else 0
+
+
+def caller_frame_table(cosy, path):
+    """the caller's curvilinear frame as the rule kernels read it (fo_spawn_rule_params_t::frame = 1, include/fo_hip.h): a row
+    per vertex p_i of the reference path -- x, y of p_i, s_i = cosy(p_i)[0], the polyline arc length of p_i (where the turn rule
+    asks cosy for its shifted line, spawn_locator.py:513-515,683), n_i = cart(s_i, 1) - cart(s_i, 0) --
+    from the two methods the reference calls on cosy_cl (spawn_locator.py:229,398).  Refused (ValueError naming the vertex):
+    a vertex that does not project or whose base point cart(s_i, 0) is more than 1 mm from p_i, s_i not strictly increasing,
+    n_i = 0.  Returns (table [n][6], fit): fit = the largest distance between cosy's cart(s_m, +-3) and the table's at the
+    midpoint s_m of every segment -- how far the object is from the model the device computes with"""
+    path = np.asarray(path, dtype=np.float64)
+    n = len(path)
+    cart = lambda s, d: np.asarray(cosy.convert_to_cartesian_coords(s, d), dtype=np.float64).reshape(-1)[:2]
+    tab = np.zeros((n, 6))
+    tab[:, :2] = path
+    for i in range(n):
+        x, y = float(path[i, 0]), float(path[i, 1])
+        try:
+            s = float(np.asarray(cosy.convert_to_curvilinear_coords(x, y), dtype=np.float64).reshape(-1)[0])
+            b0, b1 = cart(s, 0.0), cart(s, 1.0)
+        except Exception as e:      # noqa: BLE001 -- whatever the object raises outside its domain
+            raise ValueError(f"caller frame: reference path vertex {i} ({x}, {y}) does not project ({e})") from None
+        if i > 0 and not s > tab[i - 1, 2]:
+            raise ValueError(f"caller frame: s is not strictly increasing at reference path vertex {i} ({tab[i - 1, 2]} -> {s})")
+        if not math.hypot(b0[0] - x, b0[1] - y) <= 1e-3:
+            raise ValueError(f"caller frame: the base point of reference path vertex {i} is {math.hypot(b0[0] - x, b0[1] - y):.3g} m "
+                             "from the vertex (the frame must be based on the ego's reference path; keep frame: polyline)")
+        nv = b1 - b0
+        if nv[0] == 0.0 and nv[1] == 0.0:
+            raise ValueError(f"caller frame: the normal at reference path vertex {i} is zero")
+        tab[i, 2], tab[i, 4:6] = s, nv
+    tab[:, 3] = pathlength(path)
+    fit = 0.0
+    for i in range(n - 1):
+        sm = tab[i, 2] + 0.5 * (tab[i + 1, 2] - tab[i, 2])
+        for d in (-3.0, 3.0):
+            try:
+                q = cart(sm, d)
+            except Exception:       # noqa: BLE001 -- the object refuses a point of its own domain: nothing to compare
+                continue
+            fit = max(fit, math.hypot(*(q - frame_table_to_cart(tab, sm, d))))
+    return tab, fit
+
+
+def frame_table_to_cart(tab, s, d):
+    """(s, d) -> (x, y) through a caller-frame table: rl_cf_to_cart of csrc/fo_spawn_rules.hpp, operation for operation"""
+    n = len(tab)
+    if s < tab[0, 2] or s > tab[-1, 2]:
+        raise ValueError("s outside the caller frame's table")
+    k = int(min(np.searchsorted(tab[:, 2], s, side="right") - 1, n - 2))
+    r, r1 = tab[k], tab[k + 1]
+    lam = (s - r[2]) / (r1[2] - r[2])
+    bx, by = r[0] + lam * (r1[0] - r[0]), r[1] + lam * (r1[1] - r[1])
+    nx, ny = r[4] + lam * (r1[4] - r[4]), r[5] + lam * (r1[5] - r[5])
+    return np.array([bx + d * nx, by + d * ny])
 
 
 @dataclass
@@ -232,6 +288,13 @@ class SpawnLocator:
         self.mode = str(acc.get("mode", "rules"))                  # "rules" (the reference's semantics) | "cells" | "both"
         if self.mode not in ("cells", "rules", "both"):
             raise ValueError("accelerator.spawn.mode must be 'cells', 'rules' or 'both'")
+        # the curvilinear frame of the rule families: "polyline" (default) the polyline frame of the reference path; "caller"
+        # the caller's cosy_cl, sampled into a table at the path's vertices (_frame_setup) -- polyline while there is none
+        self.frame = str(acc.get("frame", "polyline"))
+        if self.frame not in ("polyline", "caller"):
+            raise ValueError("accelerator.spawn.frame must be 'polyline' or 'caller'")
+        self.frame_fit_m = None            # largest distance between the caller's frame and its table at the segment midpoints
+        self._frame_src, self._d_frame6 = None, None
         # capacity of the rule families' output: the maxima of the YAML are compared with '>' BEFORE appending and a dynamic
         # obstacle can yield a Car and a Bicycle (Q11, spawn_locator.py:212,304-309,365), so the three families emit up to
         # (max_dynamic + 2) + (max_static + 1) + 1 points -- never less room than that, whatever the YAML says
@@ -396,6 +459,25 @@ class SpawnLocator:
                           "refused (RuntimeError when it is read).  Use larger cells or spawn_points_behind_turn: False.")
         self._rules_ready = True
 
+    def _frame_setup(self):
+        """the table of the frame the rule families project through this step: (device table [n][6], frame code of
+        fo_spawn_rule_params_t).  With ``frame: caller`` and a ``cosy_cl``, the caller's frame at the path's vertices p_i
+        (include/fo_hip.h, d_path6): built from the object's two conversion methods when the object is
+        not the one the current table came from -- the same object step after step costs no call on it and no upload"""
+        cosy = getattr(self, "cosy_cl", None)
+        if getattr(self, "frame", "polyline") != "caller" or cosy is None:
+            return getattr(self, "_d_path6", None), 0
+        if cosy is not self._frame_src:
+            tab, fit = caller_frame_table(cosy, self.ref_path)
+            self._d_frame6 = torch.as_tensor(tab).to(self.device)
+            self._frame_src, self.frame_fit_m = cosy, fit
+            if fit > 1e-3:
+                import warnings
+                warnings.warn(f"SpawnLocator: the caller's frame is {fit:.3g} m from its table at the segment midpoints (d = +-3 m): "
+                              "between the path's vertices the spawn rules project through the table (base points and normals "
+                              "interpolated linearly in s), not through the object")
+        return self._d_frame6, 1
+
     def _nearest_vertex(self, s):
         """``np.argmin(np.abs(ref_s - s))`` (spawn_locator.py:684-687: the first index of the smallest distance) by bisection
         on the path's arc lengths -- this runs every planning step on the host"""
@@ -408,14 +490,22 @@ class SpawnLocator:
         return i - 1 if abs(sl[i - 1] - s) <= abs(sl[i] - s) else i
 
     def rule_params(self, ego_pos, ego_orientation, ego_pos_cl, ego_v):
-        """the step's scalars of the rule families (``fo_spawn_rule_params_t``): curvilinear ego position, ``s_threshold``
-        (spawn_locator.py:113), the reference window and the ego's intention from the curvature of the next 40 m of the
-        reference path (:678-741) -- a few host operations on cached tables, nothing is read from the device"""
+        """the step's scalars of the rule families (``fo_spawn_rule_params_t``); the table they go with: :meth:`rule_inputs`"""
+        return self.rule_inputs(ego_pos, ego_orientation, ego_pos_cl, ego_v)[0]
+
+    def rule_inputs(self, ego_pos, ego_orientation, ego_pos_cl, ego_v):
+        """(params, table) of the step: the scalars of the rule families (``fo_spawn_rule_params_t``) -- curvilinear ego position,
+        ``s_threshold`` (spawn_locator.py:113), the reference window and the ego's intention from the curvature of the next 40 m
+        of the reference path (:678-741) -- and the device table of the frame ``params.frame`` names, which goes to
+        ``fo_scene_spawn_rules`` / ``fo_step_t::d_path6`` with them.  A few host operations on cached tables, nothing is read from
+        the device"""
         from .utils.curvilinear import curvature
         if not getattr(self, "_rules_ready", False):
             self._rule_setup()
+        table, frame = self._frame_setup()
         if ego_pos_cl is None:
-            ego_pos_cl = self._cs.convert_to_curvilinear_coords(float(ego_pos[0]), float(ego_pos[1]))
+            cs = self.cosy_cl if frame else self._cs
+            ego_pos_cl = np.asarray(cs.convert_to_curvilinear_coords(float(ego_pos[0]), float(ego_pos[1]))).reshape(-1)
         s_ego = float(ego_pos_cl[0])
         i0, i1 = self._nearest_vertex(s_ego), self._nearest_vertex(s_ego + 40.0)   # :678-693
         intention = 0
@@ -434,7 +524,7 @@ class SpawnLocator:
         return N.SpawnRuleParams(float(ego_pos[0]), float(ego_pos[1]), float(ego_orientation), s_ego, float(ego_pos_cl[1]),
                                  s_ego + max(float(ego_v) * S_THRESHOLD_TIME, S_THRESHOLD_MIN), c["ped_width"], c["ped_length"],
                                  intention, i0, i1, c["behind_static"], c["behind_turn"], c["behind_dynamic"], c["max_static"],
-                                 c["max_dynamic"], 0 if n_dyn is None else n_dyn + 1, 0)
+                                 c["max_dynamic"], 0 if n_dyn is None else n_dyn + 1, frame), table
 
     def rule_obstacle_ptrs(self):
         """(O, corners, centres, headings, dimensions, flags, visibility) device pointers of this step's obstacles as the rule
@@ -460,13 +550,13 @@ class SpawnLocator:
             raise RuntimeError("SpawnLocator: call SensorModel.calc_visible_and_occluded_area first")
         if self.n_rule_points == 0:
             raise RuntimeError("SpawnLocator.queue_rules: spawn.mode 'cells' has no rule stage")
-        pr = self.rule_params(ego_pos, ego_orientation, ego_pos_cl, ego_v)
+        pr, tab = self.rule_inputs(ego_pos, ego_orientation, ego_pos_cl, ego_v)
         b = self.batch if self.batch is not None else self._batch_for_step()
         b.invalidate()
         O, corn, cen, oyaw, odims, ofl, ovis = self.rule_obstacle_ptrs()
         w, st = sm.window, N.current_stream(self._dev_index)
-        self.ctx.call("fo_scene_spawn_rules", sm.cell_class.data_ptr(), w.ix0, w.iy0, w.nx, w.ny, int(self._d_path6.shape[0]),
-                      self._d_path6.data_ptr(), O, corn, cen, oyaw, odims, ofl, ovis, C.byref(pr), b.n_rule_points,
+        self.ctx.call("fo_scene_spawn_rules", sm.cell_class.data_ptr(), w.ix0, w.iy0, w.nx, w.ny, int(tab.shape[0]),
+                      tab.data_ptr(), O, corn, cen, oyaw, odims, ofl, ovis, C.byref(pr), b.n_rule_points,
                       b.rule_points.data_ptr(), b.rule_n.data_ptr(), st)
         a0, s0, T = b.n_cell_agents, b.n_cell_agents * b.R, self.T
         self.ctx.call("fo_scene_spawn_rule_agents", b.n_rule_points, b.rule_points.data_ptr(), b.rule_n.data_ptr(), self.routes,

@@ -146,7 +146,9 @@ class PlanningStep:
                 raise RuntimeError("PlanningStep: the spawn rule families need the obstacles' headings and dimensions "
                                    "(SensorModel.upload_obstacles with an FOObstacles)")
             s.d_oyaw, s.d_odims = (q(rl[0]), q(rl[1])) if O else (None, None)
-            s.rule = sl.rule_params(ego_pos, yaw, ego_pos_cl, ego_v)
+            s.rule, tab = sl.rule_inputs(ego_pos, yaw, ego_pos_cl, ego_v)
+            s.n_path6, s.d_path6 = int(tab.shape[0]), tab.data_ptr()      # (the table of the frame s.rule names)
+            self._table = tab                                              # (kept alive while the structure points at it)
         self.batch.invalidate()
         skip = sm._edge_skip_for(sm.enclosed_hole_rings(ego_pos, yaw))
         s.d_edge_skip = None if skip is None else skip.data_ptr()

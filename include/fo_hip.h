@@ -285,17 +285,25 @@ int fo_scene_set_topology(fo_ctx *ctx, int P, const double *h_left0, const int32
  * (bit0), dynamic role (bit2), neither bicycle nor pedestrian (bit3 clear) -- or 0 = not told (every obstacle is assumed to).  The
  * rule's helper workgroups (fifteen per obstacle, a CU each) are launched for that many obstacles only -- the first ones in list
  * order whose flags qualify; one beyond the count is treated as if the rule did not apply to it -- and for none at all when no
- * obstacle qualifies: the flags are the caller's own data, whether such an obstacle is visible stays a decision of the device. */
+ * obstacle qualifies: the flags are the caller's own data, whether such an obstacle is visible stays a decision of the device.
+ * frame: the table d_path6 holds -- 0 the polyline frame of the reference path, 1 a table sampled from the caller's own
+ * curvilinear frame (see d_path6 below); any other value is FO_E_ARG.  (It was a reserved zero word: callers that leave it 0
+ * get what they got before.) */
 typedef struct {
   double ego_x, ego_y, ego_yaw, ego_s, ego_d, s_threshold;
   double ped_width, ped_length;
   int32_t intention, win_i0, win_i1;
   int32_t behind_static, behind_turn, behind_dynamic, max_static, max_dynamic;
-  int32_t n_dynamic_plus1, reserved_;
+  int32_t n_dynamic_plus1, frame;
 } fo_spawn_rule_params_t;
 
 /* Per step, after fo_scene_visibility on the same stream.  d_cls + window: that call's cell classes.  d_path6 [n_path][6]:
- * reference path table x, y, arc length, segment length, unit tangent (last row: tangent unused).  Obstacles at this
+ * with params->frame = 0, the polyline frame of the reference path: x, y, arc length, segment length, unit tangent (last row:
+ * tangent unused).  With params->frame = 1, the caller's frame sampled at the path's vertices p_i: x, y of p_i (the base point),
+ * the caller's s_i (strictly increasing), the polyline arc length of p_i from the path's first vertex (the s at which the turn
+ * rule asks the caller's frame for its shifted line, as the reference does), the caller's normal n_i = cart(s_i, 1) - cart(s_i, 0)
+ * (not normalised); between two rows base point and normal are interpolated linearly in s, (s, d) <-> b(s) + d n(s), a point
+ * without a root of cross(q - b, n) = 0 on any segment is outside the domain.  Obstacles at this
  * step: d_ocorn [O][4][2], d_ocen [O][2], d_oyaw [O], d_odims [O][2] (length, width), d_oflags [O] (bit0 present, bit1
  * occludes, bit2 dynamic role, bit3 type bicycle or pedestrian), d_obst_vis [O] = visible_objects_timestep of
  * fo_scene_visibility.  Output d_out [max_out][8]: type (FO_TYPE_*), x, y, orientation (NaN = to be derived,
