@@ -102,7 +102,7 @@ int fo_sweep_check(fo_ctx *ctx, void *stream) {
 // candidate cells are flagged inside the compaction of the occluded cells, and the phantom prediction kernels write their
 // slots' rows of the sweep's agent table themselves.
 // (FO_STEP_STAGES=1 in the environment: the plain sequence of stage calls, for A/B runs.)
-int fo_step_run(fo_ctx *ctx, const fo_step_t *p, void *stream) {
+static int fo_step_run_(fo_ctx *ctx, const fo_step_t *p, void *stream) {
   if (!ctx || !p) return fo_fail(ctx, FO_E_ARG, "fo_step_run: null argument");
   int rc;
   const char *e_stages = fo_getenv(fo_env_any("FO_STEP_"), "FO_STEP_STAGES");   // (every call: tests switch it at run time)
@@ -123,6 +123,13 @@ int fo_step_run(fo_ctx *ctx, const fo_step_t *p, void *stream) {
   if ((rc = fo_step_stage_obstacles_(ctx, p, (hipStream_t)stream))) return rc;
   rc = fo_step_body_(ctx, p, stream, stages, cells, rules, slots, slot0, cell_agents);
   if (rc == FO_OK) rc = fo_step_queue_mirror_(ctx, p, (hipStream_t)stream, !stages && fo_step_direct_mirror_(ctx, p) != nullptr);
+  return rc;
+}
+
+// a step that failed before its visibility stage leaves no occlusion memory armed for a later call
+int fo_step_run(fo_ctx *ctx, const fo_step_t *p, void *stream) {
+  const int rc = fo_step_run_(ctx, p, stream);
+  if (rc != FO_OK && ctx) (void)fo_scene_set_occlusion_memory(ctx, nullptr);
   return rc;
 }
 

@@ -102,6 +102,9 @@ struct Scene {
   size_t cap_ofar = 0;
   int *d_rule_lab = nullptr, *d_rule_cnt = nullptr;   // dynamic rule: [O][97 x 97] lattice labels, [O] arrival counters
   size_t cap_rule_lab = 0, cap_rule_cnt = 0;
+  // occlusion memory (fo_scene_set_occlusion_memory): armed for the next visibility stage only, caller-owned buffers
+  bool om_armed = false;
+  fo_occlusion_memory_t om{};
 };
 
 Scene *scene_of(fo_ctx *ctx) {
@@ -1392,6 +1395,86 @@ __global__ __launch_bounds__(64) void fo_spawn_predict_kernel(
   PRED_TICK(9);
 }
 
+// ------------------------------------------------------------------------------------------------ occlusion memory
+// An extension, not part of the reference: a cell the settled classes call occluded stays occluded only
+// if a hidden road user moving at the caller's v_max could have reached it since the previous step, i.e. if some cell
+// g + d, d in D = {dx^2 + dy^2 <= r2}, was "maybe occupied" then (P_{k-1}: H of the previous step inside its window, the
+// road bit outside it, 0 off the raster).  One thread per window cell on 64 x 4 tiles (a wave = 64 cells of one row); the
+// tile's P_{k-1} with a halo of h = floor(sqrt(r2)) <= FO_OCCLUSION_MEMORY_MAX_HALO cells is staged in LDS, and only a
+// block with an occluded cell stages it.  Runs after the settle kernel on the same stream and before the compaction:
+// every class byte is owned by one thread here, so a plain byte store clears bit 4; the compaction's per-256-cell counts
+// are lowered with at most two atomics per wave (a 64-cell row segment spans at most two 256-cell blocks).
+constexpr int OM_TX = 64, OM_TY = 4, OM_H = FO_OCCLUSION_MEMORY_MAX_HALO;
+struct OccMemArgs {
+  int r2 = 0, h = 0, reset = 1;
+  int pix0 = 0, piy0 = 0, pnx = 0, pny = 0;
+  const uint8_t *prev = nullptr;
+  uint8_t *cur = nullptr;
+};
+__global__ __launch_bounds__(256) void fo_occlusion_memory_kernel(const uint8_t *__restrict__ raster, int rnx, int rny, int ix0,
+                                                                  int iy0, int nx, int ny, uint8_t *__restrict__ cls,
+                                                                  uint8_t *__restrict__ occ_flag, int32_t *__restrict__ blk,
+                                                                  OccMemArgs a) {
+  __shared__ uint8_t tile[(OM_TX + 2 * OM_H) * (OM_TY + 2 * OM_H)];
+  __shared__ int half_w[2 * OM_H + 1];   // row dy of D: |dx| <= half_w[dy + h] (-1: empty row)
+  const int lane = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int ix = blockIdx.x * OM_TX + lane, iy = blockIdx.y * OM_TY + ty;
+  const bool in = ix < nx && iy < ny;
+  const int idx = iy * nx + ix;
+  const uint8_t c = in ? cls[idx] : 0;
+  const bool occ = in && (c & 4);
+  int hit = 1;   // reset: P_{k-1} = road, and an occluded cell is a road cell with (0, 0) in D
+  if (!a.reset && __syncthreads_or(occ)) {   // (a.reset is uniform over the grid)
+    const int h = a.h, tw = OM_TX + 2 * h, th = OM_TY + 2 * h;
+    const int qx0 = ix0 + blockIdx.x * OM_TX - h, qy0 = iy0 + blockIdx.y * OM_TY - h;   // raster cell of tile[0]
+    for (int t = threadIdx.x; t < tw * th; t += 256) {
+      const int qx = qx0 + t % tw, qy = qy0 + t / tw;
+      const int px = qx - a.pix0, py = qy - a.piy0;
+      uint8_t v = 0;
+      if (px >= 0 && px < a.pnx && py >= 0 && py < a.pny) v = a.prev[(size_t)py * a.pnx + px];
+      else if (qx >= 0 && qx < rnx && qy >= 0 && qy < rny) v = raster[(size_t)qy * rnx + qx] ? 1 : 0;
+      tile[t] = v;
+    }
+    for (int t = threadIdx.x; t <= 2 * h; t += 256) {
+      const int rem = a.r2 - (t - h) * (t - h);
+      int w = -1;
+      if (rem >= 0) {   // integer square root (the float guess corrected both ways)
+        w = (int)sqrt((double)rem);
+        while (w * w > rem) --w;
+        while ((w + 1) * (w + 1) <= rem) ++w;
+      }
+      half_w[t] = w;
+    }
+    __syncthreads();
+    if (occ) {
+      hit = 0;
+      for (int dy = 0; dy <= 2 * h && !hit; ++dy) {
+        const int w = half_w[dy];
+        const uint8_t *row = tile + (ty + dy) * tw + lane + h;
+        for (int dx = -w; dx <= w; ++dx)
+          if (row[dx]) { hit = 1; break; }
+      }
+    }
+  }
+  const uint8_t H = (c & 2) ? 0 : (c & 4) ? (uint8_t)hit : (uint8_t)(c & 1);
+  if (in) a.cur[idx] = H;
+  const bool clear = occ && !H;
+  if (clear) {
+    cls[idx] = (uint8_t)(c & ~4);
+    occ_flag[idx] = 0;
+  }
+  const unsigned long long m = __ballot(clear);
+  if (m) {   // (wave-uniform)
+    const int b0 = __shfl(idx >> 8, __builtin_ctzll(m));
+    const unsigned long long m0 = __ballot(clear && (idx >> 8) == b0), m1 = m & ~m0;
+    const int b1 = __shfl(idx >> 8, m1 ? __builtin_ctzll(m1) : 0);
+    if (lane == 0) {
+      atomicSub(&blk[b0], __popcll(m0));
+      if (m1) atomicSub(&blk[b1], __popcll(m1));
+    }
+  }
+}
+
 int ensure_cells(fo_ctx *ctx, Scene *sc, size_t cells) {
   int rc;
   if ((rc = fo_reserve(ctx, &sc->d_flags, &sc->cap_cells, cells))) return rc;
@@ -1667,6 +1750,8 @@ static int scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head
   if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_visibility: call fo_scene_set_map first");
   Scene *sc = (Scene *)ctx->scene;
   sc->cand_flags_ready = false;
+  const bool om_on = sc->om_armed;   // (fo_scene_set_occlusion_memory arms this call only)
+  sc->om_armed = false;
   FanArgs fan;
   if (fan_in) fan = *fan_in;
   if (n_rays < 4 || !d_dirs || !d_range || !d_hit_id || O < 0 || (O > 0 && (!d_ocorn || !d_ocen || !d_oflags)) ||
@@ -1682,6 +1767,9 @@ static int scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head
   }
   const int cells = win_nx * win_ny;
   if (probes && O > cells) return fo_fail(ctx, FO_E_ARG, "fo_scene_visibility: more obstacles than window cells");
+  if (om_on && sc->om.cur_bytes < (int64_t)cells)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_visibility: the occlusion memory's buffer holds %lld bytes, the window %d cells",
+                   (long long)sc->om.cur_bytes, cells);
   if ((rc = ensure_cells(ctx, sc, (size_t)cells))) return rc;
   fo_prep_args_t prep = prep_in ? *prep_in : fo_prep_args_t();
   // one wave per ray / probe / undecided cell where the soup is a single group of chunk boxes (see fo_rays_kernel) and the
@@ -1722,6 +1810,20 @@ static int scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head
     else { if (one_wave) FO_LAUNCH_SETTLE(false, 1); else FO_LAUNCH_SETTLE(false, RAY_WAVES); }
 #undef FO_LAUNCH_SETTLE
   }
+  if (om_on) {   // after the last writer of the classes, before the compaction reads the flags and counts
+    const fo_occlusion_memory_t &m = sc->om;
+    OccMemArgs a;
+    a.r2 = m.r2; a.reset = m.reset ? 1 : 0; a.cur = m.d_cur;
+    if (!a.reset) {
+      a.h = (int)sqrt((double)m.r2);
+      while (a.h * a.h > m.r2) --a.h;
+      while ((a.h + 1) * (a.h + 1) <= m.r2) ++a.h;
+      a.pix0 = m.prev_ix0; a.piy0 = m.prev_iy0; a.pnx = m.prev_nx; a.pny = m.prev_ny; a.prev = m.d_prev;
+    }
+    hipLaunchKernelGGL(fo_occlusion_memory_kernel, dim3((win_nx + OM_TX - 1) / OM_TX, (win_ny + OM_TY - 1) / OM_TY), dim3(256), 0, s,
+                       sc->map->d_raster, sc->map->rnx, sc->map->rny, win_ix0, win_iy0, win_nx, win_ny, d_cls, sc->d_flags,
+                       sc->d_blk, a);
+  }
   FO_HIP_TRY(ctx, hipGetLastError());
   if (sf_in) {
     if ((rc = fo_reserve(ctx, &sc->d_flags2, &sc->cap_cells2, (size_t)cells))) return rc;
@@ -1744,6 +1846,29 @@ int fo_scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head_x, 
   return scene_visibility(ctx, ego_x, ego_y, head_x, head_y, r, full_circle, exact_cells, n_rays, d_dirs, d_rmax, d_half, d_edge_skip,
                           O, d_ocorn, d_ocen, d_oflags, win_ix0, win_iy0, win_nx, win_ny, d_range, d_hit_id, d_ring, d_obst_vis,
                           d_cls, d_occ_idx, d_n_occ, stream, nullptr, nullptr);
+}
+
+int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om) {
+  if (!ctx) return FO_E_ARG;
+  if (ctx->scene) ((Scene *)ctx->scene)->om_armed = false;
+  if (!om) return FO_OK;   // off
+  if (!ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_occlusion_memory: call fo_scene_set_map first");
+  Scene *sc = (Scene *)ctx->scene;
+  constexpr int cap = FO_OCCLUSION_MEMORY_MAX_HALO;
+  if (om->r2 < 0 || om->r2 > cap * cap)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: r2 = %d outside [0, %d] (a reach of at most %d cells)", om->r2,
+                   cap * cap, cap);
+  if (!om->d_cur || om->cur_bytes < 1) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: no buffer for this step");
+  if (!om->reset) {
+    if (!om->d_prev || om->d_prev == om->d_cur || om->prev_nx < 1 || om->prev_ny < 1)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: the previous step needs a window and a buffer of its own");
+    if (om->prev_bytes < (int64_t)om->prev_nx * om->prev_ny)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: the previous buffer holds %lld bytes, its window %d x %d cells",
+                     (long long)om->prev_bytes, om->prev_nx, om->prev_ny);
+  }
+  sc->om = *om;
+  sc->om_armed = true;
+  return FO_OK;
 }
 
 int fo_scene_future_visibility(fo_ctx *ctx, int M, int T, const double *d_x, const double *d_y, int t_stride, int n_rays,

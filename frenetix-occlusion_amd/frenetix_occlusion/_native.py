@@ -33,6 +33,7 @@ EXPORTS = [
     "fo_scene_set_map", "fo_scene_share_map", "fo_scene_set_edge_lines", "fo_scene_set_routes", "fo_scene_map_info", "fo_scene_copy_raster", "fo_scene_fan", "fo_scene_visibility", "fo_scene_future_visibility", "fo_scene_spawn",
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
+    "fo_scene_set_occlusion_memory",
 ]
 
 
@@ -57,6 +58,15 @@ class SpawnRuleParams(C.Structure):       # fo_spawn_rule_params_t
 
 class RuleAgentTypes(C.Structure):       # fo_rule_agent_types_t: index 0 Car, 1 Bicycle, 2 Pedestrian
     _fields_ = [(n, C.c_double * 3) for n in ("speed", "raw_l", "raw_w", "infl_l", "infl_w")]
+
+
+OCCLUSION_MEMORY_MAX_HALO = 32     # FO_OCCLUSION_MEMORY_MAX_HALO: the largest reach (cells) the memory kernel stages
+
+
+class OcclusionMemory(C.Structure):     # fo_occlusion_memory_t
+    _fields_ = [("r2", C.c_int32), ("reset", C.c_int32), ("prev_ix0", C.c_int32), ("prev_iy0", C.c_int32),
+                ("prev_nx", C.c_int32), ("prev_ny", C.c_int32), ("d_prev", C.c_void_p), ("d_cur", C.c_void_p),
+                ("prev_bytes", C.c_int64), ("cur_bytes", C.c_int64)]
 
 
 SPAWN_CELLS, SPAWN_RULES, SPAWN_BOTH = 0, 1, 2
@@ -158,6 +168,7 @@ def load():
                                                                                           dp, ip, vp])
     lib.fo_scene_set_centerlines.argtypes = [vp, C.c_int, ip, dp]
     lib.fo_scene_set_shadow_length.argtypes = [vp, C.c_double]
+    lib.fo_scene_set_occlusion_memory.argtypes = [vp, C.POINTER(OcclusionMemory)]
     lib.fo_scene_spawn_rule_agents.argtypes = ([vp, C.c_int, dp, ip, C.c_int, C.POINTER(RuleAgentTypes), C.c_int, dp, C.c_int]
                                                + [D] * 3 + [dp] * 8 + [ip, ip, vp])
     for name in EXPORTS:

@@ -33,6 +33,18 @@ from .spawn_locator import SpawnLocator
 from .utils.fo_obstacle import FOObstacles
 
 
+def occlusion_memory_config(acc):
+    """``accelerator.occlusion_memory`` of a loaded configuration with its defaults: ``enabled`` False, ``v_max`` 13.9 m/s,
+    ``margin`` None (= sqrt(2) cell sizes)"""
+    om = (acc or {}).get("occlusion_memory") or {}
+    margin = om.get("margin")
+    out = {"enabled": bool(om.get("enabled", False)), "v_max": float(om.get("v_max", 13.9)),
+           "margin": None if margin is None else float(margin)}
+    if not out["v_max"] >= 0.0 or (out["margin"] is not None and not out["margin"] >= 0.0):
+        raise ValueError("accelerator.occlusion_memory: v_max and margin must be >= 0")
+    return out
+
+
 class FOInterface:
     def __init__(self, scenario, reference_path, vehicle_params, dt, config_path=None, cosy_cl=None, share_map_with=None):
         """Signature of the reference (interface.py:69) plus ``share_map_with``: another FOInterface of the same scenario
@@ -99,8 +111,19 @@ class FOInterface:
                                           dt=self.dt)
         self.metrics = Metric(self.config["metrics"], self.vehicle_params, self.agent_manager, dt=self.dt,
                               device=self.device.index, ctx=self.ctx, list_storage=str(acc.get("list_storage", "f64")))
+        # EXTENSION (accelerator.occlusion_memory, off by default): occluded cells seen empty since a hidden road user
+        # could have got there are no longer occluded (SensorModel.enable_occlusion_memory)
+        self.occlusion_memory = occlusion_memory_config(acc)
+        if self.occlusion_memory["enabled"]:
+            self.sensor_model.enable_occlusion_memory(v_max=self.occlusion_memory["v_max"],
+                                                      margin=self.occlusion_memory["margin"], dt=self.dt)
 
     # ---------------------------------------------------------------------------------------- reference API
+    def reset_occlusion_memory(self):
+        """EXTENSION: the next evaluate_scenario forgets what was seen before (its occluded area is that of a step without
+        occlusion memory); a no-op while ``accelerator.occlusion_memory.enabled`` is False"""
+        self.sensor_model.reset_occlusion_memory()
+
     def set_coordinate_system(self, cosy_cl):
         self.cosy_cl = cosy_cl
         self.spawn_locator.cosy_cl = cosy_cl
@@ -163,7 +186,7 @@ class FOInterface:
             # reference's visible-object bookkeeping -- visible_objects_timestep, current_visible, obstacle_occlusions, the
             # visible multipolygon -- is applied when somebody looks at it, or when the obstacles move on to the next step)
             sm.stage_obstacles(self.fo_obstacles)
-            self._scene_step.run(self.ego_pos, self.ego_orientation, ego_v, self.ego_pos_cl)
+            self._scene_step.run(self.ego_pos, self.ego_orientation, ego_v, self.ego_pos_cl, timestep=self.timestep)
             sm.adopt_step(self.ego_pos, self.ego_orientation)
             sm.defer_visible_objects(self.timestep, self.fo_obstacles)
             t0 = self._tick("visibility_ms", t0)

@@ -8,6 +8,7 @@ entry, same attributes afterwards (``visible_area``, ``occluded_area``, ``visibl
 therefore a :class:`VisibleArea` (ring polygon + cell mask) instead of a shapely geometry (documented deviation,
 SURVEY 8b).  All arithmetic happens in libfo_hip.so; numpy here only packs small inputs.
 """
+import ctypes as C
 import math
 from dataclasses import dataclass
 from typing import Optional
@@ -146,6 +147,55 @@ class CellWindow:
         return np.where(ok, iy * self.nx + ix, -1)
 
 
+def occlusion_memory_r2(v_max, dt_s, margin, cell_size):
+    """R2 = floor(rho^2 / cs^2), rho = v_max * dt_s + margin, in float64: the reach of the occlusion memory as a squared
+    cell count, so that device and host model decide membership in D = {dx^2 + dy^2 <= R2} in integers"""
+    rho = float(v_max) * float(dt_s) + float(margin)
+    return int(math.floor((rho * rho) / (float(cell_size) * float(cell_size))))
+
+
+class OcclusionMemoryPlan:
+    """Host side of the occlusion memory, without device state: what the next step hands the device.
+
+    :meth:`next_step` returns ``(r2, reason)``: ``reason`` None = a memory step with reach ``r2``; otherwise the step is a
+    reset (the previous step's hidden set is replaced by the road raster) and ``reason`` says why -- ``"first"`` (no
+    previous step), ``"explicit"`` (:meth:`reset`), ``"time"`` (the timestep did not increase, or no timestep was given) or
+    ``"reach"`` (``sqrt(R2)`` beyond the kernel's halo, ``OCCLUSION_MEMORY_MAX_HALO`` cells).  :meth:`commit` records a step
+    that ran; a step given no timestep leaves the recorded timestep as it was (the next step's Δt counts from the last one
+    that had a timestep, a longer reach, never a shorter one)."""
+
+    def __init__(self, v_max=13.9, margin=None, cell_size=0.5, dt=0.1, max_halo=None):
+        self.v_max, self.cell_size, self.dt = float(v_max), float(cell_size), float(dt)
+        self.margin = math.sqrt(2.0) * self.cell_size if margin is None else float(margin)
+        if not (self.v_max >= 0.0 and self.margin >= 0.0 and self.cell_size > 0.0 and self.dt > 0.0):
+            raise ValueError("occlusion memory: v_max >= 0, margin >= 0, cell_size > 0 and dt > 0")
+        self.max_halo = N.OCCLUSION_MEMORY_MAX_HALO if max_halo is None else int(max_halo)
+        self.timestep = None          # timestep of the last committed step that had one
+        self.has_prev = False         # a previous step's hidden set exists
+        self._explicit = False
+
+    def reset(self):
+        self._explicit = True
+
+    def next_step(self, timestep):
+        if self._explicit:
+            return 0, "explicit"
+        if not self.has_prev:
+            return 0, "first"
+        if timestep is None or self.timestep is None or int(timestep) <= int(self.timestep):
+            return 0, "time"
+        r2 = occlusion_memory_r2(self.v_max, (int(timestep) - int(self.timestep)) * self.dt, self.margin, self.cell_size)
+        if r2 > self.max_halo * self.max_halo:
+            return 0, "reach"
+        return r2, None
+
+    def commit(self, timestep):
+        self._explicit = False
+        self.has_prev = True
+        if timestep is not None:
+            self.timestep = int(timestep)
+
+
 class VisibleArea:
     """What ``evaluate_scenario`` hands back instead of a shapely geometry: the visible polygon's ring (device
     tensor [n_rays, 2]; for an open fan the ego position closes the polygon) and the per-cell classes."""
@@ -252,6 +302,13 @@ class SensorModel:
         self.ego_orientation = None
         self.window = None
         self.cell_class = None
+        # occlusion memory (an extension, off unless enable_occlusion_memory is called): host plan, ping-pong buffers of H
+        self._om_plan = None
+        self._om_buf = None
+        self._om_cur = 0               # index of the buffer the next step writes
+        self._om_prev_window = None    # window of the other buffer's H
+        self._om_host = None
+        self.occlusion_memory_reset_reason = None
         if share_map_with is not None:
             self._share_map(share_map_with)
         else:
@@ -366,6 +423,70 @@ class SensorModel:
         lan, kind = np.array(lan or [0], dtype=np.int32), np.array(kind or [0], dtype=np.uint8)
         self.ctx.call("fo_scene_set_topology", P, left0.ctypes.data, pred0.ctypes.data, adjl.ctypes.data, len(inters),
                       off.ctypes.data, lan.ctypes.data, kind.ctypes.data)
+
+    # ---- occlusion memory (extension)
+    def enable_occlusion_memory(self, enabled=True, v_max=13.9, margin=None, dt=0.1):
+        """keep road cells seen empty out of the occluded area until a hidden road user moving at ``v_max`` (m/s) could
+        have reached them; ``margin`` (m, None = sqrt(2) cell sizes) widens the reach, ``dt`` is the length of one
+        timestep (s).  Every step with a timestep then advances the memory; the first step after this call is a reset."""
+        if not enabled:
+            self._om_plan, self._om_buf, self._om_prev_window, self._om_host = None, None, None, None
+            self.occlusion_memory_reset_reason = None
+            return
+        self._om_plan = OcclusionMemoryPlan(v_max, margin, self.cell_size, dt)
+        self._om_prev_window, self._om_host = None, None
+
+    @property
+    def occlusion_memory_enabled(self):
+        return self._om_plan is not None
+
+    def reset_occlusion_memory(self):
+        """forget what was seen: the next step's occluded cells are those of a step without memory"""
+        if self._om_plan is not None:
+            self._om_plan.reset()
+
+    @property
+    def occlusion_memory_hidden(self):
+        """H of the last step (numpy uint8 [ny, nx] over ``self.window``: 1 = a hidden road user may be in the cell), read
+        from the device when first looked at; None while the memory is off or before its first step"""
+        if self._om_plan is None or self._om_prev_window is None:
+            return None
+        if self._om_host is None:
+            w = self._om_prev_window
+            self._om_host = self._om_buf[1 - self._om_cur][:w.nx * w.ny].view(w.ny, w.nx).cpu().numpy()
+        return self._om_host
+
+    def _occlusion_memory_arm(self, w, timestep):
+        """arm the context's next visibility stage (fo_scene_set_occlusion_memory); returns the commit to call once the
+        stage has been queued, or None while the memory is off"""
+        plan = self._om_plan
+        if plan is None:
+            return None
+        cells = w.nx * w.ny
+        if self._om_buf is None or self._om_buf[0].numel() < cells:
+            if self._om_buf is not None:
+                torch.cuda.current_stream(self.device).synchronize()   # (a step in flight may still read the old pair)
+            self._om_buf = [torch.zeros(cells, dtype=torch.uint8, device=self.device) for _ in range(2)]
+            self._om_prev_window = None
+            plan.has_prev = False
+        r2, reason = plan.next_step(timestep)
+        cur, prev = self._om_buf[self._om_cur], self._om_buf[1 - self._om_cur]
+        pw = self._om_prev_window
+        m = N.OcclusionMemory(r2=r2, reset=1 if reason else 0, d_cur=cur.data_ptr(), cur_bytes=cur.numel())
+        if reason is None:
+            m.prev_ix0, m.prev_iy0, m.prev_nx, m.prev_ny = pw.ix0, pw.iy0, pw.nx, pw.ny
+            m.d_prev, m.prev_bytes = prev.data_ptr(), prev.numel()
+        self.ctx._check(self.ctx._lib.fo_scene_set_occlusion_memory(self.ctx._h, C.byref(m)))
+
+        def commit():
+            plan.commit(timestep)
+            self._om_prev_window, self._om_cur, self._om_host = w, 1 - self._om_cur, None
+            self.occlusion_memory_reset_reason = reason
+        return commit
+
+    def _occlusion_memory_disarm(self):
+        if self._om_plan is not None:
+            self.ctx._check(self.ctx._lib.fo_scene_set_occlusion_memory(self.ctx._h, None))
 
     def road_raster(self):
         nx, ny = self.raster_dims
@@ -499,10 +620,11 @@ class SensorModel:
             self._skip_key = rings
         return self._edge_skip
 
-    def launch(self, ego_pos, ego_orientation, dirs=None, rmax=None, half=None):
+    def launch(self, ego_pos, ego_orientation, dirs=None, rmax=None, half=None, timestep=None):
         """queue the visibility kernels for one ego pose on the current stream; no host synchronisation.
         Obstacles are the ones of the last ``upload_obstacles``; ``dirs`` / ``rmax`` / ``half`` (device tensors, see
-        :meth:`fan`) default to the fan about ``ego_orientation``."""
+        :meth:`fan`) default to the fan about ``ego_orientation``.  ``timestep``: advances the occlusion memory when it is
+        on (None: a reset step)."""
         self.ego_pos = np.asarray(ego_pos, dtype=np.float64)
         self.ego_orientation = float(ego_orientation)
         full = self.sensor_angle >= 359.9
@@ -514,12 +636,15 @@ class SensorModel:
         b = self._buffers(w, O)
         p = lambda t: t.data_ptr() if t is not None else None
         hx, hy = math.cos(self.ego_orientation), math.sin(self.ego_orientation)
+        commit = self._occlusion_memory_arm(w, timestep)
         self.ctx.call("fo_scene_visibility", float(self.ego_pos[0]), float(self.ego_pos[1]), hx, hy,
                       self.sensor_radius, 1 if full else 0, 1 if self.cell_visibility == "exact" else 0, self.n_rays,
                       p(dirs), p(rmax), p(half), p(skip), O, p(d_corn),
                       p(d_cen), p(d_flags),
                       w.ix0, w.iy0, w.nx, w.ny, p(b["rng"]), p(b["hit"]), p(b["ring"]), p(b["ovis"]), p(b["cls"]),
                       p(b["occ"]), p(b["n_occ"]), N.current_stream(self._dev_index))
+        if commit is not None:
+            commit()
         self.window = w
         self.dirs, self.rmax, self.half_dirs, self.edge_skip = dirs, rmax, half, skip
         self.range, self.hit_id, self.cell_class = b["rng"], b["hit"], b["cls"]
@@ -569,7 +694,7 @@ class SensorModel:
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""
         self.timestep = timestep
         _, _, _, O = self.upload_obstacles(obstacles)
-        self.launch(ego_pos, ego_orientation)
+        self.launch(ego_pos, ego_orientation, timestep=timestep)
         return self.read_visible_objects(timestep, obstacles)
 
     def adopt_step(self, ego_pos, ego_orientation):

@@ -114,9 +114,10 @@ class PlanningStep:
         self._buf = buf
         return s
 
-    def run(self, ego_pos, ego_orientation, ego_v, ego_pos_cl=None) -> SweepResult:
+    def run(self, ego_pos, ego_orientation, ego_v, ego_pos_cl=None, timestep=None) -> SweepResult:
         """queue one planning step on the current stream; returns the (reused) device outputs.  ``ego_pos_cl``: the ego's
-        curvilinear position (s, d) for the spawn rule families (default: its projection on the reference path)"""
+        curvilinear position (s, d) for the spawn rule families (default: its projection on the reference path).
+        ``timestep``: advances the sensor model's occlusion memory when that is on (None: the step is a reset step)"""
         sm, sl = self.sm, self.sl
         yaw = float(ego_orientation)
         w = sm._window_for(ego_pos)
@@ -155,7 +156,10 @@ class PlanningStep:
         s.ego_yaw, s.ego_x, s.ego_y, s.head_x, s.head_y = yaw, float(ego_pos[0]), float(ego_pos[1]), math.cos(yaw), math.sin(yaw)
         s.win_ix0, s.win_iy0 = w.ix0, w.iy0
         s.max_dist = sl.max_distance(ego_v)
+        commit = sm._occlusion_memory_arm(w, timestep)
         self.ctx._check(self.ctx._lib.fo_step_run(self.ctx._h, C.byref(s), N.current_stream(sm._dev_index)))
+        if commit is not None:
+            commit()
         sm._obst_host = None                         # (consumed: the rows are in the context's pinned ring)
         # the stage objects see the step as if they had queued it themselves
         sm.window, sm.ego_pos, sm.ego_orientation, sm.edge_skip = w, ego_pos, yaw, skip

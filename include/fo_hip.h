@@ -231,6 +231,27 @@ int fo_scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head_x, 
                         int32_t *d_hit_id, double *d_ring, uint8_t *d_obst_vis, uint8_t *d_cls, int32_t *d_occ_idx,
                         int32_t *d_n_occ, void *stream);
 
+/* EXTENSION, not part of the reference: occlusion memory.  Arms `ctx` for its NEXT visibility stage only
+ * (fo_scene_visibility, or the visibility part of fo_step_run; NULL or no call = off: no launch, no buffer touched).  That
+ * stage then keeps a settled occluded cell g occluded only if a hidden road user could have reached it since the previous
+ * step: H(g) = 0 if visible; if occluded, 1 iff P(g + d) = 1 for some d with dx^2 + dy^2 <= r2; else the road bit.
+ * P = H of the previous step inside its window (prev_*), the road raster outside it, 0 off the raster; reset != 0 makes
+ * P = the road raster everywhere (the classes are then those of an unarmed stage).  Where H = 0 bit 4 of the class and the
+ * cell's entry in the occluded list go away; H [win_ny][win_nx] (uint8 0 / 1) is written to d_cur, which the caller passes
+ * as d_prev one step later (ping-pong: d_prev != d_cur).  One launch between the settlement and the compaction.
+ * FO_E_ARG: r2 outside [0, FO_OCCLUSION_MEMORY_MAX_HALO^2], no d_cur, or (reset == 0) no d_prev / a d_prev smaller than
+ * prev_nx * prev_ny bytes; the visibility stage returns FO_E_ARG when cur_bytes < win_nx * win_ny. */
+#define FO_OCCLUSION_MEMORY_MAX_HALO 32
+typedef struct {
+  int32_t r2;                                   /* reach in cells, squared and floored: D = {(dx, dy) : dx^2 + dy^2 <= r2} */
+  int32_t reset;                                /* != 0: P = road raster (first step, time going backwards, ...) */
+  int32_t prev_ix0, prev_iy0, prev_nx, prev_ny; /* window of d_prev (unread when reset) */
+  const uint8_t *d_prev;                        /* [prev_ny][prev_nx] H of the previous step (unread when reset) */
+  uint8_t *d_cur;                               /* H of this step, [win_ny][win_nx] */
+  int64_t prev_bytes, cur_bytes;                /* capacities of d_prev / d_cur */
+} fo_occlusion_memory_t;
+int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om);
+
 /* EXTENSION, not part of the reference: how much of the currently occluded area each candidate trajectory
  * will come to see.  d_x / d_y [M][T] as for fo_sweep_run; pose (m, k) = sample k * t_stride, K = ceil(T / t_stride).
  * From every pose a full fan of n_rays (<= 768: the 720-ray fan of the visibility stage fits) rays of length r along d_dirs [n_rays][2] (world-aligned, counter-
