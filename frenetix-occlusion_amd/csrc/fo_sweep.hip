@@ -226,6 +226,18 @@ __device__ __forceinline__ double fo_fma3(double a, double b, double c) {
 }
 
 __device__ __forceinline__ double fo_round3(double v) { return __builtin_rint(v * 1000.0) / 1000.0; }  // np.round(v,3)
+// Squared distance of the CP gate (collision_probability.py:49-67,75): the nearest of the three means mean + j dev,
+// j = 0, +1, -1, to the ego sample, in the reference's order -- the mean is displaced first, then the ego is subtracted,
+// each square is rounded on its own, then the two are added.  No contraction: a fused x^2 + y^2, or the displacement
+// added to (ego - mean) instead of to the mean, decides a few per cent of the samples within a few ulps of the 5 m
+// circle differently from the reference (tests/test_cp_gate_cpu.py), and each of those turns a CP of 1e-2 into 0.
+__device__ __forceinline__ double fo_gate_d2(double mx, double my, double devx, double devy, double ex, double ey) {
+#pragma clang fp contract(off)
+  const double cx = mx - ex, cy = my - ey;
+  const double fx = (mx + devx) - ex, fy = (my + devy) - ey;
+  const double bx = (mx - devx) - ex, by = (my - devy) - ey;
+  return fmin(cx * cx + cy * cy, fmin(fx * fx + fy * fy, bx * bx + by * by));
+}
 // r / 1000.0, correctly rounded, for finite r: q = r RN(1/1000), one fma for the exact remainder, one for the correction
 // (three operations instead of the ~30 of a float64 division; checked against true division for every integer below 2e7)
 __device__ __forceinline__ double fo_div1000(double r) {
@@ -572,10 +584,7 @@ __global__ __launch_bounds__(TILE *WAVES) void fo_sweep_generic_kernel(const Swe
         if (t + 1 < L) {
           const double devx = pc1 * hdev, devy = ps1 * hdev;
           const double rx = ex1 - px, ry = ey1 - py;  // ego(t+1) - mean
-          const double d0 = rx * rx + ry * ry;
-          const double dp = (rx - devx) * (rx - devx) + (ry - devy) * (ry - devy);
-          const double dm = (rx + devx) * (rx + devx) + (ry + devy) * (ry + devy);
-          if (!(sqrt(fmin(d0, fmin(dp, dm))) > 5.0) && !(a.ablate & 2)) {  // :67,75
+          if (!(sqrt(fo_gate_d2(px, py, devx, devy, ex1, ey1)) > 5.0) && !(a.ablate & 2)) {  // :67,75
             const double bxs = a.len3 * ec1, bys = a.len3 * es1;  // box centre step (L/3 along heading), rear-axle based (Q2)
             double acc = 0.0;
 #pragma unroll
@@ -1472,12 +1481,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           if (__ballot(dd <= gate_far2t)) {
             // (scalar loads on the rare path; the row was read a sample ago)
             const cdp_t gq = (cdp_t)((const __attribute__((address_space(4))) char *)G + (goff - 2u * (unsigned)(NAF * sizeof(double))));
-            const double rx = ex - gq[0], ry = ey - gq[1];
-            const double d0 = rx * rx + ry * ry;
-            const double devx = pc * hdev, devy = ps * hdev;
-            const double dp = (rx - devx) * (rx - devx) + (ry - devy) * (ry - devy);
-            const double dm = (rx + devx) * (rx + devx) + (ry + devy) * (ry + devy);
-            const double m2 = fmin(d0, fmin(dp, dm));
+            const double m2 = fo_gate_d2(gq[0], gq[1], pc * hdev, ps * hdev, ex, ey);
             // the reference tests the ROUNDED distance, !(sqrt(m2) > 5.0) (collision_probability.py:67,75).  The
             // correctly rounded square root of m2 is 5.0 up to and including m2 = 25 + one ulp (sqrt(25 (1 + d)) = 5 (1 + d/2),
             // half an ulp of 5.0 is 4.4e-16, one ulp of 25 is 3.6e-15): no square root needed

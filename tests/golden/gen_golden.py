@@ -182,7 +182,7 @@ def pad(arr_list, n, fill=np.nan):
     return out
 
 
-def run_case(name, trajs, kinds, preds, dt, CP, HR, TTC, TTCE, WTTC, dce_inputs=None):
+def run_case(name, trajs, kinds, preds, dt, CP, HR, TTC, TTCE, WTTC, dce_inputs=None, extra=None):
     am = AgentManager(dt)
     keys = []
     for i, (kind, pred) in enumerate(zip(kinds, preds)):
@@ -254,6 +254,8 @@ def run_case(name, trajs, kinds, preds, dt, CP, HR, TTC, TTCE, WTTC, dce_inputs=
                 ttce[m, j] = res["ttce"][key]
             wttc[m] = w
         out.update({"in_dce": dce_v, "in_time_dce": dce_t, "ref_ttc": ttc, "ref_ttce": ttce, "ref_wttc": wttc})
+    if extra is not None:
+        out.update(extra(out))
     path = os.path.join(OUT, name + ".npz")
     np.savez_compressed(path, **out)
     print("wrote", path, "M", M, "A", A, "T", T, "max cp", cp.max())
@@ -929,6 +931,148 @@ def gen_dce():
           "finite ttc", int(np.isfinite(out_ttc).sum()), "distinct time_dce", len(np.unique(out_t)))
 
 
+def gen_gate():
+    """tests/golden/cp_gate_boundary.npz: the reference's own, unmodified CP / HR code (collision_probability.py:14-126,
+    harm_model.py, hr.py) on ego samples placed ON the 5 m gate circle (collision_probability.py:49-67,75) around one of an
+    agent's three means -- centre, front, back -- at -3 ... +3 units in the last place of one coordinate, the other two means
+    outside.  Headings are 0, +-pi/2 and pi and every coordinate is at least 16 m from zero, so that NumPy's, libm's and the
+    device's cos / sin give the same displacement (the sub-ulp cos(pi/2), sin(pi) terms vanish in the addition): what is
+    pinned is the gate's arithmetic -- (mean + j dev) - ego, each square rounded, then the sum -- not transcendental ulps.
+    Map offsets 0, 1e2, 1e3, 5e3 m.  Two more samples per trajectory sit on a stationary agent at exactly
+    dx^2 + dy^2 == 25 and at the next double above 25 (sqrt still 5.0: in) or the one after (out).  Broad covariances
+    (CP at 5 m >= 1e-4, so cp == 0 is the reference's out-of-gate decision), a third of them correlated."""
+    _install_aliases()
+    sys.path.insert(0, REF)
+    for modname, cls_name, cls in (("frenetix_occlusion.metrics.dce", "DCE", _OracleDCE), ("frenetix_occlusion.metrics.be", "BE", _NoBE)):
+        mod = types.ModuleType(modname)
+        setattr(mod, cls_name, cls)
+        sys.modules[modname] = mod
+    from frenetix_occlusion.metrics.cp import CP
+    from frenetix_occlusion.metrics.hr import HR
+    from frenetix_occlusion.metrics.ttc import TTC
+    from frenetix_occlusion.metrics.ttce import TTCE
+    from frenetix_occlusion.metrics.wttc import WTTC
+    dt, T, M, A = 0.1, 31, 64, 16
+    rng = np.random.default_rng(20241016)
+    heads = np.array([0.0, np.pi / 2, np.pi, -np.pi / 2])
+    offsets = np.array([0.0, 1e2, 1e3, 5e3])
+    stationary = (0, 5, 10, 15)             # one per map offset: integer positions, the exact-25 samples sit on these
+    kinds = [AGENT_TYPES[(a + a // 4) % 4] for a in range(A)]
+    t = np.arange(T) * dt
+    preds = []
+    for a in range(A):
+        g, r = a % 4, a // 4
+        psi = heads[(r + 2 * (a % 2)) % 4]
+        p0 = np.array([offsets[g] + 20.0 + 7.0 * r, offsets[g] + 20.0 + 60.0 * r]) * (1.0 if a % 3 else -1.0)
+        if a in stationary:
+            p0 = np.round(p0)
+            pos = np.tile(p0, (T, 1))
+            spd = 0.0
+        else:
+            spd = SPEED[kinds[a]] * rng.uniform(0.3, 0.8)
+            pos = p0 + t[:, None] * np.array([round(spd * np.cos(psi), 3), round(spd * np.sin(psi), 3)])
+        yaw = np.full(T, psi)
+        if a % 4 == 2:                      # the heading turns by a quarter every five samples: heading t, mean t-1 (Q1)
+            yaw = psi + (np.pi / 2) * ((np.arange(T) // 5) % 2)
+            yaw = heads[np.argmin(np.abs(np.angle(np.exp(1j * (yaw[:, None] - heads[None, :])))), axis=1)]
+        sxx, syy = rng.uniform(4.0, 9.0, 2)
+        cov = np.zeros((T, 2, 2))
+        cov[:, 0, 0], cov[:, 1, 1] = sxx * 1.02 ** np.arange(T), syy * 1.02 ** np.arange(T)
+        if a % 3 == 1:                      # correlated covariances (correlated_cov.npz's form)
+            rho = (0.3, -0.6, 0.5, -0.4, 0.6, 0.45)[a // 3]
+            cov[:, 0, 1] = cov[:, 1, 0] = rho * np.sqrt(cov[:, 0, 0] * cov[:, 1, 1])
+        raw_l, raw_w = RAW_DIMS[kinds[a]]
+        fl, fw = (1.4, 2.5) if kinds[a] == "Bicycle" else (1.2, 1.3)
+        preds.append({"pos_list": pos, "v_list": np.full(T, spd), "orientation_list": yaw, "cov_list": cov,
+                      "shape": {"length": raw_l * fl, "width": raw_w * fw}})
+
+    def means(a, i):
+        """the reference's three means of sample i (collision_probability.py:49-53): mean i-1, heading i, (cos, sin) L / 2"""
+        p = preds[a]
+        dev = np.stack((np.cos(p["orientation_list"][i:i + 1]), np.sin(p["orientation_list"][i:i + 1])), axis=-1) * \
+            p["shape"]["length"] / 2
+        m = p["pos_list"][i - 1:i]
+        return np.array([m, m + dev, m - dev])[:, 0, :]
+
+    def dist2(mj, e):
+        d = mj - e[None, :]
+        return d[:, 0] ** 2 + d[:, 1] ** 2
+
+    ex, ey = np.zeros((M, T)), np.zeros((M, T))
+    target = np.full((M, T), -1, dtype=np.int64)     # agent whose gate circle the sample sits on
+    which = np.full((M, T), -1, dtype=np.int64)      # 0 centre, 1 front, 2 back
+    kulp = np.full((M, T), 99, dtype=np.int64)       # ulps off the computed circle point (99: the exact-25 samples)
+    for m in range(M):
+        for b in range(4):
+            a = (4 * m + b + m // 16) % A
+            j = (m + 2 * b) % 3
+            i0 = 1 + 7 * b
+            for k in range(-3, 4):
+                i = i0 + k + 3
+                mu = means(a, i)
+                h = np.array([np.cos(preds[a]["orientation_list"][i]), np.sin(preds[a]["orientation_list"][i])])
+                for tries in range(60):           # (short agents: the centre's circle hugs the other two; narrow down)
+                    spread = 0.8 ** tries
+                    if j == 0:
+                        phi = np.arctan2(h[1], h[0]) + rng.choice([-1.0, 1.0]) * (np.pi / 2 + rng.uniform(-0.6, 0.6) * spread)
+                    else:
+                        phi = np.arctan2(h[1], h[0]) + (0.0 if j == 1 else np.pi) + rng.uniform(-1.0, 1.0) * spread
+                    u = np.array([np.cos(phi), np.sin(phi)])
+                    e = mu[j] + 5.0 * u
+                    d2 = dist2(mu, e)
+                    if np.all(np.delete(d2, j) > 25.01):
+                        break
+                else:
+                    raise RuntimeError("no direction with the other two means outside")
+                c = int(np.argmax(np.abs(u)))
+                for _ in range(abs(k)):
+                    e[c] = np.nextafter(e[c], np.inf if k > 0 else -np.inf)
+                ex[m, i], ey[m, i] = e
+                target[m, i], which[m, i], kulp[m, i] = a, j, k
+        # 29: exactly 25 around mean (m % 3) of a stationary agent; 30: the next double above 25 (in) or the one after (out)
+        a = stationary[m % 4]
+        for i, want in ((29, 0), (30, 1 + m % 2)):
+            j = (m + i) % 3
+            mu = means(a, i)
+            h = np.array([np.cos(preds[a]["orientation_list"][i]), np.sin(preds[a]["orientation_list"][i])])
+            n = np.round(np.array([-h[1], h[0]])) * (1.0 if m % 2 else -1.0)       # exact unit normal
+            e = mu[j] + 5.0 * n
+            if want:
+                c = int(np.argmax(np.abs(h)))            # the coordinate along the heading: dx^2 of a few ulps of 25
+                base = e[c]
+                for dx in np.linspace(4e-8, 1e-7, 4001):
+                    e[c] = base + dx
+                    if dist2(mu, e)[j] == 25.0 + want * np.spacing(25.0):
+                        break
+                else:
+                    raise RuntimeError("no sample at 25 + %d ulp" % want)
+            d2 = dist2(mu, e)
+            assert d2[j] == 25.0 + want * np.spacing(25.0) and np.all(np.delete(d2, j) > 25.01), (m, i, d2)
+            ex[m, i], ey[m, i] = e
+            target[m, i], which[m, i], kulp[m, i] = a, j, 90 + want
+        ex[m, 0], ey[m, 0] = ex[m, 1], ey[m, 1]
+    trajs = [Traj(ex[m], ey[m], np.zeros(T), np.full(T, 8.0), np.zeros(T)) for m in range(M)]
+
+    def extra(out):
+        cp = out["ref_cp"]
+        # the reference's gate decision: its CP is >= 1e-4 on the circle, so cp == 0 is "outside"; cross-checked against
+        # the distance expression of collision_probability.py:49-67 restated in NumPy (the same operations)
+        ing = cp > 0.0
+        for m in range(M):
+            for i in range(1, T):
+                for a in range(A):
+                    restated = not (np.sqrt(dist2(means(a, i), np.array([ex[m, i], ey[m, i]]))).min() > 5.0)
+                    assert restated == ing[m, a, i - 1], (m, a, i)
+        print("in-gate cp: min %.3g, median %.3g" % (cp[ing].min(), np.median(cp[ing])))
+        assert cp[ing].min() >= 1e-4, cp[ing].min()
+        codes = {"car": 0, "truck": 1, "bus": 2, "bicycle": 3, "pedestrian": 4}
+        return {"agent_type": np.array([codes[k.lower()] for k in kinds], dtype=np.int32),     # numbers only
+                "ref_in_gate": ing, "ref_cp_argmax": np.argmax(cp, axis=-1), "sample_target": target,
+                "sample_mean": which, "sample_ulps": kulp}
+
+    run_case("cp_gate_boundary", trajs, kinds, preds, dt, CP, HR, TTC, TTCE, WTTC, extra=extra)
+
+
 def gen_be():
     """tests/golden/be_bisection.npz: the reference's own, unmodified metrics/be.py (BE.evaluate -> find_minimum_deceleration ->
     _calc_deceleration_trajectory -> _collision_check, be.py:31-193) and metrics/ttc.py on top of it.  be.py's one import
@@ -1184,6 +1328,8 @@ if __name__ == "__main__":
         gen_be()
     elif len(sys.argv) > 1 and sys.argv[1] == "dce":        # only the DCE-loop fixture (own process as well)
         gen_dce()
+    elif len(sys.argv) > 1 and sys.argv[1] == "gate":       # only the CP-gate boundary fixture (own process: stub modules)
+        gen_gate()
     elif len(sys.argv) > 1 and sys.argv[1] == "shadow":     # only the shadow-geometry fixture
         gen_shadow_geometry()
     else:

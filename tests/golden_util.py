@@ -14,7 +14,8 @@ def load_case(name):
     traj = {k: g["traj_" + k] for k in ("x", "y", "theta", "v", "a")}
     agents = {"pos": g["agent_pos"], "yaw": g["agent_yaw"], "v": g["agent_v"], "cov": g["agent_cov"],
               "shape": g["agent_shape"], "raw_dims": g["agent_raw_dims"],
-              "type": np.array([TYPE_CODES[str(t).lower()] for t in g["agent_type"]], dtype=np.int32),
+              "type": (g["agent_type"].astype(np.int32) if g["agent_type"].dtype.kind in "iu" else      # codes or type names
+                       np.array([TYPE_CODES[str(t).lower()] for t in g["agent_type"]], dtype=np.int32)),
               "len": g["agent_len"].astype(np.int32)}
     return g, traj, agents, tuple(g["vehicle"]), float(g["dt"])
 

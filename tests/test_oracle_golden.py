@@ -323,3 +323,21 @@ def test_find_spawn_points_orchestration_matches_the_references():
     finally:
         CV.curvature, R.curvature = keep_cv, keep_r
     assert n_turn >= 5
+
+
+def test_oracle_decides_the_cp_gate_boundary_like_the_reference(oracle):
+    """tests/golden/cp_gate_boundary.npz (gen_golden.py gate): ego samples within three ulps of the 5 m gate circle around
+    one of the three means, at map offsets up to 5 km, exactly at 25 m^2 and one and two doubles above it.  Every in / out
+    decision of the reference's own code is reproduced exactly (cp == 0 exactly where the reference's is), every CP, the
+    pair maxima, their first-maximum index (np.argmax, hr.py:81-82) and the harm taken there to the fixture's tolerance."""
+    g, traj, agents, veh, dt = load_case("cp_gate_boundary")
+    out = oracle.sweep(traj, agents, veh, dt)
+    cp = out["lists"][:, :, oracle.LST["cp"], :]
+    assert np.array_equal(cp > 0.0, g["ref_in_gate"]) and np.array_equal(cp == 0.0, ~g["ref_in_gate"])
+    np.testing.assert_allclose(cp, g["ref_cp"], rtol=0, atol=TOL)
+    pf, pi = out["pair_f"], out["pair_i"]
+    for key in ("max_collision_probability", "max_obst_harm_with_cp", "max_obst_risk", "max_ego_risk"):
+        np.testing.assert_allclose(pf[:, :, oracle.PF[key]], g["ref_" + key], rtol=0, atol=TOL, err_msg=key)
+    assert np.array_equal(pi[:, :, oracle.PI["cp_argmax"]], g["ref_cp_argmax"])
+    np.testing.assert_allclose(out["cost"][:, oracle.COST["max_collision_probability_all"]],
+                               g["ref_max_collision_probability_all"], rtol=0, atol=TOL)
