@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the Frenetix-Occlusion per-planning-step hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode full|pair|reduced] [--lists f32x|f32|f64] [--M 10000] [--A 256]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode full|pair|reduced] [--lists f32x|f32|f64] [--M 10000] [--A 256] [--full]
 
 One "step" = one planning step of BASELINE.json configs[2] with every input already resident in HBM:
     visibility ray fan (720 rays @ 0.5 deg, r = 50 m) over the synthetic urban lanelet net (~9.4e3 boundary edges,
@@ -28,17 +28,23 @@ arrays.  All arithmetic that reaches a cost vector, a flag or a per-pair scalar 
 Set-up (untimed, before the W warm-up steps): the library measures the sweep kernel's four agents-per-wave settings on the
 batch (`fo_sweep_autotune`, part of the C ABI: any caller gets the same choice) and keeps the best for the shape -- which
 also brings the GPU to its sustained clocks, so that the timed K steps do not depend on W (`--no-autotune` skips it).
-`--scene scenario1 --M 2000 --A 32` runs BASELINE configs[1] instead.  Beside the headline the default run measures
-(`config.*`): the other list formats, reduced outputs, `shard_probe` (the step of a 1/8, 1/4, 1/2 shard of the batch and
-the RCCL all-gather of one cost block, on this one GPU), `small_batch` (configs[1]) and `rules_step` (the reference's
-own spawn rule families as a device-resident step).
+`--scene scenario1 --M 2000 --A 32` runs BASELINE configs[1] instead.
+
+A plain run does only what its headline needs: set-up, the W warm-up steps, the K timed steps, `--dump-outputs` if given,
+the JSON line.  `--full` adds everything else the line can carry (`extra_legs`): `parity` (the GPU buffers of the last
+timed step against the CPU oracle on EVERY pair of the batch), `cpu_baseline` (the three CPU figures of SURVEY 8d: NumPy
+in the reference's loop structure on one thread, the C port on one thread and on all cores), `config.scene_stage_ms`,
+and -- for the default workload on one GPU -- the in-run counter passes behind `roofline.traffic` and the side legs
+(`config.*`): the other list formats, reduced outputs, future visibility, `shard_probe` (the step of a 1/8, 1/4, 1/2
+shard of the batch and the RCCL all-gather of one cost block, on this one GPU), `small_batch` (configs[1]), `rules_step`
+(the reference's own spawn rule families as a device-resident step) and `box`.  `--no-cpu-baseline`, `--no-extras` and
+`--no-live-pmc` leave parts of that out again.
 
 Prints ONE JSON line on rank 0.  `value` = trajectory x agent metric evaluations per second over all ranks.
 `roofline` follows SURVEY 8d: algorithmic bytes = 620 B per trajectory + 636 B per agent + 648 B per pair (full
 outputs, fp32 storage) over the HIP-event duration of the sweep kernel; `frac_stored_bytes` is the same on the bytes
-this build really moves (float64 inputs and pair scalars).  `parity` compares the GPU buffers of the last timed step
-with the CPU oracle on EVERY pair of the batch; `cpu_baseline` holds the three CPU figures of SURVEY 8d (NumPy in the
-reference's loop structure on one thread, the C port on one thread and on all cores).
+this build really moves (float64 inputs and pair scalars).  Without in-run counters `roofline.traffic` comes from the
+committed summary of the loaded library, if there is one.
 """
 import argparse
 import json
@@ -111,6 +117,18 @@ def free_port():
     p = s.getsockname()[1]
     s.close()
     return p
+
+
+def extra_legs(args, world, launched):
+    """What a run measures or checks beyond its headline figure -- nothing without --full.  `launched`: WORLD_SIZE is set
+    (a launcher above this process).  live_pmc: the two counter passes before the GPU is touched; cpu_baseline: oracle
+    parity + CPU figures; scene_stage: config.scene_stage_ms; extras: the side legs of the default workload on one GPU."""
+    default_workload = args.scene == "urban" and (args.M, args.A, args.T, args.mode) == (10000, 256, 31, "full")
+    return {"live_pmc": (args.full and args.gpus == 1 and not launched and not args.no_live_pmc and not args.no_extras
+                         and default_workload),
+            "cpu_baseline": args.full and world == 1 and not args.no_cpu_baseline,
+            "scene_stage": args.full,
+            "extras": args.full and world == 1 and default_workload and not args.no_extras}
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 without a launcher
@@ -782,7 +800,7 @@ def dump_outputs(out, path):
     return {name: list(a.shape) for name, a in arrays.items()}
 
 
-def main():
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -800,11 +818,14 @@ def main():
     ap.add_argument("--scaling", default=None, choices=["weak", "strong"],
                     help="strong (default): --M trajectories in total, split over the ranks (BASELINE configs[3]); "
                          "weak: --M trajectories per rank")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline as well: oracle parity, CPU baselines, the stage "
+                         "breakdown and, for the default workload on one GPU, in-run counters and the side legs (config.*)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baselines and the oracle parity check")
     ap.add_argument("--no-autotune", action="store_true", help="skip the agents-per-wave selection pass of the set-up")
     ap.add_argument("--entry", default="step", choices=["step", "stages"],
                     help="scene-based runs: the planning step through fo_step_run (one native call, nine launches) or as the five stage calls")
-    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other output modes, configs[1])")
+    ap.add_argument("--no-extras", action="store_true", help="skip the secondary measurements (other output modes, configs[1]) of --full")
     ap.add_argument("--order", default="sampler", choices=["sampler", "random"],
                     help="row order of the synthetic trajectories (synthetic.make_trajectories)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
@@ -813,19 +834,23 @@ def main():
                          "trajectory sample) as DIR/<name>.npy, float32 / float64, finite (NaN / inf entries coded in <name>_nonfinite.npy), "
                          "at most 64 MB in all")
     ap.add_argument("--no-live-pmc", action="store_true",
-                    help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic in this run (the default N = 1 run of the "
+                    help="do not run the two rocprofv3 --pmc passes that measure roofline.traffic in this run (the --full N = 1 run of the "
                          "headline workload does; the committed summary of the loaded library is the fallback)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = arg_parser().parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher above us: become one -- before torch is imported or a GPU is touched
         sys.exit(launch_workers(args.gpus, sys.argv[1:]))
     if args.launcher_selftest:
         sys.exit(launcher_selftest(args))
+    legs = extra_legs(args, int(os.environ.get("WORLD_SIZE", "1")), "WORLD_SIZE" in os.environ)
     # roofline.traffic measured in THIS run: counter passes as child processes, before this process touches the GPU
     live = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_live_pmc and not args.no_extras and args.scene == "urban"
-            and (args.M, args.A, args.T, args.mode) == (10000, 256, 31, "full")):
+    if legs["live_pmc"]:
         live = live_pmc(args.lists, args.mode)
 
     import numpy as np
@@ -1003,9 +1028,9 @@ def main():
         torch.cuda.synchronize()
         ag_ms = e0.elapsed_time(e1) / 100
 
-    # stage breakdown (outside the timed region): the scene stage alone, HIP events on the launch stream
+    # stage breakdown (--full, outside the timed region): the scene stage alone, HIP events on the launch stream
     scene_ms = None
-    if scene is not None:
+    if scene is not None and legs["scene_stage"]:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
         e0.record()
@@ -1102,7 +1127,7 @@ def main():
             res["config"]["safe_traj_frac"] = float(out.safe.double().mean())
         if args.dump_outputs and out is not None:
             res["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(out, args.dump_outputs)}
-        if world == 1 and not args.no_cpu_baseline:
+        if legs["cpu_baseline"]:
             # oracle on EVERY pair: parity of the last timed step's buffers + the CPU baselines (before the extras below
             # reuse the context)
             if scene is not None:
@@ -1111,7 +1136,7 @@ def main():
             res["cpu_baseline"], res["parity"] = cpu_and_parity(S, N, traj, agents, out, args.lists)
         else:
             res["cpu_baseline"], res["parity"] = None, None
-        if world == 1 and default_workload and not args.no_extras:
+        if legs["extras"]:
             def side(mode, lists, n=100):
                 r = None
                 for _ in range(60):

@@ -117,3 +117,24 @@ with open(os.path.join(d, "host", "123", "run_counter_collection.csv"), "w") as 
     monkeypatch.delenv("FAKE_DROP")
     monkeypatch.setenv("FAKE_FAIL", "1")
     assert bench.live_pmc("f32x") is None
+
+
+def test_a_plain_run_does_only_what_its_headline_needs():
+    """`bench.py` without --full: set-up, warm-up, timed steps, --dump-outputs, the line -- no counter passes, no oracle parity or
+    CPU baselines, no stage breakdown, no side legs.  --full turns each on where it applies (the counter passes and the side legs
+    only for the default workload on one GPU, parity and CPU figures on one rank), and its --no-* options leave parts out again."""
+    sys.path.insert(0, ROOT)
+    import bench
+
+    def legs(argv, world=1, launched=False):
+        return bench.extra_legs(bench.arg_parser().parse_args(argv), world, launched)
+    none = dict.fromkeys(("live_pmc", "cpu_baseline", "scene_stage", "extras"), False)
+    assert legs([]) == none
+    assert legs(["--steps", "3", "--warmup", "1", "--no-autotune", "--dump-outputs", "out", "--lists", "f64"]) == none
+    assert legs(["--gpus", "2"], world=2, launched=True) == none
+    assert legs(["--full"]) == dict.fromkeys(none, True)
+    assert legs(["--full", "--gpus", "2"], world=2, launched=True) == dict(none, scene_stage=True)
+    assert legs(["--full"], world=1, launched=True) == dict(none, cpu_baseline=True, scene_stage=True, extras=True)
+    for other in (["--scene", "scenario1", "--M", "2000", "--A", "32"], ["--mode", "reduced"], ["--M", "5000"], ["--no-extras"]):
+        assert legs(["--full"] + other) == dict(none, cpu_baseline=True, scene_stage=True)
+    assert legs(["--full", "--no-cpu-baseline", "--no-live-pmc"]) == dict(none, scene_stage=True, extras=True)

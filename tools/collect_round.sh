@@ -19,7 +19,10 @@ for t in ${R}_final ${R}_f64lists ${R}_f32 ${R}_reduced ${R}_fv; do python3 tool
 # the default bench line quotes the committed counters of the library it runs (roofline.bound / traffic / valu_issue_frac): put
 # this run's summaries where it looks for them (on the box's copy of the tree; tools/copy_profiles.sh does the same at home)
 for t in ${R}_final ${R}_f64lists ${R}_f32 ${R}_reduced; do cp gpurun_out/summ/${t}_summary.csv gpurun_out/summ/${t}_build.json profiles/; done
-python bench.py > gpurun_out/${R}_final_bench.json 2> gpurun_out/${R}_final_bench.err
+# the full bench line (--full: parity, CPU baselines and the side legs read below), beside the profiles: in the directory
+# tools/collect_profiles.sh writes to (its OUT)
+OUT=$PWD/$(sed -n 's|^OUT=\$PWD/||p' tools/collect_profiles.sh)
+python bench.py --full > "$OUT/${R}_final_bench.json" 2> "$OUT/${R}_final_bench.err"
 # keep the merge small: drop the raw counter dumps
 find gpurun_out -name "*counter_collection.csv" -delete; find gpurun_out -name "*kernel_trace.csv" -delete; find gpurun_out -name "*agent_info.csv" -delete
 ls gpurun_out/summ; du -sh gpurun_out
