@@ -132,7 +132,8 @@ __device__ __forceinline__ double fo_erf_lds(const double2 *__restrict__ tab, do
 }
 
 // sqrt by one Goldschmidt step on v_rsq_f64 (relative error ~1e-14 instead of the correctly rounded ~25-instruction
-// expansion of sqrt()); x >= 0, x = 0 -> 0.  Consumers are rounded to 1e-3 / compared at 1e-9.
+// expansion of sqrt()); x >= 0, x = 0 -> 0.  Consumers are compared at 1e-9; the distances rounded to 1e-3 take one more
+// correction (fo_mm).
 #ifndef FO_DIET
 #define FO_DIET 1   // 0: tuning builds -- the scalar-instruction diet of round 3 switched off (clamped row addresses, literals)
 #endif
@@ -889,6 +890,23 @@ __device__ __forceinline__ double fo_corr_corners(const double *__restrict__ exp
   return (eAC - eBC) - (eAD - eBD);
 }
 
+// Whole millimetres of the distance sqrt(d2): rint(RN(d * 1000)) = 1000 np.round(d, 3) (dce.py:79, half to even).  fo_sqrt alone
+// (~1e-14 relative) rounded distances at an exact half millimetre the other way -- two dyadic rectangles 19/16 m apart, 1187.5
+// mm, came out as 1187 (tests/test_sweep_exact_gpu.py).  So the root gets one more correction from its exact residual,
+// y += (d2 - y^2) / (2 y) with the residual from one fma: the error drops to ~1e-28 relative before the last rounding, so an
+// exact root (every tie) comes out exact and every other root is rounded correctly unless it lies that close to a midpoint.  Two fma per exact distance.  (A branch to sqrt() next to a half millimetre instead cost
+// the queue kernels 2 % on the headline: the kernel sits at its register cap.)
+__device__ __forceinline__ double fo_mm(double d2) {
+  const double g = __builtin_amdgcn_rsq(d2);
+  double y = d2 * g;
+  const double h = 0.5 * g;
+  y = fma(y, fma(-h, y, 0.5), y);     // fo_sqrt's Goldschmidt step
+  y = fma(fma(-y, y, d2), h, y);      // the correction
+  double z;
+  asm("v_max_f64 %0, %1, 0" : "=v"(z) : "v"(y));   // d2 = 0: NaN -> 0 (as in fo_sqrt)
+  return __builtin_rint(z * 1000.0);
+}
+
 // Rounded distance (whole millimetres, rint(1000 d) = 1000 np.round(d, 3), dce.py:79) between the ego rectangle at
 // rear-axle pose (ex, ey, heading (ec, es)) and the agent rectangle at (px, py, heading (pc, ps)): four-axis SAT
 // (overlap -> 0), otherwise the minimum over the eight corner-to-box distances.
@@ -912,7 +930,7 @@ __device__ __forceinline__ double fo_rect_mm(double ex, double ey, double ec, do
   d2 = fmin(d2, fo_pt_box2(bx + vx - zx, by + vy - zy, hlB, hwB));
   d2 = fmin(d2, fo_pt_box2(bx - vx + zx, by - vy + zy, hlB, hwB));
   d2 = fmin(d2, fo_pt_box2(bx - vx - zx, by - vy - zy, hlB, hwB));
-  return __builtin_rint(fo_sqrt(d2) * 1000.0);
+  return fo_mm(d2);
 }
 
 // wave-uniform tables are read through the constant address space: the loads become s_load (scalar cache, results in
@@ -1463,7 +1481,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
                 d2 = fmin(d2, fo_pt_box2(bx + vx - zx, by + vy - zy, hlB, hwB));
                 d2 = fmin(d2, fo_pt_box2(bx - vx + zx, by - vy + zy, hlB, hwB));
                 d2 = fmin(d2, fo_pt_box2(bx - vx - zx, by - vy - zy, hlB, hwB));
-                if (!overlap) nmm = __builtin_rint(fo_sqrt(d2) * 1000.0);
+                if (!overlap) nmm = fo_mm(d2);
               }
               if (need && (nmm < dce || (nmm == dce && t < tdce))) {
                 dce = nmm;
