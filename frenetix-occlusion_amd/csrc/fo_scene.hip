@@ -805,20 +805,39 @@ __global__ __launch_bounds__(64 * NW) void fo_settle_kernel(
 // ------------------------------------------------------------------------------------------------ future visibility
 // An extension, NOT part of the reference: how much of the currently occluded area a candidate trajectory
 // will come to see.  A workgroup per pose (trajectory m, every t_stride-th sample k): (1) the 64-piece chunks whose box
-// lies within r of the pose are listed in LDS; (2) a thread per ray of a world-aligned full fan walks that list --
-// per-ray box culling, and a wave whose rays all miss a chunk skips it -- keeping the first hit; (3) shoelace area of
-// the polygon of hit points; (4) the cells of the current occluded set are tested against the fan (chord rule of the
-// cell-grid kernel) and counted.  Ranges never leave LDS.
+// lies within r of the pose are listed in LDS; (2) a thread per ray of the fan walks that list -- per-ray box culling,
+// and a wave whose rays all miss a chunk skips it -- keeping the first hit against the map and the pose's occluder
+// slice; (3) shoelace area of the polygon of hit points; (4) the cells of the current occluded set are tested against the
+// fan (chord rule of the cell-grid kernel) and counted.  Ranges never leave LDS.
+// fo_scene_future_visibility is the form <RPT, false, false> with one slice and a world-aligned full fan.  The extended
+// entry adds: per-pose occluder slices; a fan rotated per pose by a given heading (float64, no contraction: this file is
+// built with -ffp-contract=off), open when SECTOR (open shoelace sum, fan_sector(full = 0) lookup); and with FS a
+// workgroup per TRAJECTORY that walks its poses in order and keeps a "seen" bit per occluded-list entry in LDS, so that
+// it can count the cells a pose sees for the first time.  Bit j of thread t's word w stands for list entry
+// t + 256 (32 w + j): every bit belongs to the thread that tests that entry, so the set needs no atomics.
 constexpr int FV_THREADS = 256;   // threads per pose; a thread walks RPT rays (tid, tid + 256, ...): RPT = ceil(n_rays / 256)
 constexpr int FV_MAX_RPT = 3;     // <= 768 rays: the 720-ray fan of BASELINE configs[2] (0.5 deg) fits (round 6; 256 before)
 constexpr int FV_BATCH = 48;      // 16-piece quarters staged in LDS at a time (24 KB)
-template <int RPT>
-__global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
-    int T, const double *__restrict__ x, const double *__restrict__ y, int t_stride, int K, int n_rays,
-    const double *__restrict__ dirs, double r, int E, const double *__restrict__ edges,
-    const double *__restrict__ sub_box, int O, const double *__restrict__ ocorn, const uint8_t *__restrict__ oflags,
-    const int32_t *__restrict__ occ_idx, const int32_t *__restrict__ n_occ_ptr, double rx0, double ry0, double cs,
-    int ix0, int iy0, int nx, int32_t *__restrict__ revealed, double *__restrict__ area) {
+constexpr int FV_SEEN_CELLS = 32 * FV_THREADS;   // list entries per word row of the seen set (one 1 KB row)
+static_assert(FO_FUTURE_VISIBILITY_MAX_CELLS % FV_SEEN_CELLS == 0, "seen-set capacity: whole word rows");
+struct FvArgs {
+  int T, t_stride, K, n_rays;
+  const double *x, *y, *dirs, *heading;   // heading [M][K][2] or null (world-aligned)
+  double r;
+  int E;
+  const double *edges, *sub_box;
+  int O, n_slices;                        // slice s: ocorn + 8 O s, oflags + O s; pose k reads min(k, n_slices - 1)
+  const double *ocorn;
+  const uint8_t *oflags;
+  const int32_t *occ_idx, *n_occ_ptr;
+  double rx0, ry0, cs;
+  int ix0, iy0, nx;
+  int32_t *revealed;
+  double *area;
+  int32_t *revealed_new, *revealed_any;   // FS only (either may be null)
+};
+template <int RPT, bool SECTOR, bool FS>
+__global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(const FvArgs a) {
   __shared__ double s_dir[2 * FV_THREADS * RPT];
   __shared__ double s_rng[FV_THREADS * RPT];
   __shared__ double s_seg[FV_BATCH][64];    // 16 pieces x (ax, ay, bx, by) per staged quarter
@@ -828,10 +847,34 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
   __shared__ double s_ob[64][8];            // corner rows of the obstacles within reach (64 at a time)
   __shared__ double s_red[FV_THREADS / 64];
   __shared__ int s_cnt[FV_THREADS / 64];
+  __shared__ int s_new[FV_THREADS / 64];
+  extern __shared__ uint32_t s_seen[];      // FS: [rows][FV_THREADS], rows = ceil(n_occ / FV_SEEN_CELLS)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int m = blockIdx.x / K, k = blockIdx.x % K;
-  const double px = x[(size_t)m * T + (size_t)k * t_stride], py = y[(size_t)m * T + (size_t)k * t_stride];
-  for (int i = tid; i < n_rays; i += FV_THREADS) { s_dir[2 * i] = dirs[2 * i]; s_dir[2 * i + 1] = dirs[2 * i + 1]; }
+  const int n_rays = a.n_rays, E = a.E, K = a.K;
+  const double r = a.r;
+  const int m = FS ? (int)blockIdx.x : (int)blockIdx.x / K;
+  const int k_begin = FS ? 0 : (int)blockIdx.x % K, k_end = FS ? K : k_begin + 1;
+  const int n_occ = *a.n_occ_ptr;
+  if (FS)
+    for (int w = tid; w < (n_occ + FV_SEEN_CELLS - 1) / FV_SEEN_CELLS * FV_THREADS; w += FV_THREADS) s_seen[w] = 0u;
+  int n_any = 0;
+  for (int k = k_begin; k < k_end; ++k) {
+  const size_t pose = (size_t)m * K + k;
+  const int sl = k < a.n_slices ? k : a.n_slices - 1;
+  const double *__restrict__ ocorn = a.ocorn + 8 * (size_t)a.O * sl;
+  const uint8_t *__restrict__ oflags = a.oflags + (size_t)a.O * sl;
+  const double px = a.x[(size_t)m * a.T + (size_t)k * a.t_stride], py = a.y[(size_t)m * a.T + (size_t)k * a.t_stride];
+  if (FS) __syncthreads();   // the previous pose is done with s_dir / s_rng / s_red / s_cnt
+  if (a.heading) {
+    const double hc = a.heading[2 * pose], hs = a.heading[2 * pose + 1];
+    for (int i = tid; i < n_rays; i += FV_THREADS) {
+      const double ux = a.dirs[2 * i], uy = a.dirs[2 * i + 1];
+      s_dir[2 * i] = hc * ux - hs * uy;
+      s_dir[2 * i + 1] = hs * ux + hc * uy;
+    }
+  } else {
+    for (int i = tid; i < n_rays; i += FV_THREADS) { s_dir[2 * i] = a.dirs[2 * i]; s_dir[2 * i + 1] = a.dirs[2 * i + 1]; }
+  }
   __syncthreads();
   // ray u of this thread: index tid + 256 u
   bool ray[RPT];
@@ -851,7 +894,7 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
   const double rr = r + 1e-7;
   const size_t n_dbl = 4 * (size_t)E;
   auto in_reach = [&](int c) {
-    const double *b = sub_box + 4 * (size_t)c;
+    const double *b = a.sub_box + 4 * (size_t)c;
     const double ddx = fmax(fmax(b[0] - px, px - b[2]), 0.0), ddy = fmax(fmax(b[1] - py, py - b[3]), 0.0);
     return ddx * ddx + ddy * ddy <= rr * rr;   // an empty box (inf, -inf) is never in reach
   };
@@ -886,10 +929,10 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
       const int slot = base + (tid >> 6);
       if (slot < nch) {
         const size_t g = 64 * (size_t)s_ch[slot] + (tid & 63);
-        s_seg[slot][tid & 63] = g < n_dbl ? edges[g] : 0.0;
+        s_seg[slot][tid & 63] = g < n_dbl ? a.edges[g] : 0.0;
         if ((tid & 63) < 4) {  // box relative to the pose, in float, grown by 1 mm (>> float rounding at map scale)
           const int u = tid & 63;
-          const double v = sub_box[4 * (size_t)s_ch[slot] + u] - ((u & 1) ? py : px);
+          const double v = a.sub_box[4 * (size_t)s_ch[slot] + u] - ((u & 1) ? py : px);
           s_box[slot][u] = (float)v + (u < 2 ? -1e-3f : 1e-3f);
         }
       }
@@ -923,12 +966,12 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
     __syncthreads();
   }
   // obstacles within reach: corner rows staged in LDS (64 at a time)
-  for (int base = 0; base < O; base += 64) {
+  for (int base = 0; base < a.O; base += 64) {
     __syncthreads();
     if (tid == 0) s_nob = 0;
     __syncthreads();
     const int o = base + tid;
-    if (tid < 64 && o < O && (oflags[o] & 1) && (oflags[o] & 2)) {
+    if (tid < 64 && o < a.O && (oflags[o] & 1) && (oflags[o] & 2)) {
       const double *c = ocorn + 8 * (size_t)o;
       const double mx = 0.5 * (c[0] + c[4]), my = 0.5 * (c[1] + c[5]);
       const double hd2 = (c[0] - mx) * (c[0] - mx) + (c[1] - my) * (c[1] - my);
@@ -968,11 +1011,12 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
     if (ray[u]) s_rng[tid + u * FV_THREADS] = best[u];
   }
   __syncthreads();
-  // (3) shoelace area of the polygon of hit points: per-thread terms (its rays in ascending order), fixed-order tree sum
+  // (3) shoelace area of the polygon of hit points (an open fan: pose + hit points, the two edges at the pose add
+  // nothing): per-thread terms (its rays in ascending order), fixed-order tree sum
   double term = 0.0;
 #pragma unroll
   for (int u = 0; u < RPT; ++u)
-    if (ray[u]) {
+    if (ray[u] && !(SECTOR && tid + u * FV_THREADS == n_rays - 1)) {
       const int i = tid + u * FV_THREADS, j = (i + 1 == n_rays) ? 0 : i + 1;
       const double hix = s_rng[i] * s_dir[2 * i], hiy = s_rng[i] * s_dir[2 * i + 1];
       const double hjx = s_rng[j] * s_dir[2 * j], hjy = s_rng[j] * s_dir[2 * j + 1];
@@ -982,41 +1026,70 @@ __global__ __launch_bounds__(FV_THREADS) void fo_future_visibility_kernel(
   for (int off = 32; off >= 1; off >>= 1) term += __shfl_xor(term, off);
   if (lane == 0) s_red[wave] = term;
   // (4) occluded cells inside the fan
-  const int n_occ = *n_occ_ptr;
   const double r2 = r * r;
-  int cnt = 0;
+  int cnt = 0, nw = 0;
   auto inside_fan = [&](int idx) -> int {
-    const int wx = ix0 + idx % nx, wy = iy0 + idx / nx;
-    const double cx = rx0 + ((double)wx + 0.5) * cs, cy = ry0 + ((double)wy + 0.5) * cs;
+    const int wx = a.ix0 + idx % a.nx, wy = a.iy0 + idx / a.nx;
+    const double cx = a.rx0 + ((double)wx + 0.5) * a.cs, cy = a.ry0 + ((double)wy + 0.5) * a.cs;
     const double qx = cx - px, qy = cy - py;
     if (qx * qx + qy * qy > r2) return 0;
     if (qx == 0.0 && qy == 0.0) return 1;
-    const int i = fan_sector_uniform(n_rays, s_dir, qx, qy);
+    const int i = SECTOR ? fan_sector(n_rays, s_dir, 0, qx, qy) : fan_sector_uniform(n_rays, s_dir, qx, qy);
     if (i < 0) return 0;
     const int j = (i + 1 == n_rays) ? 0 : i + 1;
     const double hix = s_rng[i] * s_dir[2 * i], hiy = s_rng[i] * s_dir[2 * i + 1];
     const double hjx = s_rng[j] * s_dir[2 * j], hjy = s_rng[j] * s_dir[2 * j + 1];
     return ((hjx - hix) * (qy - hiy) - (hjy - hiy) * (qx - hix) >= 0.0) ? 1 : 0;
   };
-  // four cell indices per thread in flight (the list is read once per pose; the loads are what the loop waits for)
-  int ci = tid;
-  for (; ci + 3 * FV_THREADS < n_occ; ci += 4 * FV_THREADS) {
-    const int i0 = occ_idx[ci], i1 = occ_idx[ci + FV_THREADS], i2 = occ_idx[ci + 2 * FV_THREADS],
-              i3 = occ_idx[ci + 3 * FV_THREADS];
-    cnt += inside_fan(i0) + inside_fan(i1) + inside_fan(i2) + inside_fan(i3);
+  if (FS) {
+    // entry ci = tid + 256 (32 w + b): bit b of this thread's word w; seen by an earlier pose = set
+    for (int w = 0; w * FV_SEEN_CELLS + tid < n_occ; ++w) {
+      uint32_t bits = s_seen[w * FV_THREADS + tid];
+      const uint32_t before = bits;
+      for (int b = 0; b < 32; ++b) {
+        const int ci = tid + (32 * w + b) * FV_THREADS;
+        if (ci >= n_occ) break;
+        if (inside_fan(a.occ_idx[ci])) { ++cnt; bits |= 1u << b; }
+      }
+      nw += __popc(bits & ~before);
+      s_seen[w * FV_THREADS + tid] = bits;
+    }
+  } else {
+    // four cell indices per thread in flight (the list is read once per pose; the loads are what the loop waits for)
+    int ci = tid;
+    for (; ci + 3 * FV_THREADS < n_occ; ci += 4 * FV_THREADS) {
+      const int i0 = a.occ_idx[ci], i1 = a.occ_idx[ci + FV_THREADS], i2 = a.occ_idx[ci + 2 * FV_THREADS],
+                i3 = a.occ_idx[ci + 3 * FV_THREADS];
+      cnt += inside_fan(i0) + inside_fan(i1) + inside_fan(i2) + inside_fan(i3);
+    }
+    for (; ci < n_occ; ci += FV_THREADS) cnt += inside_fan(a.occ_idx[ci]);
   }
-  for (; ci < n_occ; ci += FV_THREADS) cnt += inside_fan(occ_idx[ci]);
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) cnt += __shfl_xor(cnt, off);
   if (lane == 0) s_cnt[wave] = cnt;
+  if (FS) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) nw += __shfl_xor(nw, off);
+    if (lane == 0) s_new[wave] = nw;
+  }
   __syncthreads();
   if (tid == 0) {
     double a2 = 0.0;
-    int total = 0;
-    for (int w = 0; w < FV_THREADS / 64; ++w) { a2 += s_red[w]; total += s_cnt[w]; }
-    area[blockIdx.x] = 0.5 * a2;
-    revealed[blockIdx.x] = total;
+    int total = 0, fresh = 0;
+    for (int w = 0; w < FV_THREADS / 64; ++w) {
+      a2 += s_red[w];
+      total += s_cnt[w];
+      if (FS) fresh += s_new[w];
+    }
+    a.area[pose] = 0.5 * a2;
+    a.revealed[pose] = total;
+    if (FS) {
+      if (a.revealed_new) a.revealed_new[pose] = fresh;
+      n_any += fresh;
+    }
   }
+  }
+  if (FS && tid == 0 && a.revealed_any) a.revealed_any[m] = n_any;
 }
 
 // ------------------------------------------------------------------------------------------------ compaction
@@ -1871,6 +1944,25 @@ int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om) 
   return FO_OK;
 }
 
+// launch of fo_future_visibility_kernel: RPT by the ray count, the open-fan and first-seen forms by the caller
+static int launch_future_visibility(fo_ctx *ctx, const FvArgs &a, int M, bool sector, bool fs, size_t seen_bytes, void *stream) {
+  const int rpt = (a.n_rays + FV_THREADS - 1) / FV_THREADS;
+  const dim3 grid((unsigned)(fs ? (size_t)M : (size_t)M * a.K)), block(FV_THREADS);
+  const size_t lds = fs ? seen_bytes : 0;
+  hipStream_t st = (hipStream_t)stream;
+#define FO_LAUNCH_FV(RPT_, SEC_, FS_) hipLaunchKernelGGL((fo_future_visibility_kernel<RPT_, SEC_, FS_>), grid, block, lds, st, a)
+#define FO_LAUNCH_FV_RPT(SEC_, FS_)                                                      \
+  do {                                                                                   \
+    if (rpt == 1) FO_LAUNCH_FV(1, SEC_, FS_); else if (rpt == 2) FO_LAUNCH_FV(2, SEC_, FS_); else FO_LAUNCH_FV(3, SEC_, FS_); \
+  } while (0)
+  if (sector) { if (fs) FO_LAUNCH_FV_RPT(true, true); else FO_LAUNCH_FV_RPT(true, false); }
+  else { if (fs) FO_LAUNCH_FV_RPT(false, true); else FO_LAUNCH_FV_RPT(false, false); }
+#undef FO_LAUNCH_FV_RPT
+#undef FO_LAUNCH_FV
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
 int fo_scene_future_visibility(fo_ctx *ctx, int M, int T, const double *d_x, const double *d_y, int t_stride, int n_rays,
                                const double *d_dirs, double r, int O, const double *d_ocorn, const uint8_t *d_oflags,
                                const int32_t *d_occ_idx, const int32_t *d_n_occ, int win_ix0, int win_iy0, int win_nx,
@@ -1884,15 +1976,42 @@ int fo_scene_future_visibility(fo_ctx *ctx, int M, int T, const double *d_x, con
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int K = (T + t_stride - 1) / t_stride;
   // a thread per ray up to 256 rays (the form of rounds 1-5, unchanged), two or three rays per thread beyond
-#define FO_LAUNCH_FV(RPT_)                                                                                                          \
-  hipLaunchKernelGGL(fo_future_visibility_kernel<RPT_>, dim3((unsigned)((size_t)M * K)), dim3(FV_THREADS), 0, (hipStream_t)stream, \
-                     T, d_x, d_y, t_stride, K, n_rays, d_dirs, r, sc->map->E, sc->map->d_edges, sc->map->d_sub_box, O, d_ocorn,        \
-                     d_oflags, d_occ_idx, d_n_occ, sc->map->x0, sc->map->y0, sc->map->cs, win_ix0, win_iy0, win_nx, d_revealed, d_area)
-  const int rpt = (n_rays + FV_THREADS - 1) / FV_THREADS;
-  if (rpt == 1) FO_LAUNCH_FV(1); else if (rpt == 2) FO_LAUNCH_FV(2); else FO_LAUNCH_FV(3);
-#undef FO_LAUNCH_FV
-  FO_HIP_TRY(ctx, hipGetLastError());
-  return FO_OK;
+  const FvArgs a{T, t_stride, K, n_rays, d_x, d_y, d_dirs, nullptr, r, sc->map->E, sc->map->d_edges, sc->map->d_sub_box,
+                 O, 1, d_ocorn, d_oflags, d_occ_idx, d_n_occ, sc->map->x0, sc->map->y0, sc->map->cs, win_ix0, win_iy0, win_nx,
+                 d_revealed, d_area, nullptr, nullptr};
+  return launch_future_visibility(ctx, a, M, false, false, 0, stream);
+}
+
+int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, void *stream) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_future_visibility_ex: call fo_scene_set_map first");
+  if (!p) return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: no parameters");
+  Scene *sc = (Scene *)ctx->scene;
+  if (p->M < 0 || p->T < 1 || !p->d_x || !p->d_y || p->t_stride < 1 || p->n_rays < 4 || p->n_rays > FV_THREADS * FV_MAX_RPT ||
+      !p->d_dirs || !(p->r > 0) || p->O < 0 || (p->O > 0 && (!p->d_ocorn || !p->d_oflags)) || !p->d_occ_idx || !p->d_n_occ ||
+      p->win_nx < 1 || p->win_ny < 1 || !p->d_revealed || !p->d_area)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: bad arguments (4 <= n_rays <= %d)", FV_THREADS * FV_MAX_RPT);
+  if (p->n_slices < 1)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: n_slices = %d (at least one occluder slice)", p->n_slices);
+  if (!(p->fov_deg > 0))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: fov_deg must be positive");
+  const bool sector = !(p->fov_deg >= 359.9);
+  if (sector && !p->d_heading)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: a %.3g deg sector fan needs d_heading", p->fov_deg);
+  const bool fs = p->d_revealed_new || p->d_revealed_any;
+  const int64_t cells = (int64_t)p->win_nx * p->win_ny;
+  if (fs && cells > FO_FUTURE_VISIBILITY_MAX_CELLS)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_future_visibility_ex: first-seen outputs need a window of <= %d cells (%d x %d given)",
+                   FO_FUTURE_VISIBILITY_MAX_CELLS, p->win_nx, p->win_ny);
+  if (p->M == 0) return FO_OK;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int K = (p->T + p->t_stride - 1) / p->t_stride;
+  const FvArgs a{p->T, p->t_stride, K, p->n_rays, p->d_x, p->d_y, p->d_dirs, p->d_heading, p->r, sc->map->E, sc->map->d_edges,
+                 sc->map->d_sub_box, p->O, p->n_slices, p->d_ocorn, p->d_oflags, p->d_occ_idx, p->d_n_occ, sc->map->x0,
+                 sc->map->y0, sc->map->cs, p->win_ix0, p->win_iy0, p->win_nx, p->d_revealed, p->d_area, p->d_revealed_new,
+                 p->d_revealed_any};
+  // seen set: whole 1 KB rows for the largest list the window can hold
+  const size_t seen_bytes = (size_t)((cells + FV_SEEN_CELLS - 1) / FV_SEEN_CELLS) * FV_THREADS * sizeof(uint32_t);
+  return launch_future_visibility(ctx, a, p->M, sector, fs, seen_bytes, stream);
 }
 
 // fo_scene_spawn; at (fo_step_run): the prediction kernel also writes its slots' rows of the sweep's agent table, and the

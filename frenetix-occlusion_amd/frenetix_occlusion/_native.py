@@ -33,7 +33,7 @@ EXPORTS = [
     "fo_scene_set_map", "fo_scene_share_map", "fo_scene_set_edge_lines", "fo_scene_set_routes", "fo_scene_map_info", "fo_scene_copy_raster", "fo_scene_fan", "fo_scene_visibility", "fo_scene_future_visibility", "fo_scene_spawn",
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
-    "fo_scene_set_occlusion_memory",
+    "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex",
 ]
 
 
@@ -67,6 +67,18 @@ class OcclusionMemory(C.Structure):     # fo_occlusion_memory_t
     _fields_ = [("r2", C.c_int32), ("reset", C.c_int32), ("prev_ix0", C.c_int32), ("prev_iy0", C.c_int32),
                 ("prev_nx", C.c_int32), ("prev_ny", C.c_int32), ("d_prev", C.c_void_p), ("d_cur", C.c_void_p),
                 ("prev_bytes", C.c_int64), ("cur_bytes", C.c_int64)]
+
+
+FUTURE_VISIBILITY_MAX_CELLS = 114688    # FO_FUTURE_VISIBILITY_MAX_CELLS: the largest window the first-seen outputs take
+
+
+class FutureVisibility(C.Structure):    # fo_future_visibility_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("t_stride", C.c_int32), ("n_rays", C.c_int32),
+                ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_dirs", C.c_void_p), ("r", C.c_double), ("fov_deg", C.c_double),
+                ("d_heading", C.c_void_p), ("O", C.c_int32), ("n_slices", C.c_int32), ("d_ocorn", C.c_void_p),
+                ("d_oflags", C.c_void_p), ("d_occ_idx", C.c_void_p), ("d_n_occ", C.c_void_p), ("win_ix0", C.c_int32),
+                ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32), ("d_revealed", C.c_void_p),
+                ("d_area", C.c_void_p), ("d_revealed_new", C.c_void_p), ("d_revealed_any", C.c_void_p)]
 
 
 SPAWN_CELLS, SPAWN_RULES, SPAWN_BOTH = 0, 1, 2
@@ -158,6 +170,7 @@ def load():
                                         + [C.c_int] * 4 + [dp] * 7 + [vp])
     lib.fo_scene_future_visibility.argtypes = ([vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, dp, D, C.c_int, dp, dp, ip, ip]
                                                + [C.c_int] * 3 + [ip, dp, vp])
+    lib.fo_scene_future_visibility_ex.argtypes = [vp, C.POINTER(FutureVisibility), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

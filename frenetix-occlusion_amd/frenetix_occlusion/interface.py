@@ -259,6 +259,56 @@ class FOInterface:
         arr = trajectories_to_arrays(trajectories)
         return self.sensor_model.future_visibility(arr["x"], arr["y"], t_stride=t_stride, n_rays=n_rays)
 
+    def future_visibility(self, trajectories, t_stride=5, n_rays=192, fov="full", occluders="now", first_seen=True):
+        """EXTENSION, not part of the reference: :meth:`future_visibility_batch` with moving occluders, the sensor's field
+        of view and first-seen counts (:meth:`SensorModel.future_visibility_ex`; returns its
+        :class:`~frenetix_occlusion.sensor_model.FutureVisibility`).  Pose k is trajectory sample k ``t_stride``.
+
+        ``fov``: ``"full"`` (world-aligned full circle), ``"sensor"`` (``sensor_model.sensor_angle``) or degrees; an open
+        fan turns with the trajectory's ``theta`` at the pose.  ``occluders``: ``"now"`` (the obstacles of the last
+        ``evaluate_scenario``, one slice), ``"predicted"`` (that call's ``predictions``: obstacle id at ``pos_list[k
+        t_stride]`` / ``orientation_list[k t_stride]``, held at the last entry; obstacles without a prediction stay where
+        they are), ``"scenario"`` (the recorded states at ``timestep + k t_stride``, ``FOObstacles.rows_at``) or
+        ``(corners [S, O, 4, 2], flags [S, O])``.  ``first_seen``: ``revealed_new`` / ``revealed_any`` as well."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sensor_model import FutureVisibility
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("future_visibility needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        M, T = np.shape(arr["x"])
+        K = (T + t_stride - 1) // t_stride
+        if isinstance(fov, str):
+            if fov not in ("full", "sensor"):
+                raise ValueError(f"fov: 'full', 'sensor' or degrees, not {fov!r}")
+            fov_deg = 360.0 if fov == "full" else float(self.sensor_model.sensor_angle)
+        else:
+            fov_deg = float(fov)
+        samples = [k * t_stride for k in range(K)]
+        slice_ts = [self.timestep]
+        if isinstance(occluders, str):
+            if occluders == "now":
+                occ = None
+            elif occluders == "predicted":
+                occ = self.fo_obstacles.predicted_rows(self.predictions, samples)
+                slice_ts = [self.timestep + j for j in samples]
+            elif occluders == "scenario":
+                slice_ts = [self.timestep + j for j in samples]
+                occ = self.fo_obstacles.rows_at(slice_ts)
+            else:
+                raise ValueError(f"occluders: 'now', 'predicted', 'scenario' or (corners, flags), not {occluders!r}")
+        else:
+            occ, slice_ts = occluders, None
+        if M == 0:
+            dev = self.sensor_model.device
+            e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=dev)
+            return FutureVisibility(e(0, K), e(0, K, dt=torch.float64), e(0, K) if first_seen else None,
+                                    e(0) if first_seen else None, slice_ts)
+        theta = arr["theta"] if fov_deg < 359.9 else None
+        out = self.sensor_model.future_visibility_ex(arr["x"], arr["y"], theta, t_stride=t_stride, n_rays=n_rays, fov=fov_deg,
+                                                     occluders=occ, first_seen=first_seen)
+        out.slice_timesteps = slice_ts
+        return out
+
     def _update_time_step(self, timestep):
         self.timestep = timestep
         self.sensor_model.timestep = timestep

@@ -244,6 +244,20 @@ class VisibleArea:
         return out
 
 
+@dataclass
+class FutureVisibility:
+    """what :meth:`SensorModel.future_visibility_ex` returns (device tensors, K = ceil(T / t_stride) poses):
+    ``revealed [M, K]`` int32 and ``area [M, K]`` float64 as for ``future_visibility``; ``revealed_new [M, K]`` int32
+    (cells a pose sees that no earlier pose of its trajectory saw) and ``revealed_any [M]`` int32 (their row sum: distinct
+    cells the trajectory reveals), None unless asked for; ``slice_timesteps``: the time step each occluder slice stands
+    for (None when the caller handed in slices of its own)."""
+    revealed: torch.Tensor
+    area: torch.Tensor
+    revealed_new: Optional[torch.Tensor] = None
+    revealed_any: Optional[torch.Tensor] = None
+    slice_timesteps: Optional[list] = None
+
+
 class SensorModel:
     def __init__(self, lanelet_network, ref_path, sensor_radius=30, sensor_angle=90, debug=True, visualization=None,
                  ctx: Optional[N.Context] = None, n_rays=720, cell_size=0.5, device=0, routes=0,
@@ -689,6 +703,76 @@ class SensorModel:
                       self.n_occluded.data_ptr(), w.ix0, w.iy0, w.nx, revealed.data_ptr(), area.data_ptr(),
                       N.current_stream(self._dev_index))
         return revealed, area
+
+    def future_visibility_ex(self, x, y, theta=None, *, t_stride=5, n_rays=192, radius=None, fov="full", occluders=None,
+                             first_seen=False):
+        """Extended :meth:`future_visibility` (``fo_scene_future_visibility_ex``); returns a :class:`FutureVisibility`.
+        Queued on the current stream, no host synchronisation.
+
+        ``theta [M, T]``: headings of the samples; the fan of pose k is rotated by (cos, sin) of ``theta[:, k t_stride]``
+        (numpy's for host arrays, torch's on the device for device tensors; None: world-aligned).  ``fov``: ``"full"`` or degrees; below 359.9 an open fan of ``n_rays`` rays from -fov/2 to
+        +fov/2 about the pose heading, which needs ``theta``.  ``occluders``: None = the obstacles of the last
+        ``upload_obstacles`` (one slice, what ``future_visibility`` casts against), or ``(corners [S, O, 4, 2], flags [S, O])``
+        -- pose k casts against slice min(k, S - 1) (flags bit 0 present, bit 1 occludes).  ``first_seen``: also the
+        first-seen counts (a workgroup per trajectory; the window may hold at most
+        ``_native.FUTURE_VISIBILITY_MAX_CELLS`` cells)."""
+        if self.window is None:
+            raise RuntimeError("future_visibility_ex needs the occluded set of a previous launch()")
+        dev = self.device
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))).to(
+            dev, torch.float64).contiguous()
+        tx, ty = as_dev(x), as_dev(y)
+        M, T = tx.shape
+        K = (T + t_stride - 1) // t_stride
+        r = float(self.sensor_radius if radius is None else radius)
+        fov_deg = 360.0 if isinstance(fov, str) and fov == "full" else float(fov)
+        if fov_deg >= 359.9:
+            fov_deg = 360.0     # the full fan of future_visibility
+        key = (int(n_rays), fov_deg)
+        if getattr(self, "_fvx_dirs_key", None) != key:
+            self._fvx_dirs = torch.empty((key[0], 2), dtype=torch.float64, device=dev)
+            self.ctx.call("fo_scene_fan", key[0], 0.0, fov_deg, r, 0, self._fvx_dirs.data_ptr(), None, None,
+                          N.current_stream(self._dev_index))
+            self._fvx_dirs_key = key
+        heading = None
+        if theta is not None:     # [M, K, 2], computed once: on the host for host samples (a checker can redo them), else here
+            if torch.is_tensor(theta):
+                th = theta.to(dev, torch.float64)[:, ::t_stride]
+                heading = torch.stack((torch.cos(th), torch.sin(th)), -1).contiguous()
+            else:
+                th = np.asarray(theta, dtype=np.float64)[:, ::t_stride]
+                heading = as_dev(np.stack((np.cos(th), np.sin(th)), -1))
+        if occluders is None:
+            d_corn, _, d_flags, O = getattr(self, "_obst", (None, None, None, 0))
+            S = 1
+            slice_ts = [getattr(self, "timestep", None)]
+        else:
+            corn, flags = occluders
+            d_corn = (corn if torch.is_tensor(corn) else torch.as_tensor(np.ascontiguousarray(corn, dtype=np.float64)))
+            d_flags = (flags if torch.is_tensor(flags) else torch.as_tensor(np.ascontiguousarray(flags, dtype=np.uint8)))
+            d_corn = d_corn.to(dev, torch.float64).contiguous()
+            d_flags = d_flags.to(dev, torch.uint8).contiguous()
+            if d_corn.dim() != 4 or d_corn.shape[2:] != (4, 2) or tuple(d_flags.shape) != tuple(d_corn.shape[:2]):
+                raise ValueError("occluders: corners [S, O, 4, 2] and flags [S, O]")
+            S, O = int(d_corn.shape[0]), int(d_corn.shape[1])
+            slice_ts = None
+        revealed = torch.empty((M, K), dtype=torch.int32, device=dev)
+        area = torch.empty((M, K), dtype=torch.float64, device=dev)
+        new = torch.empty((M, K), dtype=torch.int32, device=dev) if first_seen else None
+        any_ = torch.empty(M, dtype=torch.int32, device=dev) if first_seen else None
+        w = self.window
+        p = lambda t: t.data_ptr() if t is not None else None
+        args = N.FutureVisibility(M=M, T=T, t_stride=int(t_stride), n_rays=key[0], d_x=tx.data_ptr(), d_y=ty.data_ptr(),
+                                  d_dirs=self._fvx_dirs.data_ptr(), r=r, fov_deg=fov_deg, d_heading=p(heading), O=O,
+                                  n_slices=S, d_ocorn=p(d_corn), d_oflags=p(d_flags),
+                                  d_occ_idx=self.occluded_idx_buffer.data_ptr(), d_n_occ=self.n_occluded.data_ptr(),
+                                  win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny, d_revealed=revealed.data_ptr(),
+                                  d_area=area.data_ptr(), d_revealed_new=p(new), d_revealed_any=p(any_))
+        self.ctx.call("fo_scene_future_visibility_ex", C.byref(args), N.current_stream(self._dev_index))
+        # (inputs made here stay referenced until the next call: the caching allocator may not hand them out earlier anyway,
+        # they are freed in stream order)
+        self._fvx_inputs = (tx, ty, heading, d_corn, d_flags)
+        return FutureVisibility(revealed, area, new, any_, slice_ts)
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

@@ -139,6 +139,21 @@ class FOObstacles:
         tb = self._table
         if tb is None:
             tb = self._table = self._build_table()
+        host, corn, cen, yaw, dims, flags, present, ya = self._rows(tb, timestep, H)
+        t0 = tb["t0_list"]
+        for i, o in enumerate(self.fo_obstacles):
+            o.global_timestep = timestep
+            o.relative_time_step = timestep - t0[i]
+            o._current_visible = False
+            if present[i]:
+                o.current_pos, o.current_orientation, o.current_corner_points = cen[i], float(ya[i]), corn[i]
+            else:
+                o.current_pos = o.current_orientation = o.current_corner_points = None
+        self._packed = (host, corn, cen, flags, yaw, dims)
+
+    def _rows(self, tb, timestep, H):
+        """the rows of time step ``timestep`` in a fresh host buffer (layout of ``packed()``) -- what ``update`` writes"""
+        O = len(self.fo_obstacles)
         host = np.empty(O * 105, dtype=np.uint8)                       # fresh per step: last step's views stay what they were
         corn = host[:O * 64].view(np.float64).reshape(O, 4, 2)
         cen = host[O * 64:O * 80].view(np.float64).reshape(O, 2)
@@ -168,16 +183,53 @@ class FOObstacles:
             if not present.all():
                 gone = ~present
                 corn[gone] = 0.0; cen[gone] = 0.0; yaw[gone] = 0.0; dims[gone] = 0.0; flags[gone] = 0
-        t0 = tb["t0_list"]
+        return host, corn, cen, yaw, dims, flags, present, ya
+
+    def rows_at(self, timesteps):
+        """corner points [S, O, 4, 2] and flags [S, O] (uint8, as ``arrays_full``) of the obstacles at each of
+        ``timesteps``: the rows ``update(t)`` would write, bit for bit, without moving any obstacle (occluder slices for
+        ``SensorModel.future_visibility_ex``)"""
+        O, S = len(self.fo_obstacles), len(timesteps)
+        corn, flags = np.zeros((S, O, 4, 2)), np.zeros((S, O), dtype=np.uint8)
+        if O == 0:
+            return corn, flags
+        tb = self._table
+        if tb is None:
+            tb = self._table = self._build_table()
+        H = _pyhost()
+        for i, t in enumerate(timesteps):
+            _, c, _, _, _, f, _, _ = self._rows(tb, int(t), H)
+            corn[i], flags[i] = c, f
+        return corn, flags
+
+    def predicted_rows(self, predictions, samples):
+        """corner points [S, O, 4, 2] and flags [S, O] with every obstacle that has a prediction moved to it: slice s
+        puts obstacle ``id`` at ``pos_list[j]`` / ``orientation_list[j]`` of ``predictions[id]`` with j = samples[s] held at
+        the prediction's last entry (the corner formula of ``scenario.Obstacle.corners``, the obstacle's own dimensions);
+        obstacles without a prediction keep the rows of the current step (``arrays_full``) in every slice"""
+        corn0, _, flags0, _, _ = self.arrays_full()
+        S = len(samples)
+        corn = np.repeat(np.asarray(corn0, dtype=np.float64)[None], S, axis=0)
+        flags = np.repeat(np.asarray(flags0, dtype=np.uint8)[None], S, axis=0)
+        preds = predictions or {}
+        if not preds:
+            return corn, flags
+        tb = self._table
+        if tb is None:
+            tb = self._table = self._build_table()
         for i, o in enumerate(self.fo_obstacles):
-            o.global_timestep = timestep
-            o.relative_time_step = timestep - t0[i]
-            o._current_visible = False
-            if present[i]:
-                o.current_pos, o.current_orientation, o.current_corner_points = cen[i], float(ya[i]), corn[i]
-            else:
-                o.current_pos = o.current_orientation = o.current_corner_points = None
-        self._packed = (host, corn, cen, flags, yaw, dims)
+            p = preds.get(o.obstacle_id)
+            if p is None:
+                continue
+            pos, ori = np.asarray(p["pos_list"], dtype=np.float64), np.asarray(p["orientation_list"], dtype=np.float64)
+            n = min(len(pos), len(ori))
+            if n == 0:
+                continue
+            for s, j in enumerate(samples):
+                jj = min(int(j), n - 1)
+                corn[s, i] = o._o.corners((float(pos[jj, 0]), float(pos[jj, 1]), float(ori[jj])))
+                flags[s, i] = tb["flags"][i]      # a predicted obstacle is present
+        return corn, flags
 
     def _build_table(self):
         obs = [o._o for o in self.fo_obstacles]

@@ -265,6 +265,37 @@ int fo_scene_future_visibility(fo_ctx *ctx, int M, int T, const double *d_x, con
                                const int32_t *d_occ_idx, const int32_t *d_n_occ, int win_ix0, int win_iy0, int win_nx,
                                int32_t *d_revealed, double *d_area, void *stream);
 
+/* EXTENSION, not part of the reference: the extended form of fo_scene_future_visibility (same meaning where the names are
+ * the same; with n_slices = 1, fov_deg >= 359.9, d_heading = NULL and no first-seen outputs it computes the same bits).
+ * Occluder slices: d_ocorn [n_slices][O][4][2], d_oflags [n_slices][O]; pose k reads slice min(k, n_slices - 1), so
+ * obstacles move, appear (bit 0 set) or leave (cleared) along the trajectory.  Field of view: fov_deg >= 359.9 is a full
+ * circle; below, d_dirs is the open fan about heading 0 (fo_scene_fan with yaw 0 and this fov_deg: rays from -fov/2 to
+ * +fov/2 inclusive) -- the polygon is pose + hit points (open shoelace sum) and a cell outside the sector is not revealed.
+ * d_heading [M][K][2] (unit (cos, sin) per pose, or NULL = world-aligned; required below 359.9): ray i of pose (m, k) is
+ * (c ux - s uy, s ux + c uy) in float64 without contraction.  First-seen outputs (either may be NULL):
+ * d_revealed_new [M][K] = cells of the occluded set inside pose k's fan and inside no earlier pose's fan of trajectory m,
+ * d_revealed_any [M] = its row sum; exact integers (a workgroup per trajectory walks its poses in order with a seen set
+ * in LDS), which needs win_nx * win_ny <= FO_FUTURE_VISIBILITY_MAX_CELLS.  FO_E_ARG: n_slices < 1, n_rays outside
+ * [4, 768], a sector without d_heading, a window above the capacity with first-seen outputs, a missing buffer. */
+#define FO_FUTURE_VISIBILITY_MAX_CELLS 114688
+typedef struct {
+  int32_t M, T, t_stride, n_rays;
+  const double *d_x, *d_y;                /* [M][T] */
+  const double *d_dirs;                   /* [n_rays][2] unit fan about heading 0 */
+  double r, fov_deg;
+  const double *d_heading;                /* [M][K][2] or NULL */
+  int32_t O, n_slices;
+  const double *d_ocorn;                  /* [n_slices][O][4][2] */
+  const uint8_t *d_oflags;                /* [n_slices][O] */
+  const int32_t *d_occ_idx, *d_n_occ;     /* the occluded set of a fo_scene_visibility call ... */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* ... and its window */
+  int32_t *d_revealed;                    /* [M][K] */
+  double *d_area;                         /* [M][K] */
+  int32_t *d_revealed_new;                /* [M][K] or NULL */
+  int32_t *d_revealed_any;                /* [M] or NULL */
+} fo_future_visibility_t;
+int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in
