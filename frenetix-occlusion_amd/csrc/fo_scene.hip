@@ -22,6 +22,7 @@
 //                          workgroup per obstacle (5 mm skin)
 //   fo_flag_compact_kernel deterministic stream compaction in one launch (ballot prefix inside a block, every block
 //                          sums the counts before it; fo_flag_scan/scatter for very large windows)
+//   fo_hr_*_kernel         hidden-traffic reach forecast, an extension outside the step (fo_hidden_reach.hpp)
 //   fo_spawn_flag_kernel   candidate cells (+ block counts), fo_spawn_predict_kernel (evenly spaced pick + heading +
 //                          predictions in the sweep's agent layout)
 #include <hip/hip_runtime.h>
@@ -30,6 +31,7 @@
 #include "fo_ctx.hpp"
 #include "fo_prep_traj.hpp"
 #include "fo_agent_rows.hpp"
+#include "fo_hidden_reach.hpp"
 
 namespace {
 
@@ -105,6 +107,9 @@ struct Scene {
   // occlusion memory (fo_scene_set_occlusion_memory): armed for the next visibility stage only, caller-owned buffers
   bool om_armed = false;
   fo_occlusion_memory_t om{};
+  // hidden-traffic reach forecast (fo_scene_hidden_reach): row distances of the grown window, allocated by its first call
+  uint8_t *d_hr_g = nullptr;
+  size_t cap_hr_g = 0;
 };
 
 Scene *scene_of(fo_ctx *ctx) {
@@ -1587,7 +1592,7 @@ extern "C" {
 void fo_scene_destroy_(fo_ctx *ctx) {
   if (!ctx || !ctx->scene) return;
   Scene *sc = (Scene *)ctx->scene;
-  void *ptrs[] = {sc->d_vis32, sc->d_flags, sc->d_blk, sc->d_flags2, sc->d_blk2, sc->d_cand, sc->d_ncand, sc->d_amb, sc->d_namb, sc->d_rule_rec, sc->d_rule_lab, sc->d_rule_cnt, sc->d_ofar};
+  void *ptrs[] = {sc->d_vis32, sc->d_flags, sc->d_blk, sc->d_flags2, sc->d_blk2, sc->d_cand, sc->d_ncand, sc->d_amb, sc->d_namb, sc->d_rule_rec, sc->d_rule_lab, sc->d_rule_cnt, sc->d_ofar, sc->d_hr_g};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   map_release(sc->map);
@@ -2012,6 +2017,70 @@ int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, 
   // seen set: whole 1 KB rows for the largest list the window can hold
   const size_t seen_bytes = (size_t)((cells + FV_SEEN_CELLS - 1) / FV_SEEN_CELLS) * FV_THREADS * sizeof(uint32_t);
   return launch_future_visibility(ctx, a, p->M, sector, fs, seen_bytes, stream);
+}
+
+int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_hidden_reach: call fo_scene_set_map first");
+  if (!p) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no parameters");
+  Scene *sc = (Scene *)ctx->scene;
+  if (sc->map->P < 1 || !sc->map->d_raster) return fo_fail(ctx, FO_E_STATE, "fo_scene_hidden_reach: call fo_scene_set_map first");
+  if (p->J < 1 || p->J > HR_MAX_J)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: J = %d outside [1, %d] (arrival steps are bytes, 255 = never)", p->J, HR_MAX_J);
+  if (!p->h_r2) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no reach table h_r2 [J]");
+  if (!p->d_arrival) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no buffer for the arrival map (d_arrival is required)");
+  if (!p->d_cls) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no cell classes (d_cls of the visibility stage)");
+  if (p->win_nx < 1 || p->win_ny < 1 || p->win_nx > 32768 || p->win_ny > 32768)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: window %d x %d outside [1, 32768]^2", p->win_nx, p->win_ny);
+  if (p->h_r2[0] < 0) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2[0] = %d is negative", p->h_r2[0]);
+  for (int j = 1; j < p->J; ++j)
+    if (p->h_r2[j] < p->h_r2[j - 1])
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2 decreases at entry %d (%d after %d)", j, p->h_r2[j], p->h_r2[j - 1]);
+  constexpr int cap = FO_HIDDEN_REACH_MAX_HALO;
+  const int r2max = p->h_r2[p->J - 1];
+  if (r2max >= (cap + 1) * (cap + 1))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2[J-1] = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
+                   "(shorten the horizon or lower v_max; the reach is never cut short)", r2max, cap);
+  int h = (int)sqrt((double)r2max);
+  while (h * h > r2max) --h;
+  while ((h + 1) * (h + 1) <= r2max) ++h;
+  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: M = %d", p->M);
+  if (p->M > 0) {
+    if (p->T < 1 || p->T > p->J)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: T = %d outside [1, J = %d] (every sample needs its reach)", p->T, p->J);
+    if (!p->d_x || !p->d_y || !p->d_heading)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0");
+    if (!p->d_cells || !p->d_first || !p->d_slack)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: d_cells [M][T], d_first [M] and d_slack [M] are required with M > 0");
+    const double ext = HR_MAX_EXTENT * sc->map->cs;   // (NaN fails every comparison)
+    if (!(p->hl >= 0.0 && p->hl <= ext) || !(p->hw >= 0.0 && p->hw <= ext) || !(fabs(p->wb) <= ext))
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: half extents outside [0, %g m] or |wb| above it (hl = %g, hw = %g, wb = %g; "
+                     "FO_HIDDEN_REACH_MAX_HALF_EXTENT = %d cells)", ext, p->hl, p->hw, p->wb, HR_MAX_EXTENT);
+  }
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int nx = p->win_nx, ny = p->win_ny;
+  int rc;
+  if ((rc = fo_reserve(ctx, &sc->d_hr_g, &sc->cap_hr_g, (size_t)(ny + 2 * h) * nx))) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  HrMapArgs a{sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_cls, p->d_hidden_or_null,
+              h, p->J, sc->d_hr_g, p->d_arrival};
+  HrR2 r2;
+  for (int j = 0; j < HR_MAX_J; ++j) r2.v[j] = p->h_r2[j < p->J ? j : p->J - 1];
+  const size_t lds_rows = (size_t)((nx + 2 * h + 63) / 64) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(fo_hr_rows_kernel, dim3(ny + 2 * h), dim3(HR_THREADS), lds_rows, s, a);
+  hipLaunchKernelGGL(fo_hr_cols_kernel, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
+                     (size_t)(HR_TY + 2 * h) * HR_TX, s, a, r2);
+  if (p->M > 0) {
+    int G = 1;
+    while (G < p->T && G < 64) G <<= 1;
+    HrTrajArgs t{p->M, p->T, G, p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0,
+                 sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_arrival,
+                 p->d_cells, p->d_first, p->d_slack};
+    const int per_block = HR_THREADS / G;
+    const dim3 grid((unsigned)(((size_t)p->M + per_block - 1) / per_block));
+    hipLaunchKernelGGL(fo_hr_traj_kernel, grid, dim3(HR_THREADS), 0, s, t);
+  }
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
 }
 
 // fo_scene_spawn; at (fo_step_run): the prediction kernel also writes its slots' rows of the sweep's agent table, and the

@@ -33,7 +33,7 @@ EXPORTS = [
     "fo_scene_set_map", "fo_scene_share_map", "fo_scene_set_edge_lines", "fo_scene_set_routes", "fo_scene_map_info", "fo_scene_copy_raster", "fo_scene_fan", "fo_scene_visibility", "fo_scene_future_visibility", "fo_scene_spawn",
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
-    "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex",
+    "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
 ]
 
 
@@ -79,6 +79,19 @@ class FutureVisibility(C.Structure):    # fo_future_visibility_t
                 ("d_oflags", C.c_void_p), ("d_occ_idx", C.c_void_p), ("d_n_occ", C.c_void_p), ("win_ix0", C.c_int32),
                 ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32), ("d_revealed", C.c_void_p),
                 ("d_area", C.c_void_p), ("d_revealed_new", C.c_void_p), ("d_revealed_any", C.c_void_p)]
+
+
+HIDDEN_REACH_MAX_HALO = 254      # FO_HIDDEN_REACH_MAX_HALO: the longest reach (cells) of the hidden-traffic forecast
+HIDDEN_REACH_MAX_HALF_EXTENT = 64   # FO_HIDDEN_REACH_MAX_HALF_EXTENT: the largest half extent of its ego rectangle (cells)
+HIDDEN_REACH_MAX_J = 254         # samples of its horizon (arrival steps are bytes, 255 = never)
+
+
+class HiddenReach(C.Structure):         # fo_hidden_reach_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double), ("J", C.c_int32),
+                ("h_r2", C.POINTER(C.c_int32)), ("d_cls", C.c_void_p), ("d_hidden_or_null", C.c_void_p),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("d_arrival", C.c_void_p), ("d_cells", C.c_void_p), ("d_first", C.c_void_p), ("d_slack", C.c_void_p)]
 
 
 SPAWN_CELLS, SPAWN_RULES, SPAWN_BOTH = 0, 1, 2
@@ -171,6 +184,7 @@ def load():
     lib.fo_scene_future_visibility.argtypes = ([vp, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, dp, D, C.c_int, dp, dp, ip, ip]
                                                + [C.c_int] * 3 + [ip, dp, vp])
     lib.fo_scene_future_visibility_ex.argtypes = [vp, C.POINTER(FutureVisibility), vp]
+    lib.fo_scene_hidden_reach.argtypes = [vp, C.POINTER(HiddenReach), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -258,6 +258,41 @@ class FutureVisibility:
     slice_timesteps: Optional[list] = None
 
 
+def hidden_reach_r2(v_max, dt, margin, cell_size, J):
+    """the reach table of the hidden-traffic forecast: ``R2[j] = occlusion_memory_r2(v_max, j dt, margin,
+    cell_size)`` for the J samples of a horizon -- what the occlusion memory uses for a step of j timesteps"""
+    return np.array([occlusion_memory_r2(v_max, j * float(dt), margin, cell_size) for j in range(int(J))], dtype=np.int32)
+
+
+def unit_headings(theta):
+    """(cos, sin) of the sample headings as a float64 host array [..., 2]: the ONE place the forecast's footprints get their
+    rotation from (the device takes no sine or cosine; a checker is handed these numbers as data)"""
+    th = theta.detach().cpu().numpy() if torch.is_tensor(theta) else theta
+    th = np.asarray(th, dtype=np.float64)
+    return np.stack((np.cos(th), np.sin(th)), -1)
+
+
+@dataclass
+class HiddenReach:
+    """what :meth:`SensorModel.hidden_reach` returns (device tensors): ``arrival [ny, nx]`` uint8 over ``window`` -- the
+    first horizon sample at which a road user hidden now may be in the cell, 255 = not within the horizon or not road;
+    ``cells [M, T]`` int32 -- cells of the ego rectangle at sample k that hidden traffic may have reached by then;
+    ``first [M]`` int32 -- the first such sample, -1 = none; ``slack [M]`` int32 -- min over samples and footprint cells of
+    (arrival - k), ``SLACK_NONE`` where the trajectory meets no reachable cell (``slack <= 0`` iff ``first >= 0``).
+    ``r2`` (host int32 [J]) is the reach table, ``heading`` the (cos, sin) [M, T, 2] the footprints were turned by,
+    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step."""
+    arrival: torch.Tensor
+    cells: torch.Tensor
+    first: torch.Tensor
+    slack: torch.Tensor
+    r2: np.ndarray
+    window: CellWindow
+    heading: Optional[torch.Tensor] = None
+    from_memory: bool = False
+
+    SLACK_NONE = 2 ** 31 - 1
+
+
 class SensorModel:
     def __init__(self, lanelet_network, ref_path, sensor_radius=30, sensor_angle=90, debug=True, visualization=None,
                  ctx: Optional[N.Context] = None, n_rays=720, cell_size=0.5, device=0, routes=0,
@@ -773,6 +808,67 @@ class SensorModel:
         # they are freed in stream order)
         self._fvx_inputs = (tx, ty, heading, d_corn, d_flags)
         return FutureVisibility(revealed, area, new, any_, slice_ts)
+
+    # ---- extension, not part of the reference
+    def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None):
+        """Hidden-traffic reach forecast (``fo_scene_hidden_reach``); returns a :class:`HiddenReach`.  The kernels are queued
+        on the current stream and nobody waits for them; ``theta`` is turned into (cos, sin) on the HOST (:func:`unit_headings`:
+        the device takes no sine or cosine), so a ``theta`` that lives on the device is first copied back, which waits for the
+        stream -- hand ``theta`` over as a host array, as a planner's trajectory objects give it, to avoid that.
+
+        ``x, y, theta [M, T]``: candidate trajectories, sample k at ``k dt`` from now (M = 0: the arrival map alone).
+        ``vehicle``: (length, width, wb_rear_axle) of the ego rectangle, ``inflate`` (m) is added to both half extents.
+        A road user hidden now -- in the occlusion memory's hidden set when the memory ran this step, else anywhere on
+        road that is not visible -- moves at up to ``v_max`` (m/s); ``margin`` (m, None = sqrt(2) cell sizes) as for the
+        memory.  ``lengths [M]``: samples ``k >= lengths[m]`` of a ragged batch contribute nothing."""
+        if self.window is None:
+            raise RuntimeError("hidden_reach needs the cell classes of a previous launch()")
+        length, width, wb = (float(v) for v in tuple(vehicle)[:3])
+        v_max, dt, inflate = float(v_max), float(dt), float(inflate)
+        margin = math.sqrt(2.0) * self.cell_size if margin is None else float(margin)
+        if not (v_max >= 0.0 and margin >= 0.0 and dt > 0.0):
+            raise ValueError("hidden_reach: v_max >= 0, margin >= 0 and dt > 0")
+        hl, hw = 0.5 * length + inflate, 0.5 * width + inflate
+        ext = N.HIDDEN_REACH_MAX_HALF_EXTENT * self.cell_size
+        if not (0.0 <= hl <= ext and 0.0 <= hw <= ext and abs(wb) <= ext):
+            raise ValueError(f"hidden_reach: the inflated half extents and |wb_rear_axle| must lie in [0, {ext} m]")
+        M, T = (int(v) for v in x.shape)
+        if tuple(y.shape) != (M, T) or tuple(theta.shape) != (M, T):
+            raise ValueError("hidden_reach: x, y and theta must be [M, T]")
+        if not 1 <= T <= N.HIDDEN_REACH_MAX_J:
+            raise ValueError(f"hidden_reach: {T} samples per trajectory, 1 .. {N.HIDDEN_REACH_MAX_J} are possible")
+        r2 = hidden_reach_r2(v_max, dt, margin, self.cell_size, T)
+        if int(r2[-1]) >= (N.HIDDEN_REACH_MAX_HALO + 1) ** 2:
+            raise ValueError(f"hidden_reach: a reach of {math.isqrt(int(r2[-1]))} cells at the end of the horizon, at most "
+                             f"{N.HIDDEN_REACH_MAX_HALO} are possible (shorter horizon, lower v_max or larger cells)")
+        if lengths is not None and tuple(np.shape(lengths)) != (M,):
+            raise ValueError("hidden_reach: lengths must be [M]")
+        dev = self.device
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))).to(
+            dev, torch.float64).contiguous()
+        tx, ty = as_dev(x), as_dev(y)
+        heading = as_dev(unit_headings(theta))
+        tlen = None
+        if lengths is not None:
+            tlen = (lengths if torch.is_tensor(lengths) else torch.as_tensor(np.ascontiguousarray(lengths, dtype=np.int32)))
+            tlen = tlen.to(dev, torch.int32).contiguous()
+        w = self.window
+        # this step's H_k when the occlusion memory ran in the stage that produced the classes, else the reset definition
+        hidden = None
+        if self._om_plan is not None and self._om_prev_window is w:
+            hidden = self._om_buf[1 - self._om_cur]
+        arrival = torch.empty((w.ny, w.nx), dtype=torch.uint8, device=dev)
+        cells = torch.empty((M, T), dtype=torch.int32, device=dev)
+        first = torch.empty(M, dtype=torch.int32, device=dev)
+        slack = torch.empty(M, dtype=torch.int32, device=dev)
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        args = N.HiddenReach(M=M, T=T, d_x=p(tx), d_y=p(ty), d_heading=p(heading), d_len_or_null=p(tlen), hl=hl, hw=hw, wb=wb,
+                             J=T, h_r2=r2.ctypes.data_as(C.POINTER(C.c_int32)), d_cls=self.cell_class.data_ptr(),
+                             d_hidden_or_null=p(hidden), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
+                             d_arrival=arrival.data_ptr(), d_cells=p(cells), d_first=p(first), d_slack=p(slack))
+        self.ctx.call("fo_scene_hidden_reach", C.byref(args), N.current_stream(self._dev_index))
+        self._hr_inputs = (tx, ty, heading, tlen)      # (stay referenced until the next call, as in future_visibility_ex)
+        return HiddenReach(arrival, cells, first, slack, r2, w, heading, hidden is not None)
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

@@ -296,6 +296,57 @@ typedef struct {
 } fo_future_visibility_t;
 int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic reach forecast -- where road users the ego cannot see
+ * may be at each sample of the planning horizon, and which candidate trajectories sweep through such road.  Called after a
+ * visibility stage (d_cls + window: that call's cell classes), on the caller's stream; nothing of it runs unless it is called.
+ * All of it is integer arithmetic on cell indices except one point-in-rectangle test, so every output is an exact integer.
+ *  Sources S(q), q a world-raster cell: inside the window d_hidden_or_null [ny][nx] (the H the occlusion memory wrote this
+ *   step, fo_occlusion_memory_t::d_cur) or, when NULL, !(c & 2) && (c & 5) != 0 (what H is after a reset); outside the window
+ *   on the raster the road bit; off the raster 0.
+ *  Reach table h_r2 [J] (HOST memory, read before the call returns): R2[j] = floor((v_max j dt + margin)^2 / cs^2), the r2
+ *   of fo_occlusion_memory_t for a step of j dt; non-decreasing, R2[0] >= 0.
+ *  D2(g) = min over q with S(q) = 1 of (gx - qx)^2 + (gy - qy)^2, searched over the window grown by h = isqrt(R2[J-1]) cells
+ *   on every side (nothing farther matters).  Euclidean, also across cells that are not road: an over-approximation.
+ *  d_arrival [ny][nx] uint8: A(g) = min { j : D2(g) <= R2[j] } for a road cell (c & 1), 255 = not within the horizon or not
+ *   road.  A cell outside the window counts as A = 0 if it is on the raster and road, else 255.
+ *  Footprint of trajectory m at sample k (time k dt): the sweep's ego rectangle -- centre (x + wb c, y + wb s), half extents
+ *   hl, hw, (c, s) = d_heading [M][T][2], the UNIT heading per sample (the device takes no sine or cosine).  World-raster
+ *   cell g with centre p = (x0 + (gx + 0.5) cs, y0 + (gy + 0.5) cs) is inside iff |u| <= hl and |w| <= hw with
+ *   ex = px - cx, ey = py - cy, u = ex c + ey s, w = ey c - ex s (float64, this order, no contraction).
+ *  d_cells [M][T] int32: footprint cells with A(g) <= k.  d_first [M] int32: smallest k with cells > 0, -1 = none.
+ *  d_slack [M] int32: min over k and footprint cells with A(g) != 255 of A(g) - k, INT32_MAX = no such cell (slack <= 0 iff
+ *   first >= 0).  d_len_or_null [M] int32: samples k >= len[m] contribute nothing and get cells = 0.
+ * With M = 0 only the map is computed.  Two launches for the map (rows, columns), one for the trajectories.
+ * FO_E_ARG (nothing is launched): J outside [1, 254]; T outside [1, J] with M > 0; h_r2 decreasing or negative;
+ * isqrt(h_r2[J-1]) > FO_HIDDEN_REACH_MAX_HALO (never a silently shortened reach); no h_r2, d_cls or d_arrival; with M > 0 no
+ * d_x / d_y / d_heading / d_cells / d_first / d_slack, or hl, hw or |wb| negative, NaN or above
+ * FO_HIDDEN_REACH_MAX_HALF_EXTENT cell sizes (a pose scans its rectangle's bounding box: the bound keeps that scan short; no
+ * road vehicle comes near it); a window outside [1, 32768]^2.  A heading that is not a unit vector is not detected: the
+ * scanned box is that of the unit rectangle, the result then is not the definition's.
+ * One call at a time per context: the row distances between the two map launches live in a workspace of the context (grown,
+ * i.e. freed and allocated, when a call needs more), so calls on different streams must not overlap -- the rule of every
+ * per-step workspace of the scene stage.
+ * FO_HIDDEN_REACH_MAX_HALO: the distance along a row is kept in a byte, h + 1 standing for "none within h", next to the
+ * arrival byte's 255 -- so h <= 254; the column pass then stages (16 + 2 h) x 64 bytes of LDS per workgroup (33 KB at 254). */
+#define FO_HIDDEN_REACH_MAX_HALO 254
+#define FO_HIDDEN_REACH_MAX_HALF_EXTENT 64
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* half length, half width (inflated by the caller), rear axle -> centre */
+  int32_t J;
+  const int32_t *h_r2;                      /* HOST [J] */
+  const uint8_t *d_cls;                     /* [win_ny][win_nx] */
+  const uint8_t *d_hidden_or_null;          /* [win_ny][win_nx] */
+  int32_t win_ix0, win_iy0, win_nx, win_ny;
+  uint8_t *d_arrival;                       /* [win_ny][win_nx] */
+  int32_t *d_cells;                         /* [M][T] */
+  int32_t *d_first, *d_slack;               /* [M] */
+} fo_hidden_reach_t;
+int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

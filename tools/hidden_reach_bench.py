@@ -1,0 +1,90 @@
+"""Time the hidden-traffic reach forecast (fo_scene_hidden_reach) with HIP events: the arrival map alone, the
+whole call, next to the visibility stage the forecast
+follows and the 720-ray first-seen future-visibility call on the same batch.
+
+    python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25]
+
+Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
+import argparse
+import json
+import math
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "frenetix-occlusion_amd")]
+from frenetix_occlusion import _native as N  # noqa: E402
+from frenetix_occlusion import scenario as SC, synthetic as SY  # noqa: E402
+from frenetix_occlusion.sensor_model import SensorModel  # noqa: E402
+from frenetix_occlusion.utils.fo_obstacle import FOObstacles  # noqa: E402
+
+
+def _median_ms(fn, calls):
+    fn()
+    torch.cuda.synchronize()
+    ts = []
+    for _ in range(calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        ts.append(e0.elapsed_time(e1))
+    return float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("M", nargs="?", type=int, default=10000)
+    ap.add_argument("--scene", default="city_grid", choices=("city_grid", "scenario1"))
+    ap.add_argument("--memory", action="store_true", help="occlusion memory on: the sources are its hidden set")
+    ap.add_argument("--steps", type=int, default=5, help="steps of the drive before the timed calls")
+    ap.add_argument("--v-max", type=float, default=13.9)
+    ap.add_argument("--calls", type=int, default=25)
+    a = ap.parse_args()
+    if a.scene == "city_grid":
+        sc = SC.synthetic_urban_grid()
+    else:
+        sc = SC.load_geometry_npz(os.path.join(ROOT, "tests", "golden", "scenario1_geometry.npz"))
+    ego0 = np.asarray(sc.ego_initial, dtype=np.float64)
+    yaw = float(ego0[2])
+    sm = SensorModel(sc.lanelets, None, sensor_radius=50.0, sensor_angle=360.0, n_rays=720)
+    if a.memory:
+        sm.enable_occlusion_memory(v_max=a.v_max, dt=0.1)
+    obs = FOObstacles(sc.obstacles)
+    for step in range(a.steps):
+        ego = ego0[:2] + 0.7634 * step * np.array([math.cos(yaw), math.sin(yaw)])
+        obs.update(step)
+        sm.calc_visible_and_occluded_area(step, ego, yaw, obs)
+    M, T, dev = a.M, 31, sm.device
+    traj = SY.make_trajectories(M, T, 0.1, seed=20240134, ego_pos=ego, ego_yaw=yaw)
+    tx, ty, tth = (torch.as_tensor(traj[k]).to(dev) for k in ("x", "y", "theta"))
+    veh = SY.VEHICLE_BMW320I[:3]
+    e = torch.empty((0, T), dtype=torch.float64, device=dev)
+    step_no = [a.steps]
+
+    def stage():        # (with the memory on, every stage is a memory step of one timestep)
+        sm.launch(ego, yaw, timestep=step_no[0])
+        step_no[0] += 1
+
+    res = {"scene": a.scene, "M": M, "T": T, "memory": bool(a.memory), "window": [sm.window.nx, sm.window.ny],
+           "build": N.build_id()[:12], "device": torch.cuda.get_device_name(0)}
+    res["visibility_stage_ms"] = _median_ms(stage, a.calls)
+    out = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1)
+    res["halo_cells"] = int(math.isqrt(int(out.r2[-1])))
+    res["map_only_ms"] = _median_ms(lambda: sm.hidden_reach(e, e, e, vehicle=veh, v_max=a.v_max, dt=0.1), a.calls)
+    res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1), a.calls)
+    res["future_visibility_720_first_seen_ms"] = _median_ms(
+        lambda: sm.future_visibility_ex(tx, ty, None, t_stride=5, n_rays=720, first_seen=True), a.calls)
+    torch.cuda.synchronize()
+    first = out.first.cpu().numpy()
+    res["trajectories_meeting_hidden_traffic"] = int((first >= 0).sum())
+    res["arrival_cells_reached"] = int((out.arrival.cpu().numpy() != 255).sum())
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
