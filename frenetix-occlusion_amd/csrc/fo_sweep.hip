@@ -68,7 +68,7 @@ __global__ void fo_erf_table_kernel(double2 *tab) {
 //   erf(x0 + d_true) = e + g d_true P,   P = (1 - s/3) + y (-1 + 2 y/3) + [y s/2 - y^3/3] + [s^2/10 - 2 s y^2/5 + 2 y^4/15] + ...
 //   evaluated as  P = a0 + y (-1 + 2 y / 3),  a0 = 1 - s/3.
 // The bracket is never evaluated: it contributes g(x0) d^5 (1/10 - 2 x0^2/5 + 2 x0^4/15) <= 1.13 * 0.1 * 256^-5 = 1.0e-13.
-// FO_ERF_ORDER 3 (default) also leaves out the two cubic terms  y s/2 - y^3/3 = d^3 x0 (1/2 - x0^2/3):  what is dropped is
+// The two cubic terms  y s/2 - y^3/3 = d^3 x0 (1/2 - x0^2/3)  are left out as well:  what is dropped is
 // g(x0) d^4 x0 (1/2 - x0^2/3), at most 0.18 * 256^-4 = 4.3e-11 per erf (at x0 = 0.6, |d| = 1/256; a fifth of that on average
 // over d), i.e. <= 2.6e-10 on a collision probability (nine products of two differences of erf, / 12; measured on the bench
 // batch against the oracle: see parity.float_max_abs_err of the bench line) -- a quarter of the 1e-9 every float output of
@@ -76,12 +76,8 @@ __global__ void fo_erf_table_kernel(double2 *tab) {
 // The price of the two terms is three instructions per erf, and the 36 erf of an in-gate sample are the one part of the
 // sweep kernel whose instructions count three times (the waves that hold the few agents next to the candidates' path carry
 // all of it, and their workgroups wait for them): 19 -> 16 -> 14 operations per erf took 6.5 % off the kernel (round 5).
-// FO_ERF_ORDER 4: the cubic terms kept, P = a0 + y (a1 + u/3), a1 = -1 + s/2, u = y (2 - y): 1.0e-13 per erf.
-// Either way the polynomial is grouped so that every fma has at most ONE constant that is not an inline operand (1.0, 2.0): a
+// The polynomial is grouped so that every fma has at most ONE constant that is not an inline operand (1.0, 2.0): a
 // VOP3 instruction of this chip reads one literal / SGPR pair, and a second constant costs two v_mov_b32 per erf to park it.
-#ifndef FO_ERF_ORDER
-#define FO_ERF_ORDER 3
-#endif
 // (Round 5, measured and dropped: the scale of y folded into the two constants of the inner fma, both parked in vector
 // registers by the caller -- one multiplication less per erf -- 0.529 ms against 0.515: four registers more across the box
 // loops of a kernel that sits at its register cap cost thirteen more spilled ones.)
@@ -97,13 +93,7 @@ __device__ __forceinline__ double fo_erf_fast128(const double2 *__restrict__ tab
   const double sq = d * d;
   const double a0 = fma(sq, -S / 3.0, 1.0);
   const double y = fi * (d * S);
-#if FO_ERF_ORDER >= 4
-  const double a1 = fma(sq, S / 2.0, -1.0);
-  const double u = y * (2.0 - y);
-  const double p = fma(y, fma(u, 1.0 / 3.0, a1), a0);
-#else
   const double p = fma(fma(y, 2.0 / 3.0, -1.0), y, a0);
-#endif
   return copysign(fma(e.y * d, p, e.x), v);
 }
 
@@ -134,11 +124,7 @@ __device__ __forceinline__ double fo_erf_lds(const double2 *__restrict__ tab, do
 // sqrt by one Goldschmidt step on v_rsq_f64 (relative error ~1e-14 instead of the correctly rounded ~25-instruction
 // expansion of sqrt()); x >= 0, x = 0 -> 0.  Consumers are compared at 1e-9; the distances rounded to 1e-3 take one more
 // correction (fo_mm).
-#ifndef FO_DIET
-#define FO_DIET 1   // 0: tuning builds -- the scalar-instruction diet of round 3 switched off (clamped row addresses, literals)
-#endif
 __device__ __forceinline__ double fo_sqrt(double x) {
-#if FO_DIET
   // x = 0: rsq gives +inf, the Goldschmidt step NaN, and v_max_f64(NaN, 0) = 0 -- a guard that needs no float64 literal
   // (1e-300 costs two s_mov per use: a scalar instruction is as dear to its wave as a vector one)
   const double g = __builtin_amdgcn_rsq(x);
@@ -149,40 +135,21 @@ __device__ __forceinline__ double fo_sqrt(double x) {
   double z;
   asm("v_max_f64 %0, %1, 0" : "=v"(z) : "v"(y));
   return z;
-#else
-  const double g = __builtin_amdgcn_rsq(fmax(x, 1e-300));
-  double y = x * g;
-  const double h = 0.5 * g;
-  const double r = fma(-h, y, 0.5);
-  y = fma(y, r, y);
-  return y;
-#endif
 }
 // Round 5: the same for x > 0 -- the squared relative speeds of the ring, which pass 1 writes with the smallest denormal added
 // (fo_sq_sum_pos: an inline integer constant 1 in a float64 operand IS that number, no literal, no extra instruction), so that
 // the guard of fo_sqrt is not needed where pass 2 takes the root: one instruction per list entry.
-#ifndef FO_P2_TINY
-#define FO_P2_TINY 1
-#endif
 __device__ __forceinline__ double fo_sqrt_pos(double x) {
-#if FO_P2_TINY
   const double g = __builtin_amdgcn_rsq(x);
   const double y = x * g;
   const double h = 0.5 * g;
   const double r = fma(-h, y, 0.5);
   return fma(y, r, y);
-#else
-  return fo_sqrt(x);
-#endif
 }
 __device__ __forceinline__ double fo_sq_sum_pos(double a, double b) {   // a^2 + b^2 (+ 4.9e-324)
-#if FO_P2_TINY
   double t;
   asm("v_fma_f64 %0, %1, %1, 1" : "=v"(t) : "v"(b));
   return fma(a, a, t);
-#else
-  return fma(a, a, b * b);
-#endif
 }
 // value with its three lowest mantissa bits replaced by u (0..7)
 __device__ __forceinline__ double fo_pack_low(double v, int u) {
@@ -200,30 +167,11 @@ __device__ __forceinline__ int fo_sel_b32(unsigned long long mask, int a, int b)
 __device__ __forceinline__ double fo_sel_hi(unsigned long long mask, double a, double b) {
   return __hiloint2double(fo_sel_b32(mask, __double2hiint(a), __double2hiint(b)), __double2loint(a));
 }
-#ifndef FO_EPI_SEL
-#define FO_EPI_SEL 1   // 0: tuning builds -- the per-pair epilogue as plain C (compare + v_cndmask chains on vcc): +1 % on the headline kernel (measured with the product build's flags on both sides; an earlier comparison across two flag sets had the sign wrong)
-#endif
 // a * b + c with three distinct register operands (the compiler prefers v_mov_b64 + v_fmac_f64 when c outlives the result)
-#ifndef FO_P2_FMA3
-#define FO_P2_FMA3 1
-#endif
-#ifndef FO_PROBE_PACK
-#define FO_PROBE_PACK 1
-#endif
-#ifndef FO_P2_RUNS
-#define FO_P2_RUNS 1
-#endif
-#ifndef FO_P2_UNROLL
-#define FO_P2_UNROLL 1
-#endif
 __device__ __forceinline__ double fo_fma3(double a, double b, double c) {
-#if FO_P2_FMA3
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
   return r;
-#else
-  return fma(a, b, c);
-#endif
 }
 
 __device__ __forceinline__ double fo_round3(double v) { return __builtin_rint(v * 1000.0) / 1000.0; }  // np.round(v,3)
@@ -367,31 +315,15 @@ __device__ __forceinline__ double fo_lr4s_coef(double ang, double side, double r
 // k == 0 the class of phi follows exactly from the signs of  S = d x h  and  C = d . h  (h = unit heading):
 // front  C > |S|,  rear  -C >= |S|,  side otherwise.  k != 0 <=> |rel - heading| > pi only has to be decided when phi is
 // not rear, where |rel - heading| is either < 3pi/4 or > 5pi/4 -- a float32 atan2 estimate (error < 0.01) is enough.
-#ifndef FO_ATAN2_DIAMOND
-#define FO_ATAN2_DIAMOND 1
-#endif
-#ifndef FO_ATAN2_GUARD
-#define FO_ATAN2_GUARD 1   // round 6: a NaN of the float32 estimate (offsets of ~1e-40 m: both casts flush to zero) sends the sample to the float64 route
-#endif
 __device__ __forceinline__ float fo_atan2_crude(float y, float x) {
-#if FO_ATAN2_DIAMOND
-  // Round 5: the "diamond angle" -- pi/2 (1 - x / (|x| + |y|)) with the sign of y: monotonic in the true angle, exact on the
+  // The "diamond angle" -- pi/2 (1 - x / (|x| + |y|)) with the sign of y: monotonic in the true angle, exact on the
   // axes and the diagonals, 0.071 rad off at worst (the decision it feeds has pi/4 of room, see above).  No comparison, no
-  // select: the three v_cmp + v_cndmask pairs of the octant form each held the SIMD for ten cycles beyond their own issue.
+  // select: the three v_cmp + v_cndmask pairs of an octant form each hold the SIMD for ten cycles beyond their own issue.
   // (x = y = 0 does not get here: the caller puts dx = 1 for coincident centres.  Offsets that are nonzero in float64 but vanish
   // -- or overflow, or are denormal -- as float32 give 0 * inf = NaN or +-inf here, never a value in [-pi, pi]: the callers hand
-  // such a sample to the reference's own float64 route, FO_ATAN2_GUARD.)
+  // such a sample to the reference's own float64 route, see the test |estimate| <= 4 in pass 1.)
   const float q = x * __builtin_amdgcn_rcpf(fabsf(x) + fabsf(y));
   return copysignf(fmaf(q, -1.57079633f, 1.57079633f), y);
-#else
-  const float ax = fabsf(x), ay = fabsf(y);
-  const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-  const float a = mx > 0.0f ? mn * __builtin_amdgcn_rcpf(mx) : 0.0f;
-  float r = a * (0.78539816f + 0.273f * (1.0f - a));
-  if (ay > ax) r = 1.57079633f - r;
-  if (x < 0.0f) r = 3.14159265f - r;
-  return copysignf(r, y);
-#endif
 }
 
 // coefficient of the class: 0 (front), side, rear.  (dx, dy): from the vehicle whose occupants are rated to the other
@@ -744,18 +676,9 @@ __global__ __launch_bounds__(TILE *WAVES) void fo_sweep_generic_kernel(const Swe
 #ifndef FO_TRACE
 #define FO_TRACE 0
 #endif
-#ifndef FO_DYN
-#define FO_DYN 0     // 1: the waves of a workgroup draw the chunk's agents one by one from an LDS counter (tuning builds)
-#endif
-#ifndef FO_BOX_UNROLL
-#define FO_BOX_UNROLL 1   // 0: tuning builds -- the three boxes of a mean one after the other outside the horizon-split form
-#endif
-#ifndef FO_POOL
-#define FO_POOL 1    // in-gate samples pooled over the workgroup's four waves at the end of every pass 1 (0: tuning builds -- every wave evaluates its own, inline)
-#endif
 #ifndef FO_X
-#define FO_X 0       // timing experiments only (tools/build_variant.sh x1 -DFO_X=1 ...): 1 no pass 2, 2 no probe, 4 no harm
-#endif               // geometry in pass 1, 8 pass 2 without its arithmetic, 32 no DCE in pass 1, 64 no gate, 128 no second (correlated) body -- WRONG results
+#define FO_X 0       // timing experiments only (-DFO_X=8: pass 2 without its arithmetic -- WRONG results).  The last bit of a family
+#endif               // of such switches: with its three tests folded away the product's device code changes, so it stays
 enum { HM_LR4S = 0, HM_DVMAX = 1, HM_GENERIC = 2 };   // pass-2 bodies by harm model (see dvmax_mode in the kernel)
 constexpr int TC = FO_TC;
 constexpr int DVR = TC + 1;          // rows of the per-wave ring of relative speeds: samples t0-1 .. t1-1 are live at once
@@ -787,9 +710,6 @@ __device__ __forceinline__ double fo_vmin_neg(double a, double b) {   // min(a, 
 // significant bits, so k * hi is exact for |k| < 2^10 and the dropped tail costs |k| * 2.1e-16 (< 1e-12 relative over
 // the arguments the logistic models produce, z in [-5e3, 6]; a logistic value moves by a quarter of that).  Few distinct
 // float64 constants on purpose: every one of them occupies an SGPR pair for the whole loop.
-#ifndef FO_EXP_EARLY_SCALE
-#define FO_EXP_EARLY_SCALE 1
-#endif
 template <bool CLAMP = true, int DEG = 3>
 __device__ __forceinline__ double fo_exp_tab(const double *__restrict__ tab2, double z) {
   if (CLAMP) z = fmin(fmax(z, -700.0), 700.0);  // CLAMP = false: the caller bounds the argument
@@ -807,17 +727,12 @@ __device__ __forceinline__ double fo_exp_tab(const double *__restrict__ tab2, do
     p = fma(r, 0.5, 1.0);   // degree 2: remainder r^3/6 < 4.2e-10 relative (a logistic value moves by a quarter of that)
   }
   p = fma(p, r, 1.0);
-#if FO_EXP_EARLY_SCALE
   return ldexp(tv, k >> 8) * p;   // the scaling beside the polynomial, not behind it (exact either way)
-#else
-  return ldexp(tv * p, k >> 8);
-#endif
 }
 // 1 + exp(z), the denominator of the logistic models: the table entry is scaled while the polynomial is evaluated, and
 // the product and the 1 are one fma -- mul, ldexp, add in a row became ldexp and fma (one instruction less per logistic).
 template <bool CLAMP = true, int DEG = 3>
 __device__ __forceinline__ double fo_exp1p_tab(const double *__restrict__ tab2, double z) {
-#if FO_EXP_EARLY_SCALE
   if (CLAMP) z = fmin(fmax(z, -700.0), 700.0);
   const double MAGIC = 6755399441055744.0;
   const double tm = fma(z, 369.3299304675746, MAGIC);
@@ -834,22 +749,14 @@ __device__ __forceinline__ double fo_exp1p_tab(const double *__restrict__ tab2, 
   }
   p = fma(p, r, 1.0);
   return fma(tv, p, 1.0);
-#else
-  return 1.0 + fo_exp_tab<CLAMP, DEG>(tab2, z);
-#endif
 }
 
 // 1 / (1 + exp(nz)); v_rcp_f64 (measured ~3e-8 relative) + one Newton step (1.6e-14 against the oracle)
-#ifndef FO_RCP_NR
-#define FO_RCP_NR 1
-#endif
 template <bool CLAMP = true, int DEG = 3>
 __device__ __forceinline__ double fo_logistic_neg(const double *__restrict__ tab2, double nz) {
   const double d = fo_exp1p_tab<CLAMP, DEG>(tab2, nz);
-  double y = __builtin_amdgcn_rcp(d);
-#pragma unroll
-  for (int i = 0; i < FO_RCP_NR; ++i) y = fma(fma(-d, y, 1.0), y, y);
-  return y;
+  const double y = __builtin_amdgcn_rcp(d);
+  return fma(fma(-d, y, 1.0), y, y);
 }
 
 // (Round 5, measured and dropped: both logistic values of a sample through ONE reciprocal -- y = 1/(d1 d2), s1 = y d2,
@@ -957,15 +864,13 @@ __device__ __forceinline__ cip_t fo_const(const int32_t *p) { return (cip_t)(uns
 // CORR: the agent set holds a covariance with correlation (status[1] of fo_prep_agents_kernel): in-gate samples then
 // add the correlation integral to their box probabilities (fo_corr_corners).  The kernel below carries both bodies and picks one at
 // its start, so that the usual diagonal case keeps the registers and the code it had.
-template <bool PAIR, int LISTS, bool ALLM, bool SPLIT, bool CORR, int TC_>
+template <bool PAIR, int LISTS, bool ALLM, bool SPLIT, bool CORR>
 __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const double2 *__restrict__ erf_tab,
                                                     const double *__restrict__ exp_tab, const double *__restrict__ zc_tab,
                                                     double *__restrict__ hk_all, double *__restrict__ cpbuf_all,
-                                                    unsigned short *__restrict__ queue_all, int *__restrict__ next_agent,
+                                                    unsigned short *__restrict__ queue_all, int *__restrict__ /* next_agent, see the kernel */,
                                                     int *__restrict__ pool_i, double *__restrict__ pool_hd) {
-  constexpr int TC = TC_, DVR = TC + 1, WROWS = TC + DVR;   // this instantiation's chunk length (see fo_sweep_queue_kernel)
-  constexpr bool POOL = FO_POOL != 0 && SPLIT;            // (measured: lock step costs the full grid 9 %, see pool_round)
-  constexpr int QCAPX = POOL ? TILE * TC : QCAP;            // queue entries per wave: a chunk's worth with the pool
+  constexpr int QCAPX = SPLIT ? TILE * TC : QCAP;           // queue entries per wave: a chunk's worth with the pool (pool_round)
   static_assert(!SPLIT || WROWS >= 10, "the horizon-split fold parks ten values per lane in the wave's rows");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1025,10 +930,9 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
 #pragma unroll 1
       for (int jm = 0; jm < 3; ++jm) {
         double cx = qx - BX, cy = qy - BY;                      // b = -1
-        // the three boxes of a mean side by side (twelve table reads in flight; round 4 kept that to the horizon-split form,
-        // whose heavy waves are bound by the latency of this loop -- with the shorter erf step the registers are there in
-        // every form: 0.514 -> 0.508 ms on the headline; all nine boxes in a row: 0.520)
-#pragma unroll (FO_BOX_UNROLL || (SPLIT && !PAIR) ? 3 : 1)
+        // the three boxes of a mean side by side (twelve table reads in flight; with the three-term erf step the registers
+        // are there in every form: 0.514 -> 0.508 ms on the headline; all nine boxes in a row: 0.520)
+#pragma unroll 3
         for (int b = 0; b < 3; ++b) {
           const double fx = fo_erf_fast128(erf_tab, cx + ox) - fo_erf_fast128(erf_tab, cx - ox);
           const double fy = fo_erf_fast128(erf_tab, cy + oy) - fo_erf_fast128(erf_tab, cy - oy);
@@ -1088,7 +992,8 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       }
     }
   };
-  // Workgroup-wide pool (POOL).  The gate work is the one part of the sweep that is NOT spread evenly: on the bench batch 56 of
+  // Workgroup-wide pool (horizon-split form only: on the full grid, whose four waves hold four different agents, the lock step
+  // of two barriers per chunk costs 9 %).  The gate work is the one part of the sweep that is NOT spread evenly: on the bench batch 56 of
   // the 256 agents have any sample inside the 5 m gate and 26 of them hold 84 % of the 1.4 million in-gate samples -- the wave
   // that holds such an agent evaluates up to seventeen batches of 36 x 64 erf for it while its three siblings have none, and
   // the workgroup lives as long as that wave (tools/sweep_stats.py; the model in DESIGN.md section 3.1 puts 5-20 % of the
@@ -1099,7 +1004,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
   // probabilities into the owner's rows.  A second barrier, then pass 2 as before.  Fuller batches come with it (one
   // remainder per workgroup and chunk instead of four).
   auto pool_round = [&](int qn_, int k_, double hd_, int gb_) {
-    static_assert(!POOL || QWAVES == 4, "the pool's prefix over the waves' queue lengths is written for four waves");
+    static_assert(!SPLIT || QWAVES == 4, "the pool's prefix over the waves' queue lengths is written for four waves");
     if (lane == 0) { pool_i[wave] = qn_; pool_i[QWAVES + wave] = k_; pool_i[2 * QWAVES + wave] = gb_; pool_hd[wave] = hd_; }
     __syncthreads();
     const int n0 = __builtin_amdgcn_readfirstlane(pool_i[0]), n1 = __builtin_amdgcn_readfirstlane(pool_i[1]);
@@ -1125,28 +1030,13 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
   // the samples this wave owns: everything, or time chunk `wave` of the agent the workgroup shares
   const int seg0 = SPLIT ? wave * TC : 0, seg1 = SPLIT ? min(seg0 + TC, a.T) : a.T;
   const int gfirst_ = max(seg0 - 1, 0);  // first harm / cp sample this wave evaluates for an agent
-  constexpr bool DYN = FO_DYN && !SPLIT && !POOL;
-  // POOL: the rounds a wave without an agent in this slot still takes part in (the barriers are the workgroup's)
-  auto dead_rounds = [&]() {
-    for (int t0 = seg0; t0 < seg1; t0 += TC) pool_round(0, 0, 0.0, 0);
-  };
-  const int kbase = k0 - wave * apw_, kcount = apw_ * QWAVES;   // the chunk's agents [kbase, kbase + kcount)
-  for (int kk = 0;; ++kk) {
+  for (int kk = 0;; ++kk) {   // (written as `kk < apw_` in the loop header the product's device code changes)
     int k;
-    if (DYN) {   // whichever wave is free takes the chunk's next agent (ascending within a wave)
-      int t_ = 0;
-      if (lane == 0) t_ = atomicAdd(next_agent, 1);
-      t_ = __builtin_amdgcn_readfirstlane(t_);
-      if (t_ >= kcount) break;
-      k = kbase + t_;
-    } else {
+    {
       if (kk >= apw_) break;
       k = k0 + kk;
     }
-    if (k >= A) {
-      if (POOL && !SPLIT) { dead_rounds(); continue; }   // (the other waves' slots may be in use)
-      break;
-    }
+    if (k >= A) break;
     const cdp_t G = fo_const(a.atab) + (size_t)k * a.Ta * NAF;
     const cdp_t C = fo_const(a.acst) + (size_t)k * NAC;
     const double hlB = C[0], hwB = C[1], hdev = C[2], Rsum = C[8];
@@ -1195,7 +1085,6 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           else fo_store_lists<false>(a.lists, ls, ((size_t)k * Tm1 + t) * M + m, NAN, NAN, NAN, NAN, NAN);
         }
       }
-      if (POOL && !SPLIT) dead_rounds();
       continue;
     }
 
@@ -1211,7 +1100,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     // win the tie on t).
     double dce = INFINITY, thr2 = INFINITY, thrR2 = INFINITY;
     int tdce = 0;
-    if (do_dce && !(ablate & 1) && !(FO_X & 2) && seg0 < min(L, seg1)) {
+    if (do_dce && !(ablate & 1) && seg0 < min(L, seg1)) {
       const int Ld = min(L, seg1);
       double bestc = INFINITY;
       int tb = seg0;
@@ -1219,12 +1108,11 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       // Every second sample is enough for a seed (on the bench workload the exact geometry runs as rarely as with all
       // of them; stride 4 would cost a quarter more) -- and halves the loads of this phase.
       constexpr int PS = 2;
-#if FO_PROBE_PACK
-      // Round 5: the running minimum carries its sample number in the low mantissa bits (v_bfi_b32 + v_min_f64: the earlier
-      // sample wins a tie, a repeat of the last sample never does, as with the strict comparison) -- a compare and three
-      // v_cndmask_b32 on vcc per sample before, and a v_cndmask on vcc holds the SIMD for 14 cycles where an add holds it
-      // for 4 (tools/microbench/valu_rate.hip).  The probe only SEEDS the bound: the 2^-47 it moves a squared distance by
-      // cannot change a result.
+      // The running minimum carries its sample number in the low mantissa bits (v_bfi_b32 + v_min_f64: the earlier
+      // sample wins a tie, a repeat of the last sample never does, as with a strict comparison) -- instead of a compare and
+      // three v_cndmask_b32 on vcc per sample: a v_cndmask on vcc holds the SIMD for 14 cycles where an add holds it
+      // for 4 (tools/microbench/valu_rate.hip; -1.4 % of the kernel).  The probe only SEEDS the bound: the 2^-47 it moves a
+      // squared distance by cannot change a result.
       if constexpr (SPLIT) {
         asm volatile("; probe operands resident" ::"s"(sp_gx[0]), "s"(sp_gy[0]), "s"(sp_gx[1]), "s"(sp_gy[1]), "s"(sp_gx[2]),
                      "s"(sp_gy[2]), "s"(sp_gx[3]), "s"(sp_gy[3]));
@@ -1237,73 +1125,36 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
         }
         tb = seg0 + 2 * (int)(__double2loint(bestc) & 7);   // (bestc = inf -- NaN positions only: sample 0 of the segment)
       } else {
-      int slot = 0;
+        int slot = 0;
 #pragma unroll 1
-      for (int t8 = 0; seg0 + t8 * PS < Ld; t8 += 8) {
-        double vx[8], vy[8], gpx[8], gpy[8];
+        for (int t8 = 0; seg0 + t8 * PS < Ld; t8 += 8) {
+          double vx[8], vy[8], gpx[8], gpy[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int t = min(seg0 + (t8 + u) * PS, Ld - 1);
-          const fo_d2 xy = fo_ld2(tj + (size_t)t * NEF * TILE);
-          vx[u] = xy.x;
-          vy[u] = xy.y;
-          const cdp_t g = G + (size_t)t * NAF;   // eight scalar loads in flight as well (one lgkmcnt wait for all)
-          gpx[u] = g[0];
-          gpy[u] = g[1];
-        }
-        asm volatile("; probe operands resident" ::"s"(gpx[0]), "s"(gpy[0]), "s"(gpx[1]), "s"(gpy[1]), "s"(gpx[2]),
-                     "s"(gpy[2]), "s"(gpx[3]), "s"(gpy[3]), "s"(gpx[4]), "s"(gpy[4]), "s"(gpx[5]), "s"(gpy[5]),
-                     "s"(gpx[6]), "s"(gpy[6]), "s"(gpx[7]), "s"(gpy[7]));
-        double blk = INFINITY;
+          for (int u = 0; u < 8; ++u) {
+            const int t = min(seg0 + (t8 + u) * PS, Ld - 1);
+            const fo_d2 xy = fo_ld2(tj + (size_t)t * NEF * TILE);
+            vx[u] = xy.x;
+            vy[u] = xy.y;
+            const cdp_t g = G + (size_t)t * NAF;   // eight scalar loads in flight as well (one lgkmcnt wait for all)
+            gpx[u] = g[0];
+            gpy[u] = g[1];
+          }
+          asm volatile("; probe operands resident" ::"s"(gpx[0]), "s"(gpy[0]), "s"(gpx[1]), "s"(gpy[1]), "s"(gpx[2]),
+                       "s"(gpy[2]), "s"(gpx[3]), "s"(gpy[3]), "s"(gpx[4]), "s"(gpy[4]), "s"(gpx[5]), "s"(gpy[5]),
+                       "s"(gpx[6]), "s"(gpy[6]), "s"(gpx[7]), "s"(gpy[7]));
+          double blk = INFINITY;
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const double rx = gpx[u] - vx[u], ry = gpy[u] - vy[u];
-          blk = fo_vmin(blk, fo_pack_low(fma(rx, rx, ry * ry), u));
+          for (int u = 0; u < 8; ++u) {
+            const double rx = gpx[u] - vx[u], ry = gpy[u] - vy[u];
+            blk = fo_vmin(blk, fo_pack_low(fma(rx, rx, ry * ry), u));
+          }
+          // (block against block: one comparison per eight samples -- the mask in a scalar pair, not in vcc)
+          const unsigned long long lt = __builtin_amdgcn_fcmp(blk, bestc, 4 /* olt */);
+          bestc = fo_vmin(bestc, blk);
+          slot = fo_sel_b32(lt, slot, t8);
         }
-        // (block against block: one comparison per eight samples -- the mask in a scalar pair, not in vcc)
-        const unsigned long long lt = __builtin_amdgcn_fcmp(blk, bestc, 4 /* olt */);
-        bestc = fo_vmin(bestc, blk);
-        slot = fo_sel_b32(lt, slot, t8);
+        tb = min(seg0 + (slot + (int)(__double2loint(bestc) & 7)) * PS, Ld - 1);
       }
-      tb = min(seg0 + (slot + (int)(__double2loint(bestc) & 7)) * PS, Ld - 1);
-      }
-#else
-      if constexpr (SPLIT) {
-        asm volatile("; probe operands resident" ::"s"(sp_gx[0]), "s"(sp_gy[0]), "s"(sp_gx[1]), "s"(sp_gy[1]), "s"(sp_gx[2]),
-                     "s"(sp_gy[2]), "s"(sp_gx[3]), "s"(sp_gy[3]));
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int t = seg0 + 2 * u;
-          const double rx = sp_gx[u] - sp_vx[u], ry = sp_gy[u] - sp_vy[u];
-          const double c2 = rx * rx + ry * ry;
-          if (t < Ld && c2 < bestc) { bestc = c2; tb = t; }
-        }
-      } else
-#pragma unroll 1
-      for (int t8 = 0; seg0 + t8 * PS < Ld; t8 += 8) {
-        double vx[8], vy[8], gpx[8], gpy[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int t = min(seg0 + (t8 + u) * PS, Ld - 1);
-          const fo_d2 xy = fo_ld2(tj + (size_t)t * NEF * TILE);
-          vx[u] = xy.x;
-          vy[u] = xy.y;
-          const cdp_t g = G + (size_t)t * NAF;   // eight scalar loads in flight as well (one lgkmcnt wait for all)
-          gpx[u] = g[0];
-          gpy[u] = g[1];
-        }
-        asm volatile("; probe operands resident" ::"s"(gpx[0]), "s"(gpy[0]), "s"(gpx[1]), "s"(gpy[1]), "s"(gpx[2]),
-                     "s"(gpy[2]), "s"(gpx[3]), "s"(gpy[3]), "s"(gpx[4]), "s"(gpy[4]), "s"(gpx[5]), "s"(gpy[5]),
-                     "s"(gpx[6]), "s"(gpy[6]), "s"(gpx[7]), "s"(gpy[7]));
-#pragma unroll
-        for (int u = 0; u < 8; ++u) {
-          const int t = min(seg0 + (t8 + u) * PS, Ld - 1);  // repeats of the last sample cannot win (strict <)
-          const double rx = gpx[u] - vx[u], ry = gpy[u] - vy[u];
-          const double c2 = rx * rx + ry * ry;
-          if (c2 < bestc) { bestc = c2; tb = t; }
-        }
-      }
-#endif
       const double *e = tj + (size_t)tb * NEF * TILE;                   // per-lane sample: gathers
       const double *g = a.atab + ((size_t)k * a.Ta + tb) * NAF;
       const fo_d2 exy = fo_ld2(e), ecs = fo_ld2(e + EF(2));
@@ -1329,7 +1180,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     // -- agents without a harm model, speed coefficients of unusual sign.  With the lists the running maximum is kept by
     // pass 2, which walks every sample anyway; without them by pass 1, and pass 2 visits the gate rows only.  The maxima are
     // the same arithmetic in all three output modes: logistic at sqrt(max dv^2).)
-    const bool dvmax_mode = FO_DIET && prot == 0 && C[10] <= 0.0 && C[11] <= 0.0 && !(FO_X & 8);
+    const bool dvmax_mode = prot == 0 && C[10] <= 0.0 && C[11] <= 0.0 && !(FO_X & 8);
     // List stores: the three blocks (cp | harm pairs | risk pairs) from per-agent scalar bases plus two running 32-bit
     // lane offsets (element size 1x and 2x) -- no 64-bit address arithmetic per sample (fo_sweep_run sends batches whose
     // (T-1) M pair elements pass 4 GB to the generic kernel)
@@ -1359,15 +1210,12 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     //          or scalar load shares a counter with the list stores (vmcnt retires loads and stores in issue order, so
     //          a load behind five stores per iteration used to wait for their acknowledgement).
     const int gfirst = gfirst_;
-#ifndef FO_CARRY
-#define FO_CARRY 0   // 1: tuning builds -- the first ego row of a chunk is carried over pass 2 instead of re-loaded (measured: float32 lists 0.562 against 0.552, float64 lists 0.637 against 0.650: the 14 live registers cost more than the wait)
-#endif
-    // (Also measured and not kept, round 3: two register sets for the current / next rows that swap roles, the loop
+    // (Measured and not kept, round 3: two register sets for the current / next rows that swap roles, the loop
     // unrolled by two, instead of one set rotated by seven v_mov_b64 and ten s_mov per sample -- 0.552 against 0.541 ms:
     // 30 spilled registers instead of 8 and a quarter more code cost more than the copies.)
-    // the ego row a chunk starts with: pass 1 of the chunk before has already fetched it (its last iteration prefetches
-    // row t1); carried over pass 2 in registers, the chunk's first loads do not queue behind that pass's list stores
-    // (vmcnt retires in issue order: a load issued after 24 stores waits for their acknowledgement)
+    // The ego row a chunk starts with is re-loaded at the chunk's start although pass 1 of the chunk before has already
+    // fetched it (its last iteration prefetches row t1): carried over pass 2, the 14 live registers cost more than the
+    // wait of the loads behind that pass's list stores (float32 lists 0.562 against 0.552 ms).
     fo_d2 nxy, ncs, nvv;
     double nth_ = 0.0;
     for (int t0 = seg0; t0 < seg1; t0 += TC) {
@@ -1396,7 +1244,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       if (!(SPLIT && t0 > 0) && t0 > seg0) dvw[lane] = dvw[TC * TILE + lane];
       // the sample ranges of the DCE and of the gate as one unsigned comparison each (scalar instructions are not free:
       // DESIGN.md section 3.1): DCE on [t0, L), gate on [max(t0, 1), L)
-      const bool dce_on = do_dce && !(ablate & 1) && !(FO_X & 32), gate_on = do_cp && !(ablate & 2) && !(FO_X & 64);
+      const bool dce_on = do_dce && !(ablate & 1), gate_on = do_cp && !(ablate & 2);
       const int rng_n = (dce_on || gate_on) ? max(L - t0, 0) : 0;
       const double gate_far2c = gate_on ? gate_far2 : -1.0;   // (no distance is below -1: the test never passes)
       // sample 0 has no gate (there is no sample -1): the radius of the chunk's first sample is -1 there, the loop sets
@@ -1404,14 +1252,12 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       double gate_far2t = (tl == 0) ? -1.0 : gate_far2c;
       if (!dce_on) thrR2 = -1.0;
       const bool geo = do_hr && !(ablate & 4);
-      if (!FO_CARRY || SPLIT || t0 == seg0) {
-        const double *e0_ = tj + (size_t)tl * NEF * TILE;
-        nxy = fo_ld2(e0_); ncs = fo_ld2(e0_ + EF(2)); nvv = fo_ld2(e0_ + EF(6));
-        if (lr4s) nth_ = e0_[EF(4)];
-      }
-      // (FO_DIET: rows are addressed without clamping -- rows past an agent's length are read but never used, every use sits
+      const double *e0_ = tj + (size_t)tl * NEF * TILE;
+      nxy = fo_ld2(e0_); ncs = fo_ld2(e0_ + EF(2)); nvv = fo_ld2(e0_ + EF(6));
+      if (lr4s) nth_ = e0_[EF(4)];
+      // (rows are addressed without clamping -- rows past an agent's length are read but never used, every use sits
       // behind t < L; the tables end in spare rows, fo_sweep_set_agents / fo_sweep_run)
-      const cdp_t gr0 = G + (size_t)(FO_DIET ? tl : min(tl, L - 1)) * NAF;
+      const cdp_t gr0 = G + (size_t)tl * NAF;
       double px = gr0[0], py = gr0[1], npx = px, npy = py;
       // Only the mean of the next row is fetched a sample ahead (the first thing a sample needs); heading and velocity
       // are re-loaded IN PLACE right after their last use in a sample -- no second register set, no copies
@@ -1514,7 +1360,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
               }
               wgate |= 1u << row;
               qn += __popcll(bal);
-              if (!POOL && qn >= 64) {
+              if (!SPLIT && qn >= 64) {
                 process(64);
                 const int rest = qn - 64;
                 unsigned short tmp = 0;
@@ -1540,7 +1386,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           const cdp_t g2 = (cdp_t)((const __attribute__((address_space(4))) char *)G + gb);
           pvx = g2[8]; pvy = g2[9];
         }
-        if (geo && t < Lh && !(FO_X & 4)) {
+        if (geo && t < Lh) {
           // squared (<= 1e8: the prep kernels cap the speeds at 5e3 m/s); pass 2 takes the root where it needs the speed
           const double dv2_ = fo_sq_sum_pos(dvx, dvy);
           dvw[(t - gbase) * TILE + lane] = dv2_;
@@ -1548,21 +1394,14 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           if (lr4s) {
             // the impact angles only enter the LR4S model, and only through their class (front / side / rear)
             double ddx = px - ex, ddy = py - ey;
-#if FO_ATAN2_DIAMOND
             // atan2(0, 0) = 0: dx = 1 for coincident centres -- |dx| + |dy| == 0, and only the high word of dx has to change
             ddx = __hiloint2double(fabs(ddx) + fabs(ddy) == 0.0 ? 0x3ff00000 : __double2hiint(ddx), __double2loint(ddx));
-#else
-            if (ddx == 0.0 && ddy == 0.0) ddx = 1.0;  // atan2(0, 0) = 0
-#endif
             const float relc = fo_atan2_crude((float)ddy, (float)ddx);
             bool be_, bo_;
             const unsigned ce = fo_lr4s_class(ddx, ddy, ec, es, relc, 0.0f, (float)eth, false, be_);
             const unsigned co = fo_lr4s_class(ddx, ddy, pc, ps, relc, 3.14159265f, (float)pyaw, true, bo_);
-#if FO_ATAN2_GUARD
+            // (a NaN or +-inf of the float32 estimate -- offsets of ~1e-40 m: both casts flush to zero -- goes the same way)
             if (__ballot(be_ || bo_ || !(fabsf(relc) <= 4.0f))) wgate |= 0x10000u << (t & 15);   // re-rated after the loop (rare; see there)
-#else
-            if (__ballot(be_ || bo_)) wgate |= 0x10000u << (t & 15);   // re-rated after the loop (rare; see there)
-#endif
             const int sh = (t & 15) * 2;
             cls_e = (cls_e & ~(3u << sh)) | (ce << sh);
             cls_o = (cls_o & ~(3u << sh)) | (co << sh);
@@ -1582,7 +1421,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
         }
         gate_far2t = gate_far2c;
       }
-      if (POOL) pool_round(qn, k, hdev, gbase);
+      if (SPLIT) pool_round(qn, k, hdev, gbase);
       else if (qn > 0) process(qn);
       wgate = __builtin_amdgcn_readfirstlane(wgate);  // uniform by construction; says so to the register allocator
       const unsigned wband = wgate >> 16;
@@ -1598,15 +1437,11 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           const cdp_t g0 = G + (size_t)min(t, L - 1) * NAF;
           double ddx = g0[0] - xy.x, ddy = g0[1] - xy.y;
           if (ddx == 0.0 && ddy == 0.0) ddx = 1.0;
-#if FO_ATAN2_GUARD
           // (an offset whose float32 casts under- or overflow -- the estimate above was NaN and "far" read false: both classes
           // by the float64 route)
           const float crude_ = fo_atan2_crude((float)ddy, (float)ddx);
           const bool nf_ = !(fabsf(crude_) <= 4.0f);   // NaN (0 * inf) or +-inf (a float32 denormal times the reciprocal of one)
           const bool be_ = nf_ || fo_lr4s_on_boundary(ddx, ddy, cs.x, cs.y), bo_ = nf_ || fo_lr4s_on_boundary(ddx, ddy, g0[2], g0[3]);
-#else
-          const bool be_ = fo_lr4s_on_boundary(ddx, ddy, cs.x, cs.y), bo_ = fo_lr4s_on_boundary(ddx, ddy, g0[2], g0[3]);
-#endif
           if (be_ || bo_) {
             const unsigned both = fo_lr4s_classes_ref(ddx, ddy, th0, g0[4]);
             const int sh = slot * 2;
@@ -1620,7 +1455,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       // ---------------------------------------------------------------- pass 2: harm, risk, maxima, lists
       // of the gate samples g in [max(t0-1, 0), t1-1) -- harm index g, cp index g (Q6)
       const int g0s = max(gbase, 0), g1s = t1 - 1;
-      if ((do_cp || do_hr) && g0s < g1s && !(FO_X & 1)) {
+      if ((do_cp || do_hr) && g0s < g1s) {
         // one instantiation per harm model: the LR4S path (impact classes -> logistic offsets) and the pedestrian /
         // LR1S path keep separate register and constant sets
         auto pass2 = [&](auto hm_tag) {
@@ -1671,7 +1506,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           } else {
           auto row_step = [&](const int t, auto fast_tag) {
             // FASTROW (compile time): the row lies inside the harm length and no lane of the wave is inside the gate -- the
-            // two mask tests, the branch on them and the long way's code are not in this copy of the body (FO_P2_RUNS)
+            // two mask tests, the branch on them and the long way's code are not in this copy of the body
             constexpr bool FASTROW = decltype(fast_tag)::value;
             const int row = t - gbase;
             const double dv = dvn, ze = zen, zo = zon;
@@ -1768,31 +1603,26 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
             lo1 += (unsigned)M * LE;
             lo2 += (unsigned)M * (2u * LE);
           };
-          // Round 5: two rows per trip -- the values read ahead for row t+1 (relative speed, LR4S offsets) change registers
-          // instead of being copied into row t's at the end of every trip (one to three v_mov_b64 per list row)
           int t = g0s;
-          // Round 5: runs of rows that take the short way (97 % of the rows of the bench workload, usually the whole chunk) in
-          // a loop of their own: per row two scalar shifts, two ands, two compares and two branches less -- 71 -> 53
-          // instructions per row of the two-coefficient models.  Measured per list format, same flags on both sides: float32
+          // Float32 arithmetic only: runs of rows that take the short way (97 % of the rows of the bench workload, usually the
+          // whole chunk) in a loop of their own: per row two scalar shifts, two ands, two compares and two branches less -- 71 ->
+          // 53 instructions per row of the two-coefficient models.  Measured per list format, same flags on both sides: float32
           // arithmetic -1.9 % (0.4538 / 0.4564 -> 0.4463 / 0.4456 ms), float64 arithmetic with float32 stores +1.4 %, float64
-          // lists +5 % (23 / 48 spilled VGPRs instead of 19 / 17, and those two are not bound by pass 2's issue): on for the
-          // first only.
-          if constexpr (FO_P2_RUNS != 0 && LISTS == LST_F32) {
-          const unsigned fastrows = hvrows & ~slow;
-          while (t < g1s) {
-            const int row = t - gbase;
-            const int run = min(__builtin_ctz(~(fastrows >> row) | 0x80000000u), g1s - t);
-            if (run > 0) {
-              const int te = t + run;
-              for (; t < te; ++t) row_step(t, std::true_type{});
-            } else {
-              row_step(t, std::false_type{});
-              ++t;
+          // lists +5 % (23 / 48 spilled VGPRs instead of 19 / 17, and those two are not bound by pass 2's issue).
+          if constexpr (LISTS == LST_F32) {
+            const unsigned fastrows = hvrows & ~slow;
+            while (t < g1s) {
+              const int row = t - gbase;
+              const int run = min(__builtin_ctz(~(fastrows >> row) | 0x80000000u), g1s - t);
+              if (run > 0) {
+                const int te = t + run;
+                for (; t < te; ++t) row_step(t, std::true_type{});
+              } else {
+                row_step(t, std::false_type{});
+                ++t;
+              }
             }
           }
-          }
-          if (FO_P2_UNROLL == 2)
-            for (; t + 1 < g1s; t += 2) { row_step(t, std::false_type{}); row_step(t + 1, std::false_type{}); }
           for (; t < g1s; ++t) row_step(t, std::false_type{});
           }
         };
@@ -1803,7 +1633,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       SW_STAMP(2);
     }
     // (horizon-split form, a wave whose segment lies beyond the horizon: it still takes part in the agent's pool round)
-    if (POOL && SPLIT && !(seg0 < seg1)) pool_round(0, 0, 0.0, 0);
+    if (SPLIT && !(seg0 < seg1)) pool_round(0, 0, 0.0, 0);
     if (dvmax_mode) {
       if (nze_min < INFINITY) {   // nze_min = -(largest squared relative speed)
         const double dvm = fo_sqrt(-nze_min);
@@ -1857,7 +1687,6 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       pf[FO_PF_DCE * ps_] = do_dce ? dce_m : NAN;
       pf[FO_PF_TTC * ps_] = do_ttc ? ttc : NAN;
       pf[FO_PF_TTCE * ps_] = do_ttce ? ttce : NAN;
-#if FO_EPI_SEL
       if (hr_valid) {   // (wave-uniform)
         // a collision probability of this pair was NaN (see pass 2): NaN where the probability enters -- the high word alone
         const unsigned long long bad = __builtin_amdgcn_fcmp(max_er, max_er, 8 /* uno */);
@@ -1871,15 +1700,6 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
         pf[FO_PF_MAX_EGO_RISK * ps_] = NAN; pf[FO_PF_MAX_OBST_RISK * ps_] = NAN; pf[FO_PF_HARM_WITH_CP * ps_] = NAN;
         pf[FO_PF_MAX_EGO_HARM * ps_] = NAN; pf[FO_PF_MAX_OBST_HARM * ps_] = NAN; pf[FO_PF_MAX_CP * ps_] = NAN;
       }
-#else
-      const bool cp_ok = hr_valid && max_er == max_er;   // false: a collision probability of this pair was NaN (see pass 2)
-      pf[FO_PF_MAX_EGO_RISK * ps_] = hr_valid ? max_er : NAN;
-      pf[FO_PF_MAX_OBST_RISK * ps_] = cp_ok ? max_or : NAN;
-      pf[FO_PF_HARM_WITH_CP * ps_] = cp_ok ? hwc : NAN;
-      pf[FO_PF_MAX_EGO_HARM * ps_] = hr_valid ? max_eh : NAN;
-      pf[FO_PF_MAX_OBST_HARM * ps_] = hr_valid ? max_oh : NAN;
-      pf[FO_PF_MAX_CP * ps_] = cp_ok ? max_cp : NAN;
-#endif
       pf[FO_PF_BE_DECEL * ps_] = NAN;
       pf[FO_PF_BE_BTN * ps_] = NAN;
       pf[FO_PF_SPARE * ps_] = NAN;
@@ -1889,11 +1709,11 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       pi[FO_PI_CP_ARGMAX * ps_] = hr_valid ? idx_cp : 0;
       pi[FO_PI_HR_VALID * ps_] = hr_valid ? 1 : 0;
     }
-#if FO_EPI_SEL
-    // Round 5: the running extrema over the wave's agents as v_min / v_max plus ONE select of the index on a scalar-pair mask
+    // The running extrema over the wave's agents as v_min / v_max plus ONE select of the index on a scalar-pair mask
     // (a compare followed by three v_cndmask on vcc holds the SIMD for ~25 cycles beyond the instructions' own issue --
-    // tools/microbench/valu_rate.hip, "v_cmp_f64 + v_cndmask"); fmax() with its canonicalising v_max x, x in front
-    // replaced by the bare instruction (operands are results of arithmetic, never signalling NaNs).
+    // tools/microbench/valu_rate.hip, "v_cmp_f64 + v_cndmask"; as plain C this epilogue costs the headline kernel +1 %); the
+    // bare instruction instead of fmax() with its canonicalising v_max x, x in front (operands are results of arithmetic,
+    // never signalling NaNs).
     if (do_dce) {
       const unsigned long long lt = __builtin_amdgcn_fcmp(dce_m, w_min_dce, 4 /* olt */);
       w_min_dce = fo_vmin(w_min_dce, dce_m);
@@ -1916,22 +1736,6 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       w_max_cp = fo_vmax(w_max_cp, max_cp);
       w_max_hwc = fo_vmax(w_max_hwc, hwc);
     }
-#else
-    if (do_dce) {
-      if (dce_m < w_min_dce) { w_min_dce = dce_m; w_arg_dce = k; }
-      if (dce_m < a.thr_dce) w_dce_flag = true;
-      if (do_ttc && dce == 0.0 && tdce < w_min_tttc) { w_min_tttc = tdce; w_arg_ttc = k; }
-      if (do_ttce) w_min_tttce = min(w_min_tttce, tdce);
-    }
-    if (hr_valid) {
-      w_max_er = fmax(w_max_er, max_er);
-      if (max_or > w_max_or) { w_max_or = max_or; w_arg_or = k; }
-      w_max_eh = fmax(w_max_eh, max_eh);
-      w_max_oh = fmax(w_max_oh, max_oh);
-      w_max_cp = fmax(w_max_cp, max_cp);
-      w_max_hwc = fmax(w_max_hwc, hwc);
-    }
-#endif
   }
 
   // ---------------- combine the waves of the workgroup (ascending agent order); scratch aliases the cp buffers
@@ -1955,14 +1759,13 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     if (!SPLIT)
     for (int w = 0; w < QWAVES - 1; ++w) {
       const double *rp = red + (size_t)w * NPS * TILE + lane;
-      // (ties keep the smaller agent index: with FO_DYN the waves' agents interleave, without it wave order = agent order
-      // and the index test never fires)
+      // (ties keep the value in hand: wave order = agent order, so that is the smaller agent index)
       const int ad_ = (int)rp[PS_ARG_DCE * TILE], at_ = (int)rp[PS_ARG_TTC * TILE], ao_ = (int)rp[PS_ARG_OR * TILE];
-      if (rp[PS_MIN_DCE * TILE] < w_min_dce || (DYN && rp[PS_MIN_DCE * TILE] == w_min_dce && ad_ >= 0 && (w_arg_dce < 0 || ad_ < w_arg_dce))) { w_min_dce = rp[PS_MIN_DCE * TILE]; w_arg_dce = ad_; }
-      if (rp[PS_MIN_TTC * TILE] < w_min_ttc || (DYN && rp[PS_MIN_TTC * TILE] == w_min_ttc && at_ >= 0 && (w_arg_ttc < 0 || at_ < w_arg_ttc))) { w_min_ttc = rp[PS_MIN_TTC * TILE]; w_arg_ttc = at_; }
+      if (rp[PS_MIN_DCE * TILE] < w_min_dce) { w_min_dce = rp[PS_MIN_DCE * TILE]; w_arg_dce = ad_; }
+      if (rp[PS_MIN_TTC * TILE] < w_min_ttc) { w_min_ttc = rp[PS_MIN_TTC * TILE]; w_arg_ttc = at_; }
       w_min_ttce = fmin(w_min_ttce, rp[PS_MIN_TTCE * TILE]);
       w_max_er = fmax(w_max_er, rp[PS_MAX_ER * TILE]);
-      if (rp[PS_MAX_OR * TILE] > w_max_or || (DYN && rp[PS_MAX_OR * TILE] == w_max_or && ao_ >= 0 && (w_arg_or < 0 || ao_ < w_arg_or))) { w_max_or = rp[PS_MAX_OR * TILE]; w_arg_or = ao_; }
+      if (rp[PS_MAX_OR * TILE] > w_max_or) { w_max_or = rp[PS_MAX_OR * TILE]; w_arg_or = ao_; }
       w_max_eh = fmax(w_max_eh, rp[PS_MAX_EH * TILE]);
       w_max_oh = fmax(w_max_oh, rp[PS_MAX_OH * TILE]);
       w_max_cp = fmax(w_max_cp, rp[PS_MAX_CP * TILE]);
@@ -1979,29 +1782,13 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
   }
 }
 
-// Chunk length and occupancy by output mode: with the per-sample lists the hot loops need 164 VGPRs (three waves per
-// SIMD, chunks of eight); without them -- and not in the horizon-split form, whose four waves must cover T <= 32 with
-// one chunk each -- chunks of four fit 128 VGPRs and 37 KB of LDS: four waves per SIMD (measured -5 % on those modes).
-#ifndef FO_WIDE_LISTS
-#define FO_WIDE_LISTS 0   // 1: tuning builds -- the full-output instantiation in the four-wave shape as well
-#endif
-#ifndef FO_WIDE_NONE
-#define FO_WIDE_NONE 0    // 1: the instantiations without lists in the four-wave shape (round 2 and early round 3: faster then; since the scalar diet of round 3 the three-wave shape wins, reduced outputs 0.417 against 0.438 ms)
-#endif
-#ifndef FO_WIDE_F32
-#define FO_WIDE_F32 0     // 1: the float32-list instantiation in the four-wave shape
-#endif
-template <int LISTS, bool SPLIT>
-struct SweepShape {
-  static constexpr bool wide = ((LISTS == LST_NONE && FO_WIDE_NONE) || FO_WIDE_LISTS || (LISTS == LST_F32 && FO_WIDE_F32)) && !SPLIT &&
-                               FO_MINW == 3 && FO_TC == 8;   // tuning builds override both macros
-  static constexpr int tc = wide ? 4 : FO_TC, minw = wide ? 4 : FO_MINW;
-};
+// Every output mode runs in one shape: chunks of FO_TC = 8 samples, FO_MINW = 3 waves per SIMD (the hot loops of the modes
+// with per-sample lists need 164 VGPRs).  The four-wave shape -- chunks of four, 128 VGPRs, 37 KB of LDS -- was faster for
+// the modes without lists until the scalar-instruction diet of round 3; since then it loses everywhere: reduced outputs 0.438
+// against 0.417 ms, float32 lists 0.604 against 0.590, float64 lists 0.701-0.716 against 0.685.
 template <bool PAIR, int LISTS, bool ALLM, bool SPLIT = false>
-__global__ __launch_bounds__(TILE *QWAVES)
-__attribute__((amdgpu_waves_per_eu(SweepShape<LISTS, SPLIT>::minw, SweepShape<LISTS, SPLIT>::minw)))
+__global__ __launch_bounds__(TILE *QWAVES) __attribute__((amdgpu_waves_per_eu(FO_MINW, FO_MINW)))
 void fo_sweep_queue_kernel(const SweepArgs a) {
-  constexpr int TCK = SweepShape<LISTS, SPLIT>::tc, WROWS = TCK + TCK + 1;
   __shared__ double2 erf_tab[ERF_N];
   __shared__ double exp_tab[EXP_N];
   __shared__ double zc_tab[4];                      // LR4S logistic offsets by impact class: front, side, rear
@@ -2009,10 +1796,10 @@ void fo_sweep_queue_kernel(const SweepArgs a) {
   constexpr int BUFROWS = QWAVES * WROWS > (QWAVES - 1) * NPS ? QWAVES * WROWS : (QWAVES - 1) * NPS;
   __shared__ double cpbuf_all[BUFROWS * TILE];  // per wave: TC rows of collision probabilities, DVR rows of
                                                        // relative speeds; also the cross-wave reduction scratch
-  __shared__ unsigned short queue_all[QWAVES * (FO_POOL && SPLIT ? TILE * TCK : QCAP)];   // per wave: in-gate samples (lane | row << 6)
-  __shared__ int pool_i[3 * QWAVES];       // FO_POOL, per wave: queue length, agent, gate sample of buffer row 0
-  __shared__ double pool_hd[QWAVES];       //          half the agent's inflated length
-  __shared__ int next_agent;   // FO_DYN: agents of the chunk handed out so far
+  __shared__ unsigned short queue_all[QWAVES * (SPLIT ? TILE * TC : QCAP)];   // per wave: in-gate samples (lane | row << 6)
+  __shared__ int pool_i[3 * QWAVES];       // pool_round, per wave: queue length, agent, gate sample of buffer row 0
+  __shared__ double pool_hd[QWAVES];       //             half the agent's inflated length
+  __shared__ int next_agent;   // unused; without it and its store the product's device code changes
   if (threadIdx.x == 0) next_agent = 0;
   {
     // The two tables into LDS.  All of a thread's loads are issued before the first store (written as a loop the copy
@@ -2031,8 +1818,7 @@ void fo_sweep_queue_kernel(const SweepArgs a) {
   }
   if (threadIdx.x < 4)
     zc_tab[threadIdx.x] = -a.hc.lr4s_const - (threadIdx.x == 0 ? 0.0 : threadIdx.x == 1 ? a.hc.lr4s_side : a.hc.lr4s_rear);
-  // (FO_X & 128: register / timing experiments without the second body -- WRONG results for correlated covariances)
-  const bool corr = !(FO_X & 128) && a.status[1] == a.gen;   // scalar load; written by fo_prep_agents_kernel on this stream
+  const bool corr = a.status[1] == a.gen;   // scalar load; written by fo_prep_agents_kernel on this stream
 #if FO_TRACE
   if (a.trace && threadIdx.x == 0) {
     unsigned hw, xcc;
@@ -2047,9 +1833,9 @@ void fo_sweep_queue_kernel(const SweepArgs a) {
   if (a.trace && threadIdx.x == 0) a.trace[4 * (size_t)blockIdx.x + 3] = wall_clock64();   // tables in LDS
 #endif
   if (__builtin_expect(!corr, 1))
-    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, false, TCK>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
+    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, false>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
   else
-    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, true, TCK>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
+    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, true>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
 #if FO_TRACE
   if (a.trace && threadIdx.x == 0) a.trace[4 * (size_t)blockIdx.x + 1] = wall_clock64();
 #endif
@@ -2249,10 +2035,8 @@ inline int round_up(int v, int q) { return (v + q - 1) / q * q; }
 constexpr int AGENT_PAD_ROWS = 256;   // spare rows behind the agent table (unclamped row addresses of the queue kernel)
 
 // one instantiation of the queue kernel per output mode: cost vectors only / + pair scalars / + float64 or float32 lists
-// false: no instantiation for this combination (fo_sweep_run sends those to the generic kernel BEFORE it plans the grid; a
-// change of its conditions must not end in a launch that silently writes nothing)
 template <bool ALLM, bool SPLIT>
-bool launch_queue(int lst, bool pair, dim3 g, dim3 b, hipStream_t s, const SweepArgs &a) {
+void launch_queue(int lst, bool pair, dim3 g, dim3 b, hipStream_t s, const SweepArgs &a) {
   if (lst == LST_F64) hipLaunchKernelGGL((fo_sweep_queue_kernel<true, LST_F64, ALLM, SPLIT>), g, b, 0, s, a);
   else if (lst == LST_F32) hipLaunchKernelGGL((fo_sweep_queue_kernel<true, LST_F32, ALLM, SPLIT>), g, b, 0, s, a);
   // (round 6: the headline format has every instantiation the other list formats have -- horizon-split for small batches,
@@ -2260,7 +2044,15 @@ bool launch_queue(int lst, bool pair, dim3 g, dim3 b, hipStream_t s, const Sweep
   else if (lst == LST_F32X) hipLaunchKernelGGL((fo_sweep_queue_kernel<true, LST_F32X, ALLM, SPLIT>), g, b, 0, s, a);
   else if (pair) hipLaunchKernelGGL((fo_sweep_queue_kernel<true, LST_NONE, ALLM, SPLIT>), g, b, 0, s, a);
   else hipLaunchKernelGGL((fo_sweep_queue_kernel<false, LST_NONE, ALLM, SPLIT>), g, b, 0, s, a);
-  return true;
+}
+
+// the list format of a run as the LST_* mode of a sweep instantiation
+int lst_mode_of(const fo_ctx *ctx, const double *d_lists) {
+  return !d_lists ? LST_NONE : ctx->list_format == FO_LISTS_F32 ? LST_F32 : ctx->list_format == FO_LISTS_F32_EXACT ? LST_F32X : LST_F64;
+}
+// the batch shape an entry of fo_sweep_autotune's table was measured on
+bool tuned_for(const fo_ctx::Tuned &tu, int n_tiles, int A, int T, int lst, bool pair) {
+  return tu.n_tiles == n_tiles && tu.A == A && tu.T == T && tu.lst == lst && tu.pair == pair;
 }
 
 // agents per wave in the first phase of the (tapered) grid: long workgroups keep the per-workgroup start-up (table fill,
@@ -2440,16 +2232,14 @@ int sweep_run(fo_ctx *ctx, int M, int T, const double *d_x, const double *d_y, c
   const char *force_generic = fo_getenv(knobs, "FO_SWEEP_GENERIC");  // debug / A-B aid
   // (the queue kernel reads agent rows up to index T without clamping: horizons far beyond the predictions' take the generic kernel)
   // (the queue kernel addresses one agent's list rows by 32-bit byte offsets: (T-1) M pairs of float64 must stay under 4 GB)
-  bool use_queue = !(force_generic && force_generic[0] == '1') && (!FO_DIET || T <= Ta + AGENT_PAD_ROWS - 1 || A == 0) &&
+  bool use_queue = !(force_generic && force_generic[0] == '1') && (T <= Ta + AGENT_PAD_ROWS - 1 || A == 0) &&
                          (size_t)(T > 1 ? T - 1 : 1) * (size_t)M * 16u < ((size_t)1 << 32);
-  const int lst_mode = !d_lists ? LST_NONE : ctx->list_format == FO_LISTS_F32 ? LST_F32 : ctx->list_format == FO_LISTS_F32_EXACT ? LST_F32X : LST_F64;
+  const int lst = lst_mode_of(ctx, d_lists);
   const int wpb = use_queue ? QWAVES : WAVES;  // waves per workgroup of the kernel that will run
   int apw = pick_apw(n_tiles, A, wpb);
   // a setting fo_sweep_autotune measured for this shape on this context wins over the static choice
-  for (int i = 0; i < ctx->n_tuned; ++i) {
-    const fo_ctx::Tuned &tu = ctx->tuned[i];
-    if (tu.n_tiles == n_tiles && tu.A == A && tu.T == T && tu.lst == lst_mode && tu.pair == (d_pair_f != nullptr)) apw = tu.apw;
-  }
+  for (int i = 0; i < ctx->n_tuned; ++i)
+    if (tuned_for(ctx->tuned[i], n_tiles, A, T, lst, d_pair_f != nullptr)) apw = ctx->tuned[i].apw;
   if (ctx->force_apw > 0) apw = ctx->force_apw;   // (fo_sweep_autotune while it measures)
   if (const char *e = fo_getenv(knobs, "FO_SWEEP_APW")) { const int v = atoi(e); if (v >= 1 && v <= 64) apw = v; }  // tuning aid
   // Small batches: with one agent per wave the grid is n_tiles x A waves; below the 3 072 wave slots of the chip the
@@ -2547,17 +2337,13 @@ int sweep_run(fo_ctx *ctx, int M, int T, const double *d_x, const double *d_y, c
     if (trace_path && !d_trace) (void)hipMalloc((void **)&d_trace, sizeof(long long) * 4 * 65536);
     a.trace = trace_path ? d_trace : nullptr;
 #endif
-    const int lst = lst_mode;
     if (use_queue) {
       const uint32_t all5 = FO_M_DCE | FO_M_CP | FO_M_TTC | FO_M_TTCE | FO_M_HR;
       const bool allm = (a.mask & all5) == all5 && a.ablate == 0;
-      const bool launched = allm && split ? launch_queue<true, true>(lst, d_pair_f != nullptr, g, b, s, a)
-                            : split       ? launch_queue<false, true>(lst, d_pair_f != nullptr, g, b, s, a)
-                            : allm        ? launch_queue<true, false>(lst, d_pair_f != nullptr, g, b, s, a)
-                                          : launch_queue<false, false>(lst, d_pair_f != nullptr, g, b, s, a);
-      if (!launched)
-        return fo_fail(ctx, FO_E_STATE, "fo_sweep_run: no queue-kernel instantiation for list format %d with allm=%d split=%d "
-                       "(internal: such batches belong to the generic kernel)", lst, (int)allm, (int)split);
+      if (allm && split) launch_queue<true, true>(lst, d_pair_f != nullptr, g, b, s, a);
+      else if (split) launch_queue<false, true>(lst, d_pair_f != nullptr, g, b, s, a);
+      else if (allm) launch_queue<true, false>(lst, d_pair_f != nullptr, g, b, s, a);
+      else launch_queue<false, false>(lst, d_pair_f != nullptr, g, b, s, a);
     } else {
       if (lst == LST_F64) hipLaunchKernelGGL((fo_sweep_generic_kernel<true, LST_F64>), g, b, 0, s, a);
       else if (lst_is32(lst)) hipLaunchKernelGGL((fo_sweep_generic_kernel<true, LST_F32>), g, b, 0, s, a);   // (converts at the store: exact)
@@ -2629,7 +2415,7 @@ int fo_sweep_autotune(fo_ctx *ctx, int M, int T, const double *d_x, const double
   hipStream_t s = (hipStream_t)stream;
   const int A = ctx->A;
   const int n_tiles = round_up(M > 0 ? M : 1, TILE) / TILE;
-  const int lst = !d_lists ? LST_NONE : ctx->list_format == FO_LISTS_F32 ? LST_F32 : ctx->list_format == FO_LISTS_F32_EXACT ? LST_F32X : LST_F64;
+  const int lst = lst_mode_of(ctx, d_lists);
   static const int cand[4] = {1, 2, 4, 8};
   hipEvent_t e0, e1;
   FO_HIP_TRY(ctx, hipEventCreate(&e0));
@@ -2660,10 +2446,8 @@ int fo_sweep_autotune(fo_ctx *ctx, int M, int T, const double *d_x, const double
   if (rc != FO_OK) return rc == FO_E_HIP ? fo_fail(ctx, FO_E_HIP, "fo_sweep_autotune: HIP event failure") : rc;
   // remember (replace an entry of the same shape; the table is small and round-robin)
   int slot = -1;
-  for (int i = 0; i < ctx->n_tuned; ++i) {
-    const fo_ctx::Tuned &tu = ctx->tuned[i];
-    if (tu.n_tiles == n_tiles && tu.A == A && tu.T == T && tu.lst == lst && tu.pair == (d_pair_f != nullptr)) slot = i;
-  }
+  for (int i = 0; i < ctx->n_tuned; ++i)
+    if (tuned_for(ctx->tuned[i], n_tiles, A, T, lst, d_pair_f != nullptr)) slot = i;
   if (slot < 0) {
     if (ctx->n_tuned < fo_ctx::kMaxTuned) slot = ctx->n_tuned++;
     else slot = ctx->next_tuned++ % fo_ctx::kMaxTuned;

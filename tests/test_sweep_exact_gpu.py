@@ -17,7 +17,7 @@ from test_sweep_gpu import ATOL, _hip_sweep
 
 pytestmark = pytest.mark.gpu
 
-CP_ERF_BOUND = 2.6e-10      # fo_sweep.hip, FO_ERF_ORDER 3: what the dropped Taylor terms may cost a collision probability
+CP_ERF_BOUND = 2.6e-10      # fo_sweep.hip, fo_erf_fast128: what the dropped Taylor terms may cost a collision probability
 
 
 @pytest.fixture(scope="module")
