@@ -1,4 +1,4 @@
-// fo_agent_rows.hpp -- one row of the sweep's agent table, shared by fo_prep_agents_kernel (fo_sweep.hip) and by the
+// fo_agent_rows.hpp -- one row of the sweep's agent table, shared by fo_prep_agents_kernel (fo_sweep_generic.hpp) and by the
 // phantom prediction kernel of the fused planning step (fo_scene.hip, fo_step_run), which writes the table for its own
 // slot and saves the launch.  Floating-point contraction is switched off inside so that the two translation units
 // (fo_scene.hip is built with -ffp-contract=off, fo_sweep.hip is not) produce the same bits.

@@ -24,7 +24,7 @@ struct fo_ctx {
   int A = 0, Ta = 0;
   double *d_agent_tab = nullptr;    // [A][Ta][NAF]
   double *d_agent_const = nullptr;  // [A][NAC]
-  void *d_erf_tab = nullptr;        // erf lookup table (fo_sweep.hip)
+  void *d_erf_tab = nullptr;        // erf lookup table (fo_sweep_common.hpp)
   void *d_exp_tab = nullptr;        // 2^(j/256) table
   void *d_gl_tab = nullptr;         // Gauss-Legendre nodes / weights (box probabilities under correlated covariances)
   int32_t *d_agent_int = nullptr;   // [A][2] protection class, valid length

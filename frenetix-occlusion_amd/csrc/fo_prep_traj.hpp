@@ -1,5 +1,5 @@
 // fo_prep_traj.hpp -- the candidates' tile table (trajectories [M][T] -> [tile][T][4 pairs][64 lanes]) and the sweep launch's
-// chunk table, as a device function: fo_prep_traj_kernel (fo_sweep.hip) is one caller, the ray kernel of the fused planning
+// chunk table, as a device function: fo_prep_traj_kernel (fo_sweep_generic.hpp) is one caller, the ray kernel of the fused planning
 // step (fo_scene.hip, fo_step_run) the other -- there the table is written by extra workgroups of a launch that leaves most
 // of the chip idle, instead of by a launch of its own in front of the sweep.  No contractable arithmetic inside (one
 // product per output), so the two translation units produce the same bits whatever their -ffp-contract.
@@ -7,7 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 
-constexpr int FO_PREP_TILE = 64;   // = TILE of fo_sweep.hip (static_assert there)
+constexpr int FO_PREP_TILE = 64;   // = TILE of fo_sweep_plan.hpp (static_assert in fo_sweep_common.hpp)
 constexpr int FO_PREP_NEF = 8;     // = NEF
 constexpr int FO_PREP_TZ = 8;      // longest horizon slice of a block
 typedef double fo_prep_d2 __attribute__((ext_vector_type(2)));

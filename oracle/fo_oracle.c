@@ -169,7 +169,7 @@ double fo_oracle_box_prob(const double lo[2], const double hi[2], const double m
  * integrand is not below 1e-30 (|X| < 8.5 and the erf difference alive), then split into panels of half the width of
  * the integrand's narrowest feature, min(1, sqrt(1 - rho^2)/|rho|), 16 nodes each: 1e-15 against mvnun whatever the
  * variances are (tight covariances make boxes dozens of standard deviations wide).  |rho| > 0.99 counts as degenerate.
- * The HIP side integrates a different formula (over the correlation angle, fo_sweep.hip fo_corr_corners): the two
+ * The HIP side integrates a different formula (over the correlation angle, fo_sweep_generic.hpp fo_corr_corners): the two
  * check each other. */
 #define FO_GL_N 16
 static double gl_x[FO_GL_N], gl_w[FO_GL_N];

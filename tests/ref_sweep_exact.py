@@ -341,7 +341,7 @@ CP_VEH = DCE_VEH
 CP_DT = 0.1
 CP_T = 33
 ZONE = 16.0                 # agent k sits at its own zone centre; a trajectory visits one zone, the others are > 5 m off
-RHO_SWITCH = (0.5, 0.7, 0.9, 0.97)        # where fo_sweep.hip changes its Gauss-Legendre rule (GL_ASR)
+RHO_SWITCH = (0.5, 0.7, 0.9, 0.97)        # where the sweep changes its Gauss-Legendre rule (GL_ASR, fo_sweep_common.hpp)
 RHO_EXTRA = (0.99, -0.99, 0.985, -0.985, 0.3, -0.6)
 # (sxx, syy): powers of two, so that rho = sxy / sqrt(sxx syy) is the float64 rho exactly in every implementation.  Box
 # widths in units of sigma sqrt 2: 34 x 40 (tight), 1.06 x 2.47, 0.023 x 0.055 (wide)

@@ -1,9 +1,10 @@
 """The collision-probability gate (collision_probability.py:49-67,75: a CP is computed only where the nearest of the three
 means mean + j dev, j = 0, +1, -1, is not more than 5 m from the ego sample) replayed operation for operation on the samples
 of tests/golden/cp_gate_boundary.npz -- ego samples within three ulps of the 5 m circle around one of the means, produced by
-the reference's own code (gen_golden.py gate).  The sweep kernels evaluate the gate in fo_gate_d2 (csrc/fo_sweep.hip): the
+the reference's own code (gen_golden.py gate).  The sweep kernels evaluate the gate in fo_gate_d2 (csrc/fo_sweep_common.hpp): the
 mean displaced first, then the ego subtracted, each square rounded, the sum, no contraction.  NumPy float64 does exactly
 that; a fused multiply-add is emulated exactly with fractions.Fraction.  CPU only."""
+import glob
 import os
 import re
 from fractions import Fraction
@@ -13,7 +14,8 @@ import numpy as np
 from golden_util import load_case
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SWEEP = os.path.join(ROOT, "frenetix-occlusion_amd", "csrc", "fo_sweep.hip")
+CSRC = os.path.join(ROOT, "frenetix-occlusion_amd", "csrc")
+SWEEP = [os.path.join(CSRC, "fo_sweep.hip")] + sorted(glob.glob(os.path.join(CSRC, "fo_sweep_*.hpp")))   # the translation unit
 M2_IN = 25.000000000000004      # the queue kernel's square-root-free form of !(sqrt(m2) > 5.0)
 
 
@@ -100,7 +102,7 @@ def test_the_old_gate_expression_misdecides_fixture_samples():
 
 def test_both_sweep_kernels_evaluate_the_gate_through_the_replayed_function():
     """the replay above is fo_gate_d2's text: pin that text, its contraction pragma, and that both kernels call it"""
-    src = open(SWEEP).read()
+    src = "\n".join(open(f).read() for f in SWEEP)
     m = re.search(r"__device__ __forceinline__ double fo_gate_d2\(double mx, double my, double devx, double devy, double ex, "
                   r"double ey\) \{(.*?)\n\}", src, re.S)
     assert m, "fo_gate_d2 not found"

@@ -4,7 +4,7 @@ tests/golden/gen_sweep_exact.py; this module reads only those files and NumPy):
 * DCE's millimetre rounding at exact half-millimetre ties, a few 2^-51 m around them, at the 0.5 mm boundary (where TTC
   and `safe` straddle) and in walks with tied samples next to the queue kernels' (nmm + 0.51) mm pruning bound:
   dce, time_dce, ttc, ttce and safe exactly;
-* the diagonal CP within the bound fo_sweep.hip states for its erf table (2.6e-10), over every table node and phase,
+* the diagonal CP within the bound fo_sweep_common.hpp states for its erf table (2.6e-10), over every table node and phase,
   sigma^2 from 1e-6 to 1e4; the correlated CP within 1e-9, rho on both sides of every rule switch.
 
 For every kernel form, both list formats and the reduced mode.  Needs a real MI355X: run with `pytest -m gpu`."""
@@ -17,7 +17,7 @@ from test_sweep_gpu import ATOL, _hip_sweep
 
 pytestmark = pytest.mark.gpu
 
-CP_ERF_BOUND = 2.6e-10      # fo_sweep.hip, fo_erf_fast128: what the dropped Taylor terms may cost a collision probability
+CP_ERF_BOUND = 2.6e-10      # fo_sweep_common.hpp, fo_erf_fast128: what the dropped Taylor terms may cost a collision probability
 
 
 @pytest.fixture(scope="module")

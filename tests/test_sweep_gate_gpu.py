@@ -148,7 +148,7 @@ def test_saturated_gate_pools_match_the_oracle(torch_cuda, oracle, monkeypatch, 
 
 # ---------------------------------------------------------------------------------------- tapered plans, ragged phases
 # (M, A, env, tapered): A = wpb * apw * k -+ 1 with wpb = 4, so every phase boundary of the taper and its tail are ragged.
-# `tapered` is what the planner (fo_sweep.hip, the phase table before the launch) does with that shape TODAY: a planner
+# `tapered` is what the planner (plan_sweep, fo_sweep_plan.hpp) does with that shape TODAY: a planner
 # change that moves a case from one form to the other must update this table, knowingly -- the matrix must meet both.
 TAPER_CASES = [
     (4095, 255, {}, True),                          # the default apw = 2 taper: 85 % at apw 2, 10 % at 1, the apw 1 tail

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Node counts of the correlation integral (fo_sweep.hip fo_corr_corners): largest absolute error of the n-node
+"""Node counts of the correlation integral (fo_sweep_generic.hpp fo_corr_corners): largest absolute error of the n-node
 Gauss-Legendre rule over the correlation angle, against a 400-node rule of the same formula (itself equal to scipy's
 mvnun to 2e-15, checked at the end), on boxes whose corners lie near the mean and near the diagonals h = +-k where the
 integrand is sharpest.  CPU only: `python tools/corr_nodes.py`."""

@@ -1,11 +1,12 @@
 #!/bin/bash
-# hipcc -S of fo_sweep.hip into /tmp/isa/$1.s + register summary of the queue-kernel instantiations
+# hipcc -S of fo_sweep.hip (with its fo_sweep_*.hpp parts) into /tmp/isa/$1.s + register summary of the queue-kernel instantiations
 set -e
+R=$(cd "$(dirname "$0")/../.." && pwd)
 mkdir -p /tmp/isa
 out=/tmp/isa/${1:-cur}.s
 shift || true
-/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -I/root/repo/include -I/root/repo/frenetix-occlusion_amd/csrc \
-  -S --cuda-device-only "$@" -o $out /root/repo/frenetix-occlusion_amd/csrc/fo_sweep.hip 2>/dev/null
+/opt/rocm/bin/hipcc -O3 --offload-arch=gfx950 -fPIC -std=c++17 -I$R/include -I$R/frenetix-occlusion_amd/csrc \
+  -S --cuda-device-only "$@" -o $out $R/frenetix-occlusion_amd/csrc/fo_sweep.hip 2>/dev/null
 python3 - $out <<'PY'
 import re, sys
 txt = open(sys.argv[1]).read()
