@@ -16,19 +16,26 @@ Rules restated: ego intention from the curvature of the next 40 m of the referen
 visible static obstacle (:323-476), pedestrian behind a turn (:481-578), Car / Bicycle behind a visible dynamic
 obstacle (:145-317; the candidate region is sampled on a 0.25 m lattice with exact lanelet / wedge / distance tests
 and the cell classes for "occluded", the rectangle fit on a 0.1 m lattice).
-PARITY: the GEOMETRY is unpinned (no GEOS here, no reference test; known-answer scenes in tests/test_spawn_rules.py).  Pinned
-to the reference's own, unmodified SpawnLocator code (tests/golden/relevant_lanelets.npz, gen_golden.py relevant): find_spawn_points'
-orchestration -- s_threshold, the 40 m window, which family runs under which intention and switch, the order of the list -- the
-intention thresholds, the nearest-vertex rule with ties, and the dynamic rule's topology side (which intersection is the ego's,
-which lanelets are relevant with and without one).
+PARITY: BODIES PINNED, PREDICATES RESTATED.  tests/golden/spawn_rule_bodies.npz (gen_golden.py rules) records the reference's own,
+unmodified rule methods -- _find_spawn_point_behind_static_obstacle, _find_spawn_point_behind_turn,
+_find_spawn_point_behind_dynamic_obstacle with _find_matching_rectangle / _calculate_polygon_metrics, directly and through
+find_spawn_points -- over stand-ins that answer every geometric question with THIS file's primitives (CellView,
+segment_rect_distance, the lattices, the hull-edge search): the geometry under the rules stays the build's, every decision above it
+is the reference's.  tests/test_spawn_rule_bodies_cpu.py holds this checker to the recorded lists, tests/test_spawn_rules_gpu.py
+the device.  What stays unpinned is what GEOS would make of the predicates themselves (known-answer scenes in
+tests/test_spawn_rules.py).  Also pinned to the reference's own code (tests/golden/relevant_lanelets.npz, gen_golden.py relevant):
+find_spawn_points' orchestration -- s_threshold, the 40 m window, which family runs under which intention and switch, the order of
+the list -- the intention thresholds, the nearest-vertex rule with ties, and the dynamic rule's topology side.
+Where the reference raises this checker skips the obstacle or returns no point.
+From the product this file imports the SpawnPoint record and nothing else (tests/test_abi_cpu.py scans the imports): arc length,
+curvature and point-in-polygon are its own.
 """
 import math
 from typing import List, Optional
 
 import numpy as np
 
-from frenetix_occlusion.spawn_locator import SpawnPoint
-from frenetix_occlusion.utils.curvilinear import curvature, pathlength
+from frenetix_occlusion.spawn_locator import SpawnPoint      # the record only: everything else here is the checker's own
 
 ROAD, VISIBLE, OCCLUDED = 1, 2, 4      # class bits of fo_scene_visibility (include/fo_hip.h)
 
@@ -42,6 +49,58 @@ AGENT_AREA_LIMITS = {"Car": 9.0, "Bicycle": 1.7}           # :72
 OFFSET_REF_PATH = {"left turn": 3.0, "right turn": 0.0}    # :76-78
 PHANTOM_OFFSET_S = {"left turn": -0.5, "right turn": 0.0}
 PHANTOM_OFFSET_D = {"left turn": 1.0, "right turn": -1.0}
+
+
+def pathlength(polyline):
+    """arc length at every vertex of a polyline [n,2] (the checker's own: nothing is shared with the product)"""
+    p = np.asarray(polyline, dtype=np.float64)
+    seg = p[1:] - p[:-1]
+    return np.concatenate(([0.0], np.cumsum(np.sqrt(seg[:, 0] ** 2 + seg[:, 1] ** 2))))
+
+
+def _ddx(f, s):
+    """derivative of samples f at abscissae s: the three-point formula that is exact for a parabola through unevenly spaced
+    neighbours inside, the two-point difference at both ends"""
+    n = len(f)
+    out = np.empty(n)
+    out[0] = (f[1] - f[0]) / (s[1] - s[0])
+    out[-1] = (f[-1] - f[-2]) / (s[-1] - s[-2])
+    for i in range(1, n - 1):
+        hl, hr = s[i] - s[i - 1], s[i + 1] - s[i]
+        out[i] = (hl * hl * f[i + 1] + (hr * hr - hl * hl) * f[i] - hr * hr * f[i - 1]) / (hl * hr * (hl + hr))
+    return out
+
+
+def curvature(polyline):
+    """signed curvature at every vertex: (x' y'' - x'' y') / (x'^2 + y'^2)^1.5 with derivatives w.r.t. the polyline's arc length
+    by finite differences; repeated vertices are dropped first"""
+    p = np.asarray(polyline, dtype=np.float64)
+    if len(p) > 1:
+        seg = p[1:] - p[:-1]
+        p = p[np.concatenate(([True], (seg[:, 0] != 0.0) | (seg[:, 1] != 0.0)))]
+    if len(p) < 3:
+        return np.zeros(len(p))
+    s = pathlength(p)
+    xd, yd = _ddx(p[:, 0], s), _ddx(p[:, 1], s)
+    xdd, ydd = _ddx(xd, s), _ddx(yd, s)
+    den = (xd * xd + yd * yd) ** 1.5
+    return (xd * ydd - xdd * yd) / np.where(den > 1e-300, den, 1e-300)
+
+
+def points_in_polygon(q, poly):
+    """plain crossing count, half-open in y (a vertex belongs to the edge above it): q [n,2] -> bool [n]"""
+    q, poly = np.asarray(q, dtype=np.float64).reshape(-1, 2), np.asarray(poly, dtype=np.float64)
+    odd = np.zeros(len(q), dtype=bool)
+    n = len(poly)
+    for i in range(n):
+        xi, yi = poly[i]
+        xj, yj = poly[i - 1]
+        if yi == yj:
+            continue
+        hit = (yi > q[:, 1]) != (yj > q[:, 1])
+        xc = xi + (q[:, 1] - yi) * (xj - xi) / (yj - yi)
+        odd ^= hit & (q[:, 0] < xc)
+    return odd
 
 
 class CellView:
@@ -326,7 +385,6 @@ class SpawnRules:
 
     # ---- spawn_locator.py:145-317
     def _lanelets_at(self, xy):
-        from frenetix_occlusion.scenario import points_in_polygon
         q = np.asarray(xy, dtype=np.float64).reshape(1, 2)
         return [ll for ll in self.lanelets if points_in_polygon(q, ll.polygon)[0]]
 
@@ -353,7 +411,6 @@ class SpawnRules:
 
     def behind_dynamic_obstacle(self, view: CellView) -> List[SpawnPoint]:
         from scipy import ndimage
-        from frenetix_occlusion.scenario import points_in_polygon
         pts: List[SpawnPoint] = []
         vis = [o for o in self.fo_obstacles if o.current_visible and o.obstacle_role == "dynamic"]
         vis.sort(key=lambda o: float(np.linalg.norm(self.ego_pos - o.current_pos)))
@@ -463,29 +520,24 @@ def _rect_distance_points(q, center, yaw, length, width):
     return np.hypot(ex, ey)
 
 
-def _fit_rectangle(center, length, width, yaw, in_region, h=0.1):
-    """oriented rectangle clipped to the region, on a 0.1 m lattice: area, centroid and the Jaccard similarity of the
-    clipped shape with its minimum rotated rectangle (spawn_locator.py:695-726)"""
+def _rect_lattice(center, length, width, yaw, h=0.1):
+    """centres of the h-cells of an oriented rectangle, row by row in its own frame"""
     nx_, ny_ = int(round(length / h)), int(round(width / h))
     u = (np.arange(nx_) + 0.5) * h - length / 2.0
     v = (np.arange(ny_) + 0.5) * h - width / 2.0
     uu, vv = np.meshgrid(u, v)
     c, s_ = math.cos(yaw), math.sin(yaw)
-    p = np.stack((center[0] + c * uu.ravel() - s_ * vv.ravel(), center[1] + s_ * uu.ravel() + c * vv.ravel()), -1)
-    ok = in_region(p)
-    if not ok.any():
-        return None
-    area = float(ok.sum()) * h * h
-    pts = p[ok]
-    centroid = pts.mean(axis=0)
-    if ok.all():
-        return {"area": area, "centroid": centroid, "jaccard": 1.0}
-    # minimum rotated rectangle of the clipped cells (edge directions of the convex hull), cells have size h
+    return np.stack((center[0] + c * uu.ravel() - s_ * vv.ravel(), center[1] + s_ * uu.ravel() + c * vv.ravel()), -1)
+
+
+def _min_rect_area(pts, h=0.1):
+    """area of the minimum rotated rectangle of h-cells centred at pts (edge directions of the convex hull); None where the
+    hull does not exist (collinear centres)"""
     from scipy.spatial import ConvexHull
     try:
         hull = pts[ConvexHull(pts).vertices]
     except Exception:
-        return {"area": area, "centroid": centroid, "jaccard": 0.0}
+        return None
     best = np.inf
     for i in range(len(hull)):
         e = hull[(i + 1) % len(hull)] - hull[i]
@@ -496,4 +548,22 @@ def _fit_rectangle(center, length, width, yaw, in_region, h=0.1):
         a1 = hull @ e
         a2 = hull @ np.array([-e[1], e[0]])
         best = min(best, (a1.max() - a1.min() + h) * (a2.max() - a2.min() + h))
+    return float(best)
+
+
+def _fit_rectangle(center, length, width, yaw, in_region, h=0.1):
+    """oriented rectangle clipped to the region, on a 0.1 m lattice: area, centroid and the Jaccard similarity of the
+    clipped shape with its minimum rotated rectangle (spawn_locator.py:695-726)"""
+    p = _rect_lattice(center, length, width, yaw, h)
+    ok = in_region(p)
+    if not ok.any():
+        return None
+    area = float(ok.sum()) * h * h
+    pts = p[ok]
+    centroid = pts.mean(axis=0)
+    if ok.all():
+        return {"area": area, "centroid": centroid, "jaccard": 1.0}
+    best = _min_rect_area(pts, h)
+    if best is None:
+        return {"area": area, "centroid": centroid, "jaccard": 0.0}
     return {"area": area, "centroid": centroid, "jaccard": min(1.0, area / best)}

@@ -17,8 +17,9 @@ Three third-party names those files import are absent from this image and are al
                                                   (collision_probability.py:149-156 uses only these)
   * scipy.stats.mvn                            -> scipy.stats._mvn (the same Fortran MVNDST wrapper; the public
                                                   alias was dropped in scipy 1.15)
-SensorModel and SpawnLocator need shapely/commonroad proper and are NOT run here; for those the oracle is pinned by
-analytic known-answer tests only ("parity unpinned").  DCE and BE (round 6; `gen_golden.py dce`, `gen_golden.py be`,
+SensorModel needs shapely/commonroad proper and is NOT run here (analytic known-answer tests).  SpawnLocator:
+`gen_golden.py relevant` (topology side and orchestration) and `gen_golden.py rules` (the three rule bodies, unmodified, over
+stand-ins that answer the geometry from this build's discretisation -> spawn_rule_bodies.npz), each in a process of its own.  DCE and BE (round 6; `gen_golden.py dce`, `gen_golden.py be`,
 each in a process of its own): metrics/dce.py and metrics/be.py ARE executed unmodified -- the walk over the time steps with its
 rounding, tie and stop rules; the deceleration profiles, scipy re-sampling and bisection -- with the ONE module they import
 besides numpy / scipy, metrics/utils/convert_dynamic_obstacle.py (commonroad proper), replaced by duck-typed obstacles over this
@@ -1319,9 +1320,625 @@ def gen_relevant_lanelets():
           "ego on no lanelet", sum(not c["at_ego"] for c in cases), "intentions", np.bincount(out["intention"]).tolist())
 
 
+def gen_spawn_rule_bodies():
+    """tests/golden/spawn_rule_bodies.npz: the three spawn rule bodies from the reference's OWN, unmodified methods --
+    ``_find_spawn_point_behind_static_obstacle`` (spawn_locator.py:323-476), ``_find_spawn_point_behind_turn`` (:481-578) and
+    ``_find_spawn_point_behind_dynamic_obstacle`` (:145-317, with ``_find_matching_rectangle`` / ``_calculate_polygon_metrics``,
+    :695-726) -- called directly and through ``find_spawn_points``.  spawn_locator.py and utils/helper_functions.py
+    (``vector_from_angle``, ``create_oriented_rectangle``) are loaded unmodified; shapely, commonroad_dc,
+    commonroad_route_planner and the ``cosy_cl`` object are stand-ins written here.
+
+    THE GEOMETRY UNDER THE RULES STAYS THE BUILD'S; EVERY DECISION ABOVE IT IS THE REFERENCE'S.  The stand-ins answer each
+    geometric question from the build's discretisation: the areas (occluded / visible / road, visible obstacles) through
+    oracle.fo_spawn_rules_ref.CellView and segment_rect_distance on the cell classes of the CPU scene oracle, with the checker's
+    sample steps; the dynamic rule's regions as a point predicate plus the 0.25 m lattice anchored at the obstacle (parts by
+    scipy.ndimage.label, the fits on the 0.1 m lattice, the minimum rotated rectangle by the hull-edge search); lanelet queries
+    from the scenario objects, orientations from the lane-yaw raster; the curvilinear frame is the project's PolylineCS or a
+    duck-typed frame with interpolated normals.  The order of the rejections, the comparisons, what is appended when and what
+    is returned are the reference's control flow.  Where a stand-in has no defined answer (centroid of an empty shape, the
+    orientation at a point on no lanelet ...) it raises, and the case is recorded as 'the reference raises'.
+
+    The methods run under a line tracer: the generator fails unless every executable line of the four ranges is hit, save the
+    allow-list of tests/test_spawn_rule_bodies_cpu.py, and unless the caps of that file hold (raising cases, points per family,
+    MultiPoint / MultiLineString cases)."""
+    import importlib.util
+    import math
+    repo = os.path.dirname(os.path.dirname(OUT))
+    for q in (repo, os.path.join(repo, "frenetix-occlusion_amd"), os.path.dirname(OUT)):
+        if q not in sys.path:
+            sys.path.insert(0, q)
+    from scipy import ndimage
+    from oracle import fo_oracle as O
+    from oracle import fo_spawn_rules_ref as CK
+    import spawn_rule_cases as SC
+    import test_spawn_rule_bodies_cpu as LIM
+    O.build()
+    NS = types.SimpleNamespace
+    ctx = NS(view=None, lane_yaw_at=None, polys=None)
+
+    class Undefined(Exception):
+        """a stand-in was asked something it has no defined answer to"""
+
+    # ---- shapely.geometry / shapely.ops / shapely.affinity ------------------------------------------------------------
+    class Empty:
+        geom_type, is_empty = "GeometryCollection", True
+
+        def buffer(self, r):
+            return self
+
+        def intersects(self, other):
+            return False
+
+        def within(self, other):
+            return False
+
+    class Point:
+        geom_type, is_empty = "Point", False
+
+        def __init__(self, *a):
+            xy = a[0] if len(a) == 1 else a
+            self.xy = np.array([float(xy[0]), float(xy[1])])
+        x = property(lambda self: self.xy[0])
+        y = property(lambda self: self.xy[1])
+
+        def buffer(self, r):
+            return Disc(self.xy, float(r))
+
+        def within(self, area):
+            return bool(area._contains_point(self.xy))
+
+    class MultiPoint:
+        geom_type, is_empty = "MultiPoint", False
+
+        def __init__(self, pts):
+            self.geoms = [Point(q) for q in pts]
+
+    class Disc:
+        def __init__(self, c, r):
+            self.c, self.r = c, r
+
+        def intersects(self, area):
+            return bool(area._touches_disc(self.c, self.r))
+
+        def within(self, area):
+            return bool(area._disc_within(self.c, self.r))
+
+        def _member(self, q):
+            return np.hypot(q[:, 0] - self.c[0], q[:, 1] - self.c[1]) <= self.r
+
+    class LineString:
+        geom_type = "LineString"
+
+        def __init__(self, pts=()):
+            self.pts = np.asarray(pts, dtype=np.float64).reshape(-1, 2)
+            if len(self.pts) == 1:
+                raise ValueError("a line needs two points")
+            self.is_empty, self.coords = len(self.pts) == 0, self.pts
+
+        def intersects(self, area):
+            return bool(area._touches_line(self.pts))
+
+        def buffer(self, r):
+            return FatLine(self.pts, float(r))
+
+        def intersection(self, area):
+            runs = [] if self.is_empty else area._runs(self.pts)
+            if not runs:
+                return Empty()
+            parts = []
+            for a, b in runs:
+                ls = LineString()
+                ls.pts = ls.coords = np.array([a, b])
+                ls.is_empty = False
+                parts.append(ls)
+            return parts[0] if len(parts) == 1 else NS(geom_type="MultiLineString", is_empty=False, geoms=parts)
+
+    class FatLine:
+        def __init__(self, pts, r):
+            self.pts, self.r = pts, r
+
+        def intersects(self, multi):
+            return any(CK.segment_rect_distance(a, b, c) <= self.r for a, b in zip(self.pts[:-1], self.pts[1:]) for c in multi.polys)
+
+    class ObstacleUnion:                      # fo_obstacles.visible_obstacle_multipolygon
+        def __init__(self, polys):
+            self.polys = polys
+
+        def _touches_disc(self, c, r):
+            return any(CK.segment_rect_distance(c, c, q) <= r for q in self.polys)
+
+    class ClassArea:                          # sensor_model.occluded_area / visible_area / road_polygon
+        def __init__(self, bit):
+            self.bit = bit
+
+        def _touches_line(self, pts):
+            return ctx.view.polyline_touches(pts, self.bit)
+
+        def _touches_disc(self, c, r):
+            return ctx.view.disc_touches(c, r, self.bit)
+
+        def _disc_within(self, c, r):
+            return ctx.view.disc_within(c, r, self.bit)
+
+        def _contains_point(self, xy):
+            return bool(ctx.view.class_at(xy) & self.bit)
+
+        def _member(self, q):
+            return np.array([bool(ctx.view.class_at(p) & self.bit) for p in q], dtype=bool)
+
+        def _runs(self, pts):
+            return ctx.view.runs_inside(pts, self.bit)
+
+        def buffer(self, b):
+            area = self
+
+            class Exterior:
+                def intersection(self, line):
+                    p, _ = ctx.view.sample_polyline(line.pts)
+                    near = np.array([ctx.view.disc_touches(q, b, area.bit) for q in p])
+                    flips = np.nonzero(near[1:] != near[:-1])[0]
+                    cand = [p[i + 1] if near[i] else p[i] for i in flips]       # the sample just outside the buffered area
+                    return Empty() if not cand else Point(cand[0]) if len(cand) == 1 else MultiPoint(cand)
+            return NS(exterior=Exterior())
+
+    class Polygon:
+        """base of every area of the dynamic rule (``isinstance(geom, Polygon)``); built from four corner tuples it is the
+        rectangle helper_functions.create_oriented_rectangle starts from"""
+        is_empty = False
+
+        def __init__(self, coords=None):
+            if coords is not None:
+                c = np.asarray(coords, dtype=np.float64)
+                self.length, self.width = float(c[:, 0].max() - c[:, 0].min()), float(c[:, 1].max() - c[:, 1].min())
+                self.yaw, self.center = 0.0, np.zeros(2)
+
+        def intersection(self, region):       # the oriented rectangle clipped to the allowed area: the 0.1 m fit
+            return Fit(self.center, self.length, self.width, self.yaw, region)
+
+    def rotate(poly, angle, origin=(0, 0), use_radians=False):
+        assert tuple(origin) == (0, 0) and not use_radians
+        out = Polygon()
+        out.length, out.width, out.center, out.yaw = poly.length, poly.width, poly.center, math.radians(angle)
+        return out
+
+    def translate(poly, xoff=0.0, yoff=0.0):
+        out = Polygon()
+        out.length, out.width, out.yaw, out.center = poly.length, poly.width, poly.yaw, np.array([float(xoff), float(yoff)])
+        return out
+
+    class Region(Polygon):
+        """a point predicate; with an anchor (the 12 m disc about the obstacle) the 0.25 m lattice the checker labels"""
+        H = 0.25
+
+        def __init__(self, member, anchor=None, part=None):
+            self._m, self.anchor, self.part, self._lat = member, anchor, part, None
+
+        def _member(self, q):
+            return self._m(np.asarray(q, dtype=np.float64).reshape(-1, 2))
+
+        def intersection(self, other):
+            anchor = self.anchor or getattr(other, "anchor", None) or ((other.c, other.r) if isinstance(other, Disc) else None)
+            return Region(lambda q: self._member(q) & other._member(q), anchor)
+
+        def difference(self, other):
+            return Region(lambda q: self._member(q) & ~other._member(q), self.anchor)
+
+        def _lattice(self):
+            if self._lat is None:
+                if self.anchor is None:
+                    raise Undefined("a region without a lattice")
+                c, rad = self.anchor
+                ax = np.arange(-rad, rad + 0.5 * self.H, self.H)
+                gx, gy = np.meshgrid(c[0] + ax, c[1] + ax)
+                inside = self._member(np.stack((gx.ravel(), gy.ravel()), -1)).reshape(gx.shape)
+                lab, n = ndimage.label(inside)
+                self._lat = (gx, gy, inside, lab, n)
+            return self._lat
+
+        @property
+        def mask(self):
+            gx, gy, inside, lab, n = self._lattice()
+            return inside if self.part is None else lab == self.part
+
+        @property
+        def geom_type(self):
+            return "MultiPolygon" if self.part is None and self._lattice()[4] > 1 else "Polygon"
+
+        @property
+        def geoms(self):
+            parts = []
+            for k in range(1, self._lattice()[4] + 1):
+                r = Region(self._m, self.anchor, k)
+                r._lat = self._lat
+                parts.append(r)
+            return parts
+
+        @property
+        def area(self):
+            return float(self.mask.sum()) * self.H * self.H
+
+        @property
+        def centroid(self):
+            gx, gy, m = self._lattice()[0], self._lattice()[1], self.mask
+            if not m.any():
+                raise Undefined("centroid of an empty region")
+            return Point(gx[m].mean(), gy[m].mean())
+
+        def contains(self, p):
+            """membership of arbitrary points: predicate true and the nearest lattice node belongs to this part"""
+            p = np.asarray(p, dtype=np.float64).reshape(-1, 2)
+            gx, gy, m = self._lattice()[0], self._lattice()[1], self.mask
+            ix = np.rint((p[:, 0] - gx[0, 0]) / self.H).astype(int)
+            iy = np.rint((p[:, 1] - gy[0, 0]) / self.H).astype(int)
+            okb = (ix >= 0) & (ix < gx.shape[1]) & (iy >= 0) & (iy < gx.shape[0])
+            out = np.zeros(len(p), dtype=bool)
+            out[okb] = m[iy[okb], ix[okb]]
+            return out & self._member(p)
+
+        def _contains_point(self, xy):
+            return bool(self.contains(xy)[0])
+
+    class Fit(Polygon):
+        H = 0.1
+
+        def __init__(self, center, length, width, yaw, region):
+            p = CK._rect_lattice(center, length, width, yaw, self.H)
+            self.pts = p[region.contains(p)]
+            self.area = float(len(self.pts)) * self.H * self.H
+
+        @property
+        def centroid(self):
+            if not len(self.pts):
+                raise Undefined("centroid of an empty shape")
+            return Point(self.pts.mean(axis=0))
+
+        @property
+        def minimum_rotated_rectangle(self):
+            if not len(self.pts):
+                return Box(0.0)
+            best = CK._min_rect_area(self.pts, self.H)
+            if best is None:
+                raise Undefined("no hull")
+            return Box(best)
+
+        def intersection(self, box):          # a shape lies inside its minimum rotated rectangle
+            assert isinstance(box, Box)
+            return self
+
+    class Box(Polygon):
+        def __init__(self, area):
+            self.area = float(area)
+
+    def unary_union(geoms):
+        geoms = list(geoms)
+        boxes = [g for g in geoms if isinstance(g, Box)]
+        if boxes:                              # shape | its minimum rotated rectangle
+            return boxes[0]
+        return Region(lambda q: np.logical_or.reduce([g._member(q) for g in geoms]))
+
+    def lanelet_orientation_at_position(lanelet, pos):
+        yaw = ctx.lane_yaw_at(pos) if lanelet is not None else None
+        if yaw is None:
+            raise Undefined("no lanelet orientation here")
+        return yaw
+
+    def curvature_or_raise(polyline):
+        if len(polyline) < 3:
+            raise Undefined("curvature of fewer than three points")
+        return CK.curvature(polyline)
+
+    def mod(name, **attrs):
+        m = types.ModuleType(name)
+        for k, v in attrs.items():
+            setattr(m, k, v)
+        sys.modules[name] = m
+        return m
+    mod("commonroad_dc", geometry=mod("commonroad_dc.geometry", util=mod(
+        "commonroad_dc.geometry.util", compute_pathlength_from_polyline=CK.pathlength,
+        compute_curvature_from_polyline=curvature_or_raise)))
+    mod("shapely", geometry=mod("shapely.geometry", Polygon=Polygon, Point=Point, MultiPolygon=Polygon, LineString=LineString),
+        affinity=mod("shapely.affinity", rotate=rotate, translate=translate), ops=mod("shapely.ops", unary_union=unary_union))
+    mod("commonroad_route_planner", utility=mod("commonroad_route_planner.utility", route=mod(
+        "commonroad_route_planner.utility.route", lanelet_orientation_at_position=lanelet_orientation_at_position)))
+
+    def load(name, rel):                       # the reference's file, unmodified, under a name that is not the product's
+        spec = importlib.util.spec_from_file_location(name, os.path.join(REF, "frenetix_occlusion", rel))
+        m = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(m)
+        return m
+    import frenetix_occlusion.utils as product_utils
+    hf = load("fo_reference_helper_functions", "utils/helper_functions.py")
+    sys.modules["frenetix_occlusion.utils.helper_functions"] = product_utils.helper_functions = hf
+    RSL = load("fo_reference_spawn_locator", "spawn_locator.py")
+    del sys.modules["frenetix_occlusion.utils.helper_functions"], product_utils.helper_functions
+    ref_file = RSL.SpawnLocator.find_spawn_points.__code__.co_filename
+
+    # ---- executable lines of the four ranges, and the tracer ----------------------------------------------------------
+    def in_ranges(n):
+        return any(a <= n <= b for a, b in LIM.RANGES)
+    executable, hit = set(), set()
+
+    def walk(code):
+        executable.update(n for _, _, n in code.co_lines() if n is not None and in_ranges(n) and n != code.co_firstlineno)
+        for c in code.co_consts:
+            if isinstance(c, types.CodeType):
+                walk(c)
+    for name in ("_find_spawn_point_behind_dynamic_obstacle", "_find_spawn_point_behind_static_obstacle",
+                 "_find_spawn_point_behind_turn", "_find_matching_rectangle", "_calculate_polygon_metrics"):
+        walk(getattr(RSL.SpawnLocator, name).__code__)
+
+    def tracer(frame, event, arg):
+        if frame.f_code.co_filename != ref_file:
+            return None
+        if event == "line":
+            ctx.case_hit.add(frame.f_lineno)
+        return tracer
+
+    # ---- the scenario side --------------------------------------------------------------------------------------------
+    def reference_locator(case, view, obs, lane_yaw_at):
+        lls = {}
+        for ll in case.lanelets:
+            lls[ll.lanelet_id] = NS(lanelet_id=ll.lanelet_id, adj_left=ll.adj_left, predecessor=list(ll.predecessors),
+                                    left_vertices=ll.left, polygon=NS(shapely_object=Region(
+                                        lambda q, poly=ll.polygon: CK.points_in_polygon(q, poly))))
+        net = NS(intersections=[NS(incomings=[NS(incoming_lanelets=set(e["incoming"]), successors_left=set(e["left"]),
+                                                 successors_right=set(e["right"]), successors_straight=set(e["straight"]))
+                                              for e in it["incomings"]]) for it in case.intersections],
+                 find_lanelet_by_id=lambda i: lls[i],
+                 find_lanelet_by_position=lambda plist: [[ll.lanelet_id for ll in case.lanelets if CK.points_in_polygon(
+                     np.asarray(q, dtype=np.float64).reshape(1, 2), ll.polygon)[0]] for q in plist])
+
+        class Obstacles(list):
+            pass
+        fo = Obstacles()
+        wedges = {}
+        for o in obs:
+            body = NS(buffer=lambda b, o=o: NS(_member=lambda q: CK._rect_distance_points(
+                q, o.current_pos, o.current_orientation, o.length, o.width) <= b))
+            fo.append(NS(current_visible=bool(o.current_visible), current_pos=o.current_pos, current_orientation=o.current_orientation,
+                         current_corner_points=o.current_corner_points, current_polygon=body,
+                         cr_obstacle=NS(obstacle_role=NS(name=str(o.obstacle_role).upper()), obstacle_type=NS(value=str(o.obstacle_type)),
+                                        obstacle_id=o.obstacle_id)))
+            if o.current_pos is not None:
+                wedges[o.obstacle_id] = Region(lambda q, o=o: CK._behind_rect(case.ego, q, o.current_corner_points))
+        fo.visible_obstacle_multipolygon = ObstacleUnion([o.current_corner_points for o in obs if o.current_visible])
+        sm = NS(occluded_area=ClassArea(CK.OCCLUDED), visible_area=ClassArea(CK.VISIBLE), road_polygon=ClassArea(CK.ROAD),
+                obstacle_occlusions=wedges)
+        ctx.view, ctx.lane_yaw_at = view, lane_yaw_at
+        cfg = {"spawn_locator": case.cfg["spawn_locator"], "agent_manager": case.cfg["agent_manager"]}
+        return RSL.SpawnLocator(NS(scenario=NS(lanelet_network=net)), case.path, SC.frame_of(case), sm, fo, cfg)
+
+    def record(call):
+        sys.settrace(tracer)
+        try:
+            res = call()
+        except Exception as e:      # noqa: BLE001 -- whatever the reference raises over the stand-ins is the recorded answer
+            return (SC.RAISES, type(e).__name__, [])
+        finally:
+            sys.settrace(None)
+        return (SC.NONE if res is None else SC.POINTS, "", SC.points_of(res))
+
+    def run(case):
+        view, obs, lane_yaw_at, _ = SC.cpu_scene(O, case)
+        try:
+            ego_cl = np.asarray(SC.frame_of(case).convert_to_curvilinear_coords(case.ego[0], case.ego[1]))
+        except ValueError:
+            return None                       # the ego outside the frame's projection domain: not a case
+        sl = reference_locator(case, view, obs, lane_yaw_at)
+        ctx.case_hit = set()
+        calls = {"find": record(lambda: list(sl.find_spawn_points(case.ego, case.yaw, ego_cl, case.v)))}
+        intention = None
+        if sl.reference is not None and len(sl.reference) >= 3:
+            intention = sl._find_ego_intention(sl.reference)
+        skipped = (SC.NOT_RUN, "", [])
+        calls["dynamic"] = record(sl._find_spawn_point_behind_dynamic_obstacle) if intention else skipped
+        calls["static"] = record(sl._find_spawn_point_behind_static_obstacle) if intention else skipped
+        calls["turn"] = record(lambda: sl._find_spawn_point_behind_turn(intention)) if intention in ("left turn", "right turn") else skipped
+        return dict(intention=intention, counts=SC.class_counts(view.cls), calls=calls, lines=frozenset(ctx.case_hit),
+                    multipoint=LIM.LINE_MULTIPOINT in ctx.case_hit, multiline=LIM.LINE_MULTILINESTRING in ctx.case_hit)
+
+    # ---- the scenes -----------------------------------------------------------------------------------------------------
+    rng = np.random.default_rng(20250917)
+    cands, pool, tagged = [], [], {}
+    SPACING_GAPS = (4.9, 4.99, 5.01, 5.1)
+    FLOOR_CASES = ((6.0, 25.9), (6.0, 26.1), (6.3, 26.1), (6.3, 26.3))
+    HOOK_CASES = ((-11.0, -15.0, -0.5), (-10.0, -14.0, -0.5), (-11.0, -15.5, -0.8))
+    park = lambda i, x, y=-2.4, yaw=0.0, length=4.5, width=1.8: [i, 0, SC.TYPES.index("parkedVehicle"), length, width, x, y, yaw, 0.0]
+    moving = lambda i, typ, x, y, yaw, length=9.0, width=3.2, v=8.0: [i, 1, SC.TYPES.index(typ), length, width, x, y, yaw, v]
+    # (a) the three scenario fixtures at seeded poses, time steps and speeds (the _random_case recipe of tests/test_spawn_rules_gpu.py)
+    scs = [NS(lanelets=SC.load_map(i)[0]) for i in range(3)]
+    def seeded_scenario_case():
+        while True:
+            si = int(rng.integers(3))
+            lanelets = scs[si].lanelets
+            by = {l.lanelet_id: l for l in lanelets}
+            ll = lanelets[int(rng.integers(len(lanelets)))]
+            c = ll.center
+            i = int(rng.integers(0, max(len(c) - 2, 1)))
+            ego = c[i] + rng.normal(0.0, 0.3, 2)
+            yaw = math.atan2(c[i + 1, 1] - c[i, 1], c[i + 1, 0] - c[i, 0]) + float(rng.normal(0.0, 0.05))
+            if rng.random() < 0.5:
+                path = ego[None] + np.linspace(-5.0, 80.0, 171)[:, None] * np.array([[math.cos(yaw), math.sin(yaw)]])
+            else:
+                parts, cur = [c[max(i - 3, 0):]], ll
+                for _ in range(3):
+                    if not cur.successors:
+                        break
+                    cur = by.get(cur.successors[int(rng.integers(len(cur.successors)))])
+                    if cur is None:
+                        break
+                    parts.append(cur.center[1:])
+                path = np.concatenate(parts)
+                path = path[np.concatenate(([True], np.hypot(np.diff(path[:, 0]), np.diff(path[:, 1])) > 1e-6))]
+            step, v = int(rng.integers(0, 80)), float(rng.choice([rng.uniform(2.0, 12.0), 6.25, 6.2, 6.3]))
+            if len(path) < 4:
+                continue
+            return (SC.make_case(si, ego, yaw, v, step, path, (), rng.random(3) < 0.9, int(rng.choice([0, 1, 3])),
+                                      int(rng.choice([0, 1, 3])), int(rng.random() < 0.25), 360))
+    while len(cands) < 120:
+        cands.append(seeded_scenario_case())
+    # (b) parked cars on the straight road: counts against the maxima, pairs on either side of the 5 m spacing, far / behind
+    path_s = np.stack((np.linspace(-5, 115, 241), np.full(241, -1.0)), -1)
+    for mx in (0, 1, 3):
+        for n_cars in (1, 2, 6):
+            cands.append(SC.make_case(3, [0.0, -1.0], 0.0, 12.0, 0, path_s, [park(70 + i, 12.0 + 7.0 * i) for i in range(n_cars)],
+                                      max_static=mx, max_dynamic=mx))
+    for gap in (4.0, 4.9, 5.0, 5.1, 5.6, 6.5, 8.0):
+        for v in (6.0, 6.25, 6.5):
+            cands.append(SC.make_case(3, [0.0, -1.0], 0.0, v, 0, path_s, [park(70, 14.0), park(71, 14.0 + gap, width=1.8)], max_static=3))
+    for x in (17.0, 29.0, 31.5, 45.0, -6.0, 2.0, 24.0, 27.5):
+        for v in (5.0, 6.25, 8.0):
+            cands.append(SC.make_case(3, [0.0, -1.0], 0.0, v, 0, path_s, [park(77, x), park(78, x + 9.0, y=2.4)], max_static=3))
+    for k in range(24):                        # seeded: lateral offsets, headings, a second row of cars, short reference paths
+        cars = [park(60 + i, float(rng.uniform(6.0, 34.0)), y=float(rng.choice([-2.4, 2.4, -1.2, -3.2])), yaw=float(rng.normal(0.0, 0.15)))
+                for i in range(int(rng.integers(1, 6)))]
+        p = path_s[:int(rng.choice([241, 80, 50, 14]))]
+        cands.append(SC.make_case(3, [float(rng.uniform(-3.0, 3.0)), float(rng.uniform(-2.5, 1.0))], float(rng.normal(0.0, 0.05)),
+                                  float(rng.uniform(3.0, 12.0)), 0, p, cars, max_static=int(rng.choice([0, 1, 3])), frame=int(k % 4 == 0)))
+    # (c) the side street: right and left turns, ego positions and speeds, parked cars at the corner, paths that go straight on
+    ang = np.linspace(0, math.pi / 2, 30)
+    turn = np.concatenate((np.stack((np.linspace(-30, 7.75, 76), np.full(76, -1.75)), -1),
+                           np.stack((7.75 + 4.0 * np.sin(ang), -5.75 + 4.0 * np.cos(ang)), -1)[1:],
+                           np.stack((np.full(60, 11.75), np.linspace(-6.25, -36.0, 60)), -1)))
+    straight_on = np.stack((np.linspace(-30, 40, 141), np.full(141, -1.75)), -1)
+    mir = np.array([1.0, -1.0])
+    for mi, sg in ((4, 1.0), (5, -1.0)):
+        for ex in (-28.0, -20.0, -12.0, -5.0, 0.0, 4.0, 7.0):
+            for v in (3.0, 6.25, 9.0):
+                rows = [] if ex != -5.0 else [park(50, 11.75 if v < 9 else 14.0, y=sg * (-9.0 if v < 6 else -14.0), yaw=math.pi / 2)]
+                cands.append(SC.make_case(mi, np.array([ex, -1.75]) * [1.0, sg], 0.0, v, 0, turn * [1.0, sg], rows,
+                                          frame=int(ex in (-12.0, 4.0))))
+        cands.append(SC.make_case(mi, np.array([-5.0, -1.75]) * [1.0, sg], 0.0, 6.0, 0, straight_on * [1.0, sg]))
+        for k in range(8):
+            rows = [park(40 + i, float(rng.uniform(-2.0, 16.0)), y=sg * float(rng.uniform(-30.0, -1.0)), yaw=float(rng.choice([0.0, math.pi / 2])))
+                    for i in range(int(rng.integers(1, 4)))]
+            cands.append(SC.make_case(mi, np.array([float(rng.uniform(-25.0, 6.0)), -1.75 + float(rng.normal(0, 0.2))]) * [1.0, sg],
+                                      float(rng.normal(0.0, 0.04)), float(rng.uniform(2.0, 10.0)), 0, turn * [1.0, sg], rows))
+    # (d) the two-way road: oncoming vehicles with headings on and next to the 160 / 200 degree bounds, types, distances, several
+    path_t = np.stack((np.linspace(-5, 65, 141), np.full(141, -1.75)), -1)
+    d2r = math.radians
+    for deg in (180.0, 160.0, 159.9, 160.1, 200.0, 199.9, 200.1, 170.0, 0.0, 90.0):
+        for typ in ("truck", "car"):
+            cands.append(SC.make_case(6, [0.0, -1.75], 0.0, 8.0, 0, path_t,
+                                      [moving(31, typ, 20.0, 1.75, d2r(deg), *((9.0, 3.2) if typ == "truck" else (4.8, 2.0)))]))
+    for typ, x, y in (("bicycle", 20.0, 1.75), ("pedestrian", 20.0, 1.75), ("truck", 33.0, 1.75), ("truck", 1.0, 1.75), ("truck", 20.0, -1.75),
+                      ("truck", 20.0, 5.5), ("bus", 12.0, 1.75), ("truck", 62.0, 1.75), ("truck", 28.0, 1.75)):
+        cands.append(SC.make_case(6, [0.0, -1.75], 0.0, 8.0, 0, path_t, [moving(32, typ, x, y, math.pi)]))
+    for mx in (0, 1, 3):
+        cands.append(SC.make_case(6, [0.0, -1.75], 0.0, 8.0, 0, path_t,
+                                  [moving(31 + i, "truck", 14.0 + 13.0 * i, 1.75, math.pi, 7.0, 3.0) for i in range(3)], max_dynamic=mx))
+    for k in range(30):
+        rows = [moving(31 + i, str(rng.choice(["truck", "car", "bus"])), float(rng.uniform(6.0, 40.0)), float(rng.choice([1.75, 1.75, 1.2, 2.4])),
+                       math.pi + float(rng.choice([0.0, 0.0, rng.normal(0.0, 0.3)])), float(rng.uniform(4.5, 12.0)), float(rng.uniform(1.8, 3.3)))
+                for i in range(int(rng.integers(1, 4)))]
+        if k % 5 == 0:
+            rows.append(park(90, float(rng.uniform(10.0, 30.0)), y=-2.6))
+        cands.append(SC.make_case(6, [float(rng.uniform(-4.0, 6.0)), -1.75], float(rng.normal(0.0, 0.03)), float(rng.uniform(4.0, 12.0)), 0,
+                                  path_t[:int(rng.choice([141, 141, 60]))], rows, max_dynamic=int(rng.choice([0, 1, 3])), frame=int(k % 6 == 0)))
+    # (e) the urban grid at the bench's pose and along its street
+    ego0 = SC.urban_ego_initial()
+    for dx, dyaw in ((0.0, 0.0), (14.0, 0.0), (31.0, 0.0), (-12.0, 0.0), (6.0, 0.03), (22.0, -0.02), (40.0, 0.0), (52.0, 0.01)):
+        yaw = float(ego0[2]) + dyaw
+        ego = ego0[:2] + dx * np.array([math.cos(ego0[2]), math.sin(ego0[2])])
+        path = ego[None] + np.linspace(-5.0, 80.0, 171)[:, None] * np.array([[math.cos(yaw), math.sin(yaw)]])
+        for mx in (1, 3):
+            cands.append(SC.make_case(7, ego, yaw, 8.0, 0, path, max_static=mx, max_dynamic=mx))
+
+    # (f) a right bend of 42.5 / 47.5 degrees: the lanelet orientation at the phantom position on either side of the 45 degree rule
+    for name in ("bend_42", "bend_47"):
+        bp = SC.bend_path(SC.BEND_DEG[name])
+        for ex in (-25.0, -18.0, -12.0, -8.0):
+            cands.append(SC.make_case(SC.MAPS.index(name), [ex, bp[0, 1]], 0.0, 6.0, 0, bp))
+    # (g) two short parked cars whose far cross lines lie 4.9 / 4.99 / 5.01 / 5.1 m apart in s: the second pedestrian on either
+    # side of the 5 m spacing (the straight path makes s of a spawn point the s of its cross line: car centre + 1.0 + 0.8)
+    short = lambda i, x: park(i, x, length=2.0, width=1.8)
+    for gap in SPACING_GAPS:
+        tagged["gap", gap] = SC.make_case(3, [0.0, -1.0], 0.0, 8.0, 0, path_s, [short(70, 14.0), short(71, 14.0 + gap)], max_static=3)
+    # (h) one parked car on either side of the s limit, where the 25 m floor holds (4 v = 24) and where 4 v = 25.2 has just
+    # taken over; the path starts 1 m behind the ego, so that the limit (twice the ego's s plus the threshold) stays inside the
+    # 30 m distance limit: s = 27 and 27.2, x = 26 and 26.2
+    path_f = np.stack((np.linspace(-1, 115, 233), np.full(233, -1.0)), -1)
+    for v, x in FLOOR_CASES:
+        tagged["floor", v, x] = SC.make_case(3, [0.0, -1.0], 0.0, v, 0, path_f, [park(70, x)])
+    # (i) the hook: a small oncoming car before the mitred corner of the narrow inner lanelet, the ego close behind it on the
+    # outer one; the car's shadow holds the rest of the leg and the leg after the corner, and the centre of that L lies in
+    # the angle between the legs, on no lanelet
+    hook = SC.MAPS.index("hook_left")
+    hp = (SC.bend_path(90.0, v=1.75) * np.array([1.0, -1.0]))[:70]          # the straight lead: no turn is intended
+    for cx, ex, ey in HOOK_CASES:
+        tagged["hook", cx, ex, ey] = SC.make_case(hook, [ex, ey], 0.0, 8.0, 0, hp, [moving(31, "car", cx, 1.0, math.pi, 3.0, 1.4)])
+    cands += list(tagged.values())
+    cands = [(c, True) for c in cands]
+    # search pools (kept only where they add coverage, see below)
+    for k in range(400):
+        pool.append((seeded_scenario_case(), False))
+    for k in range(250):                       # parked cars across the whole road width and over its edges
+        cars = [park(60 + i, float(rng.uniform(5.0, 34.0)), y=float(rng.uniform(-4.4, 4.4)), yaw=float(rng.choice([0.0, rng.normal(0.0, 0.3)])),
+                     length=float(rng.uniform(3.5, 7.0)), width=float(rng.uniform(1.6, 2.6))) for i in range(int(rng.integers(1, 5)))]
+        pool.append((SC.make_case(3, [float(rng.uniform(-3.0, 3.0)), float(rng.uniform(-3.0, 3.0))], float(rng.normal(0.0, 0.05)),
+                                  float(rng.uniform(3.0, 12.0)), 0, path_s, cars, max_static=3), False))
+    for k in range(300):                       # the side street with parked cars on and next to the path, before and after the corner
+        mi, sg = ((4, 1.0), (5, -1.0))[k % 2]
+        ex = float(rng.uniform(-28.0, 8.0))
+        rows = []
+        for i in range(int(rng.integers(1, 4))):
+            if rng.random() < 0.5:             # on the main road ahead of the ego
+                rows.append(park(40 + i, ex + float(rng.uniform(6.0, 25.0)), y=sg * float(rng.choice([-1.75, -2.75, -0.8])), yaw=0.0))
+            else:                              # in the side street
+                rows.append(park(40 + i, float(rng.uniform(10.0, 14.0)), y=sg * float(rng.uniform(-30.0, -5.0)), yaw=math.pi / 2))
+        pool.append((SC.make_case(mi, np.array([ex, -1.75]) * [1.0, sg], 0.0, float(rng.uniform(2.0, 10.0)), 0, turn * [1.0, sg], rows), False))
+    # every designed scene is kept; a scene of a search pool is kept when it executes a line of the rule bodies that no scene
+    # before it did, or takes a branch whose minimum count is still open
+    cases, records, n_ml, n_mp = [], [], 0, 0
+    for case, designed in cands + pool:
+        rec = run(case)
+        if rec is None:
+            continue
+        new_lines = (ctx.case_hit & executable) - hit
+        raises = any(c[0] == SC.RAISES for c in rec["calls"].values())
+        if designed and raises and case.map_index < 3 and sum(any(c[0] == SC.RAISES for c in r["calls"].values()) for r in records) >= 12:
+            continue                           # (seeded scenario poses where the reference raises: a dozen is enough)
+        if not designed and not new_lines and not (rec["multiline"] and n_ml < 2 * LIM.MIN_BRANCH_CASES and not raises) \
+                and not (rec["multipoint"] and n_mp < 2 * LIM.MIN_BRANCH_CASES and not raises):
+            continue
+        hit.update(ctx.case_hit)
+        n_ml, n_mp = n_ml + rec["multiline"], n_mp + rec["multipoint"]
+        cases.append(case)
+        records.append(rec)
+    # the designed scenes (g), (h), (i) do what they were designed for, from the reference run alone
+    rec_of = {key: records[next(i for i, c in enumerate(cases) if c is case)] for key, case in tagged.items()}
+    static_s = lambda pts: [float(p[3][0]) for p in pts]
+
+    def reference_static(case, **attrs):       # the static rule with an attribute of the reference's object set to another value
+        view, obs, lane_yaw_at, _ = SC.cpu_scene(O, case)
+        sl = reference_locator(case, view, obs, lane_yaw_at)
+        list(sl.find_spawn_points(case.ego, case.yaw, np.asarray(SC.frame_of(case).convert_to_curvilinear_coords(*case.ego)), case.v))
+        for name, value in attrs.items():
+            assert hasattr(sl, name)
+            setattr(sl, name, value)
+        return static_s(SC.points_of(sl._find_spawn_point_behind_static_obstacle()))
+    for gap in SPACING_GAPS:
+        rec, got = rec_of["gap", gap], static_s(rec_of["gap", gap]["calls"]["static"][2])
+        assert 453 in rec["lines"] and len(got) == (2 if gap > 5.0 else 1), (gap, got)
+        if gap < 5.0:                          # the second car's point is refused by the spacing and by nothing else
+            got = reference_static(tagged["gap", gap], min_distance_between_pedestrians=gap - 0.005)
+        assert len(got) == 2 and abs(abs(got[1] - got[0]) - gap) < 1e-6, (gap, got)
+    for v, x in FLOOR_CASES:
+        inside = x + 1.0 < 2.0 + max(4.0 * v, 25.0)
+        assert len(rec_of["floor", v, x]["calls"]["static"][2]) == int(inside), (v, x)
+    assert all(294 in rec_of[("hook",) + h]["lines"] and rec_of[("hook",) + h]["calls"]["dynamic"] == (SC.POINTS, "", [])
+               for h in HOOK_CASES)
+    out = SC.save_fixture(os.path.join(OUT, "spawn_rule_bodies.npz"), cases, records, hit & executable, executable)
+    stats = LIM.check_fixture(SC.load_fixture(os.path.join(OUT, "spawn_rule_bodies.npz")))
+    print("wrote spawn_rule_bodies.npz: cases", len(cases), "candidates", len(cands), stats,
+          "bytes", os.path.getsize(os.path.join(OUT, "spawn_rule_bodies.npz")))
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "relevant":     # only the relevant-lanelets fixture (own process: stub modules)
         gen_relevant_lanelets()
+    elif len(sys.argv) > 1 and sys.argv[1] == "rules":      # only the rule-bodies fixture (own process: stand-in modules)
+        gen_spawn_rule_bodies()
     elif len(sys.argv) > 1 and sys.argv[1] == "sampling":     # only the sampling-matrix fixture
         gen_sampling_matrix()
     elif len(sys.argv) > 1 and sys.argv[1] == "be":         # only the brake-evaluation fixture (own process: it replaces a module)

@@ -98,3 +98,22 @@ def test_ctypes_structures_have_the_layout_of_the_header(native, tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()
     assert [int(v) for v in out[:3]] == [C.sizeof(native.Step), C.sizeof(native.SpawnRuleParams), C.sizeof(native.RuleAgentTypes)]
     assert [int(v) for v in out[3:]] == [getattr(native.Step, f).offset for f in fields]
+
+
+def test_rule_checker_takes_nothing_from_the_product_but_the_spawn_point_record():
+    """oracle/fo_spawn_rules_ref.py judges the device's spawn rules: a helper shared with the product (curvature, arc length,
+    point in polygon) would put a defect of that helper on both sides of every comparison.  AST scan of every import in the
+    file, at any depth: from the product package at most ``SpawnPoint``"""
+    import ast
+    tree = ast.parse(open(os.path.join(ROOT, "oracle", "fo_spawn_rules_ref.py")).read())
+    taken, n_imports = [], 0
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Import):
+            n_imports += 1
+            taken += [(a.name, None) for a in node.names if a.name.split(".")[0] == "frenetix_occlusion"]
+        elif isinstance(node, ast.ImportFrom):
+            n_imports += 1
+            if node.level or (node.module or "").split(".")[0] == "frenetix_occlusion":
+                taken += [(node.module, a.name) for a in node.names]
+    assert n_imports >= 3
+    assert taken in ([], [("frenetix_occlusion.spawn_locator", "SpawnPoint")]), taken

@@ -231,6 +231,56 @@ def test_scenario1_steps(torch_cuda):
     assert n_pts > 0
 
 
+def test_device_returns_the_reference_decisions_on_every_recorded_scene(torch_cuda):
+    """tests/golden/spawn_rule_bodies.npz (the reference's own, unmodified rule methods over the build's discretisation,
+    ``gen_golden.py rules``) through ``SpawnLocator.find_spawn_points`` -> ``fo_scene_spawn_rules`` on every recorded scene,
+    the caller-frame cases with ``accelerator.spawn.frame: caller``: the device's cell classes reproduce the recorded counts of
+    road / visible / occluded cells, and the list is the reference's -- the same ordered (agent type, source), the same cell,
+    positions and cl_pos to 1e-9, orientations to 1e-12 (``_same``'s tolerances).  Scenes in which the reference raises are
+    only required to give a list.  Reads tests/golden/ only."""
+    import spawn_rule_cases as SC
+    from test_spawn_rule_bodies_cpu import compare
+    from frenetix_occlusion.sensor_model import SensorModel
+    from frenetix_occlusion.spawn_locator import SpawnLocator
+    from frenetix_occlusion.utils.fo_obstacle import FOObstacles
+    from oracle.fo_spawn_rules_ref import CellView
+    cases, _ = SC.load_fixture()
+    assert len(cases) >= 200
+    models, bad, worst, n_caller = {}, [], 0.0, 0
+    for k, (case, rec) in enumerate(cases):
+        key = (case.map_index, case.n_rays, case.cell_size)
+        if key not in models:
+            models[key] = SensorModel(case.lanelets, None, sensor_radius=SC.SENSOR_RADIUS, sensor_angle=360.0, n_rays=case.n_rays,
+                                      intersections=case.intersections, cell_size=case.cell_size)
+        sm = models[key]
+        obs = FOObstacles(case.obstacles)
+        obs.update(case.step)
+        sm.calc_visible_and_occluded_area(case.step, case.ego, case.yaw, obs)
+        cosy = SC.frame_of(case)
+        ego_cl = cosy.convert_to_curvilinear_coords(case.ego[0], case.ego[1])
+        am = SimpleNamespace(scenario=SimpleNamespace(intersections=case.intersections))
+        sl = SpawnLocator(am, case.path, case.cfg, sm, cosy_cl=cosy if case.frame else None, fo_obstacles=obs)
+        n_caller += case.frame
+        dev = list(sl.find_spawn_points(case.ego, case.yaw, ego_cl, case.v))
+        torch_cuda.cuda.synchronize()
+        view = CellView(sm.cell_class.cpu().numpy(), sm.window)
+        if not np.array_equal(SC.class_counts(view.cls), rec["counts"]):
+            bad.append(f"case {k}: class counts {SC.class_counts(view.cls)} != {rec['counts']}")
+        if rec["intention"] is not None and sl.last_intention != rec["intention"]:
+            bad.append(f"case {k}: intention {sl.last_intention} != {rec['intention']}")
+        if rec["calls"]["find"][0] == SC.RAISES:
+            continue                     # the reference raises here: the device continues (DESIGN.md section 6) and gave a list
+        why = compare(rec["calls"]["find"], dev, view)
+        if why:
+            bad.append(f"case {k} find: {why}")
+        for a, b in zip(SC.points_of(dev), rec["calls"]["find"][2]):
+            if a[:2] == b[:2]:
+                worst = max(worst, float(np.abs(a[2] - b[2]).max()))
+    print(f"recorded scenes {len(cases)}, through a caller's frame {n_caller}, largest position difference {worst:.3g} m")
+    assert n_caller >= 10
+    assert not bad, f"{len(bad)} differences, cases {sorted({int(b.split()[1].rstrip(':')) for b in bad})}:\n" + "\n".join(bad[:40])
+
+
 def _random_case(rng, scs):
     """one random case of tools/spawn_rules_fuzz.py: a scenario, an ego pose near a lanelet centre line, a reference path
     straight ahead or along the centre lines of the lanelet and its successors, a time step, a speed"""
