@@ -23,6 +23,7 @@
 //   fo_flag_compact_kernel deterministic stream compaction in one launch (ballot prefix inside a block, every block
 //                          sums the counts before it; fo_flag_scan/scatter for very large windows)
 //   fo_hr_*_kernel         hidden-traffic reach forecast, an extension outside the step (fo_hidden_reach.hpp)
+//   fo_hr_road_*_kernel    its road metric: distance bands along the road, arrival merge (fo_hidden_reach_road.hpp)
 //   fo_spawn_flag_kernel   candidate cells (+ block counts), fo_spawn_predict_kernel (evenly spaced pick + heading +
 //                          predictions in the sweep's agent layout)
 #include <hip/hip_runtime.h>
@@ -32,6 +33,7 @@
 #include "fo_prep_traj.hpp"
 #include "fo_agent_rows.hpp"
 #include "fo_hidden_reach.hpp"
+#include "fo_hidden_reach_road.hpp"
 
 namespace {
 
@@ -110,6 +112,8 @@ struct Scene {
   // hidden-traffic reach forecast (fo_scene_hidden_reach): row distances of the grown window, allocated by its first call
   uint8_t *d_hr_g = nullptr;
   size_t cap_hr_g = 0;
+  uint16_t *d_hr_dist = nullptr;        // ... and the road metric's distance map, when the caller hands in no buffer for it
+  size_t cap_hr_dist = 0;
 };
 
 Scene *scene_of(fo_ctx *ctx) {
@@ -1592,7 +1596,7 @@ extern "C" {
 void fo_scene_destroy_(fo_ctx *ctx) {
   if (!ctx || !ctx->scene) return;
   Scene *sc = (Scene *)ctx->scene;
-  void *ptrs[] = {sc->d_vis32, sc->d_flags, sc->d_blk, sc->d_flags2, sc->d_blk2, sc->d_cand, sc->d_ncand, sc->d_amb, sc->d_namb, sc->d_rule_rec, sc->d_rule_lab, sc->d_rule_cnt, sc->d_ofar, sc->d_hr_g};
+  void *ptrs[] = {sc->d_vis32, sc->d_flags, sc->d_blk, sc->d_flags2, sc->d_blk2, sc->d_cand, sc->d_ncand, sc->d_amb, sc->d_namb, sc->d_rule_rec, sc->d_rule_lab, sc->d_rule_cnt, sc->d_ofar, sc->d_hr_g, sc->d_hr_dist};
   for (void *p : ptrs)
     if (p) (void)hipFree(p);
   map_release(sc->map);
@@ -2019,47 +2023,52 @@ int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, 
   return launch_future_visibility(ctx, a, p->M, sector, fs, seen_bytes, stream);
 }
 
-int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
-  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_hidden_reach: call fo_scene_set_map first");
-  if (!p) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no parameters");
+// both metrics of the forecast: `road` adds the distance bands and the arrival merge between the map and the trajectories
+static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road, uint16_t *d_dist, const char *fn, void *stream) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
+  if (!p) return fo_fail(ctx, FO_E_ARG, "%s: no parameters", fn);
   Scene *sc = (Scene *)ctx->scene;
-  if (sc->map->P < 1 || !sc->map->d_raster) return fo_fail(ctx, FO_E_STATE, "fo_scene_hidden_reach: call fo_scene_set_map first");
+  if (sc->map->P < 1 || !sc->map->d_raster) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
   if (p->J < 1 || p->J > HR_MAX_J)
-    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: J = %d outside [1, %d] (arrival steps are bytes, 255 = never)", p->J, HR_MAX_J);
-  if (!p->h_r2) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no reach table h_r2 [J]");
-  if (!p->d_arrival) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no buffer for the arrival map (d_arrival is required)");
-  if (!p->d_cls) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: no cell classes (d_cls of the visibility stage)");
+    return fo_fail(ctx, FO_E_ARG, "%s: J = %d outside [1, %d] (arrival steps are bytes, 255 = never)", fn, p->J, HR_MAX_J);
+  if (!p->h_r2) return fo_fail(ctx, FO_E_ARG, "%s: no reach table h_r2 [J]", fn);
+  if (!p->d_arrival) return fo_fail(ctx, FO_E_ARG, "%s: no buffer for the arrival map (d_arrival is required)", fn);
+  if (!p->d_cls) return fo_fail(ctx, FO_E_ARG, "%s: no cell classes (d_cls of the visibility stage)", fn);
   if (p->win_nx < 1 || p->win_ny < 1 || p->win_nx > 32768 || p->win_ny > 32768)
-    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: window %d x %d outside [1, 32768]^2", p->win_nx, p->win_ny);
-  if (p->h_r2[0] < 0) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2[0] = %d is negative", p->h_r2[0]);
+    return fo_fail(ctx, FO_E_ARG, "%s: window %d x %d outside [1, 32768]^2", fn, p->win_nx, p->win_ny);
+  if (p->h_r2[0] < 0) return fo_fail(ctx, FO_E_ARG, "%s: h_r2[0] = %d is negative", fn, p->h_r2[0]);
   for (int j = 1; j < p->J; ++j)
     if (p->h_r2[j] < p->h_r2[j - 1])
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2 decreases at entry %d (%d after %d)", j, p->h_r2[j], p->h_r2[j - 1]);
+      return fo_fail(ctx, FO_E_ARG, "%s: h_r2 decreases at entry %d (%d after %d)", fn, j, p->h_r2[j], p->h_r2[j - 1]);
   constexpr int cap = FO_HIDDEN_REACH_MAX_HALO;
   const int r2max = p->h_r2[p->J - 1];
   if (r2max >= (cap + 1) * (cap + 1))
-    return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: h_r2[J-1] = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
-                   "(shorten the horizon or lower v_max; the reach is never cut short)", r2max, cap);
+    return fo_fail(ctx, FO_E_ARG, "%s: h_r2[J-1] = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
+                   "(shorten the horizon or lower v_max; the reach is never cut short)", fn, r2max, cap);
   int h = (int)sqrt((double)r2max);
   while (h * h > r2max) --h;
   while ((h + 1) * (h + 1) <= r2max) ++h;
-  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: M = %d", p->M);
+  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
   if (p->M > 0) {
     if (p->T < 1 || p->T > p->J)
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: T = %d outside [1, J = %d] (every sample needs its reach)", p->T, p->J);
+      return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, J = %d] (every sample needs its reach)", fn, p->T, p->J);
     if (!p->d_x || !p->d_y || !p->d_heading)
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0");
+      return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0", fn);
     if (!p->d_cells || !p->d_first || !p->d_slack)
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: d_cells [M][T], d_first [M] and d_slack [M] are required with M > 0");
+      return fo_fail(ctx, FO_E_ARG, "%s: d_cells [M][T], d_first [M] and d_slack [M] are required with M > 0", fn);
     const double ext = HR_MAX_EXTENT * sc->map->cs;   // (NaN fails every comparison)
     if (!(p->hl >= 0.0 && p->hl <= ext) || !(p->hw >= 0.0 && p->hw <= ext) || !(fabs(p->wb) <= ext))
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_hidden_reach: half extents outside [0, %g m] or |wb| above it (hl = %g, hw = %g, wb = %g; "
-                     "FO_HIDDEN_REACH_MAX_HALF_EXTENT = %d cells)", ext, p->hl, p->hw, p->wb, HR_MAX_EXTENT);
+      return fo_fail(ctx, FO_E_ARG, "%s: half extents outside [0, %g m] or |wb| above it (hl = %g, hw = %g, wb = %g; "
+                     "FO_HIDDEN_REACH_MAX_HALF_EXTENT = %d cells)", fn, ext, p->hl, p->hw, p->wb, HR_MAX_EXTENT);
   }
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int nx = p->win_nx, ny = p->win_ny;
   int rc;
   if ((rc = fo_reserve(ctx, &sc->d_hr_g, &sc->cap_hr_g, (size_t)(ny + 2 * h) * nx))) return rc;
+  if (road && !d_dist) {                // the caller does not want the distances: they live in a workspace of the context
+    if ((rc = fo_reserve(ctx, &sc->d_hr_dist, &sc->cap_hr_dist, (size_t)ny * nx))) return rc;
+    d_dist = sc->d_hr_dist;
+  }
   hipStream_t s = (hipStream_t)stream;
   HrMapArgs a{sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_cls, p->d_hidden_or_null,
               h, p->J, sc->d_hr_g, p->d_arrival};
@@ -2069,6 +2078,26 @@ int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream)
   hipLaunchKernelGGL(fo_hr_rows_kernel, dim3(ny + 2 * h), dim3(HR_THREADS), lds_rows, s, a);
   hipLaunchKernelGGL(fo_hr_cols_kernel, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
                      (size_t)(HR_TY + 2 * h) * HR_TX, s, a, r2);
+  if (road) {
+    HrR2 reach;                         // L[j] = isqrt(169 R2[j]): the reach in distance units (12 / 17 per step, 13 per cell)
+    for (int j = 0; j < HR_MAX_J; ++j) {
+      const int64_t v = (int64_t)169 * r2.v[j];
+      int64_t l = (int64_t)sqrt((double)v);
+      while (l * l > v) --l;
+      while ((l + 1) * (l + 1) <= v) ++l;
+      reach.v[j] = (int32_t)l;
+    }
+    const int lmax = reach.v[p->J - 1];
+    // a launch per band of B: fixed by the reach alone, nothing is read back (one launch also when the reach is 0: the sources)
+    const int bands = lmax > 0 ? (lmax + HRR_BAND - 1) / HRR_BAND : 1;
+    const dim3 tiles((nx + HRR_TILE - 1) / HRR_TILE, (ny + HRR_TILE - 1) / HRR_TILE);
+    for (int b = 1; b <= bands; ++b) {
+      const HrRoadBandArgs ba{a, d_dist, (b - 1) * HRR_BAND, b * HRR_BAND < lmax ? b * HRR_BAND : lmax};
+      hipLaunchKernelGGL(fo_hr_road_band_kernel, tiles, dim3(HR_THREADS), 0, s, ba);
+    }
+    const HrRoadArrivalArgs aa{p->d_cls, d_dist, p->d_arrival, nx * ny, p->J};
+    hipLaunchKernelGGL(fo_hr_road_arrival_kernel, dim3((nx * ny + HR_THREADS - 1) / HR_THREADS), dim3(HR_THREADS), 0, s, aa, reach);
+  }
   if (p->M > 0) {
     int G = 1;
     while (G < p->T && G < 64) G <<= 1;
@@ -2081,6 +2110,14 @@ int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream)
   }
   FO_HIP_TRY(ctx, hipGetLastError());
   return FO_OK;
+}
+
+int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
+  return hidden_reach_call(ctx, p, false, nullptr, "fo_scene_hidden_reach", stream);
+}
+
+int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream) {
+  return hidden_reach_call(ctx, p ? &p->base : nullptr, true, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_road", stream);
 }
 
 // fo_scene_spawn; at (fo_step_run): the prediction kernel also writes its slots' rows of the sweep's agent table, and the

@@ -34,6 +34,7 @@ EXPORTS = [
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
+    "fo_scene_hidden_reach_road",
 ]
 
 
@@ -92,6 +93,10 @@ class HiddenReach(C.Structure):         # fo_hidden_reach_t
                 ("h_r2", C.POINTER(C.c_int32)), ("d_cls", C.c_void_p), ("d_hidden_or_null", C.c_void_p),
                 ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
                 ("d_arrival", C.c_void_p), ("d_cells", C.c_void_p), ("d_first", C.c_void_p), ("d_slack", C.c_void_p)]
+
+
+class HiddenReachRoad(C.Structure):     # fo_hidden_reach_road_t
+    _fields_ = [("base", HiddenReach), ("d_dist_or_null", C.c_void_p)]
 
 
 SPAWN_CELLS, SPAWN_RULES, SPAWN_BOTH = 0, 1, 2
@@ -185,6 +190,7 @@ def load():
                                                + [C.c_int] * 3 + [ip, dp, vp])
     lib.fo_scene_future_visibility_ex.argtypes = [vp, C.POINTER(FutureVisibility), vp]
     lib.fo_scene_hidden_reach.argtypes = [vp, C.POINTER(HiddenReach), vp]
+    lib.fo_scene_hidden_reach_road.argtypes = [vp, C.POINTER(HiddenReachRoad), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -309,14 +309,16 @@ class FOInterface:
         out.slice_timesteps = slice_ts
         return out
 
-    def hidden_reach(self, trajectories, v_max=None, margin=None, inflate=0.0):
+    def hidden_reach(self, trajectories, v_max=None, margin=None, inflate=0.0, metric="euclid"):
         """EXTENSION, not part of the reference: where road users the ego cannot see may be during the planning horizon, and
         which candidate trajectories drive through such road (:meth:`SensorModel.hidden_reach`; returns its
         :class:`~frenetix_occlusion.sensor_model.HiddenReach`: ``arrival`` map, ``cells [M, T]``, ``first [M]``,
         ``slack [M]``).  ``trajectories`` as for :meth:`future_visibility`, sample k at ``k dt``; the footprint is the ego
         rectangle of ``vehicle_params`` grown by ``inflate`` (m).  ``v_max`` / ``margin`` default to
         ``accelerator.occlusion_memory``'s values, so that the forecast and the memory speak of the same road user; with the
-        memory enabled the sources are its hidden set of this step, otherwise all road that is not visible."""
+        memory enabled the sources are its hidden set of this step, otherwise all road that is not visible.  ``metric``:
+        "euclid" -- the reach is a disc around every hidden cell, also across what is not road -- or "road": no cell is reached
+        earlier than the distance along the road allows (hidden road behind a building block does not arrive through it)."""
         from .metrics.metric import trajectories_to_arrays
         from .sweep import _vehicle_tuple
         if self.timestep is None or self.sensor_model.window is None:
@@ -326,7 +328,8 @@ class FOInterface:
         vehicle = _vehicle_tuple(self.vehicle_params)[:3]      # length, width, wb_rear_axle
         return self.sensor_model.hidden_reach(arr["x"], arr["y"], arr["theta"], vehicle=vehicle,
                                               v_max=om["v_max"] if v_max is None else v_max,
-                                              margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate)
+                                              margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate,
+                                              metric=metric)
 
     def _update_time_step(self, timestep):
         self.timestep = timestep

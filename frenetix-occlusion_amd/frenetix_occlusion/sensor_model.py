@@ -264,6 +264,15 @@ def hidden_reach_r2(v_max, dt, margin, cell_size, J):
     return np.array([occlusion_memory_r2(v_max, j * float(dt), margin, cell_size) for j in range(int(J))], dtype=np.int32)
 
 
+def hidden_reach_road_units(r2):
+    """the reach table of the forecast's road metric: ``L[j] = isqrt(169 R2[j])`` -- the Euclidean reach in the
+    units of the road distance (12 per axis step, 17 per diagonal step, 13 per cell of Euclidean length), host int32 [J]"""
+    return np.array([math.isqrt(169 * int(v)) for v in r2], dtype=np.int32)
+
+
+HIDDEN_REACH_METRICS = ("euclid", "road")
+
+
 def unit_headings(theta):
     """(cos, sin) of the sample headings as a float64 host array [..., 2]: the ONE place the forecast's footprints get their
     rotation from (the device takes no sine or cosine; a checker is handed these numbers as data)"""
@@ -280,7 +289,10 @@ class HiddenReach:
     ``first [M]`` int32 -- the first such sample, -1 = none; ``slack [M]`` int32 -- min over samples and footprint cells of
     (arrival - k), ``SLACK_NONE`` where the trajectory meets no reachable cell (``slack <= 0`` iff ``first >= 0``).
     ``r2`` (host int32 [J]) is the reach table, ``heading`` the (cos, sin) [M, T, 2] the footprints were turned by,
-    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step."""
+    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step.  ``metric``: "euclid" (reach as
+    a disc around every hidden cell) or "road" (that, and no earlier than the distance along passable cells allows);
+    ``reach`` (host int32 [J]) is the table in road-distance units (:func:`hidden_reach_road_units`), ``road_dist [ny, nx]``
+    uint16 the road distance itself, 65535 = impassable or beyond ``reach[-1]`` (None for "euclid")."""
     arrival: torch.Tensor
     cells: torch.Tensor
     first: torch.Tensor
@@ -289,6 +301,9 @@ class HiddenReach:
     window: CellWindow
     heading: Optional[torch.Tensor] = None
     from_memory: bool = False
+    metric: str = "euclid"
+    reach: Optional[np.ndarray] = None
+    road_dist: Optional[torch.Tensor] = None
 
     SLACK_NONE = 2 ** 31 - 1
 
@@ -810,8 +825,9 @@ class SensorModel:
         return FutureVisibility(revealed, area, new, any_, slice_ts)
 
     # ---- extension, not part of the reference
-    def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None):
-        """Hidden-traffic reach forecast (``fo_scene_hidden_reach``); returns a :class:`HiddenReach`.  The kernels are queued
+    def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, metric="euclid"):
+        """Hidden-traffic reach forecast (``fo_scene_hidden_reach``, with ``metric="road"`` ``fo_scene_hidden_reach_road``:
+        hidden traffic arrives along the road, not through what is not road); returns a :class:`HiddenReach`.  The kernels are queued
         on the current stream and nobody waits for them; ``theta`` is turned into (cos, sin) on the HOST (:func:`unit_headings`:
         the device takes no sine or cosine), so a ``theta`` that lives on the device is first copied back, which waits for the
         stream -- hand ``theta`` over as a host array, as a planner's trajectory objects give it, to avoid that.
@@ -821,6 +837,8 @@ class SensorModel:
         A road user hidden now -- in the occlusion memory's hidden set when the memory ran this step, else anywhere on
         road that is not visible -- moves at up to ``v_max`` (m/s); ``margin`` (m, None = sqrt(2) cell sizes) as for the
         memory.  ``lengths [M]``: samples ``k >= lengths[m]`` of a ragged batch contribute nothing."""
+        if metric not in HIDDEN_REACH_METRICS:
+            raise ValueError(f"hidden_reach: metric {metric!r}, one of {HIDDEN_REACH_METRICS} is possible")
         if self.window is None:
             raise RuntimeError("hidden_reach needs the cell classes of a previous launch()")
         length, width, wb = (float(v) for v in tuple(vehicle)[:3])
@@ -866,9 +884,16 @@ class SensorModel:
                              J=T, h_r2=r2.ctypes.data_as(C.POINTER(C.c_int32)), d_cls=self.cell_class.data_ptr(),
                              d_hidden_or_null=p(hidden), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
                              d_arrival=arrival.data_ptr(), d_cells=p(cells), d_first=p(first), d_slack=p(slack))
-        self.ctx.call("fo_scene_hidden_reach", C.byref(args), N.current_stream(self._dev_index))
+        dist = None
+        if metric == "road":
+            dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev)
+            args = N.HiddenReachRoad(base=args, d_dist_or_null=dist.data_ptr())
+            self.ctx.call("fo_scene_hidden_reach_road", C.byref(args), N.current_stream(self._dev_index))
+        else:
+            self.ctx.call("fo_scene_hidden_reach", C.byref(args), N.current_stream(self._dev_index))
         self._hr_inputs = (tx, ty, heading, tlen)      # (stay referenced until the next call, as in future_visibility_ex)
-        return HiddenReach(arrival, cells, first, slack, r2, w, heading, hidden is not None)
+        return HiddenReach(arrival, cells, first, slack, r2, w, heading, hidden is not None, metric,
+                           hidden_reach_road_units(r2), dist)
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

@@ -306,7 +306,8 @@ int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, 
  *  Reach table h_r2 [J] (HOST memory, read before the call returns): R2[j] = floor((v_max j dt + margin)^2 / cs^2), the r2
  *   of fo_occlusion_memory_t for a step of j dt; non-decreasing, R2[0] >= 0.
  *  D2(g) = min over q with S(q) = 1 of (gx - qx)^2 + (gy - qy)^2, searched over the window grown by h = isqrt(R2[J-1]) cells
- *   on every side (nothing farther matters).  Euclidean, also across cells that are not road: an over-approximation.
+ *   on every side (nothing farther matters).  Euclidean, also across cells that are not road: an over-approximation;
+ *   fo_scene_hidden_reach_road below bounds it by the distance along the road.
  *  d_arrival [ny][nx] uint8: A(g) = min { j : D2(g) <= R2[j] } for a road cell (c & 1), 255 = not within the horizon or not
  *   road.  A cell outside the window counts as A = 0 if it is on the raster and road, else 255.
  *  Footprint of trajectory m at sample k (time k dt): the sweep's ego rectangle -- centre (x + wb c, y + wb s), half extents
@@ -346,6 +347,30 @@ typedef struct {
   int32_t *d_first, *d_slack;               /* [M] */
 } fo_hidden_reach_t;
 int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream);
+
+/* EXTENSION, not part of the reference: the same forecast with the ROAD metric (DESIGN.md §5.10 "Road metric") -- hidden traffic
+ * arrives along passable cells, not through a building block.  Everything of fo_scene_hidden_reach holds (arguments, outputs,
+ * limits, one call at a time per context); only the arrival map differs.  Integers only:
+ *  Passable P(q) = S(q) or road(q); road(q) = c & 1 inside the window, and outside it P = S (the raster's road bit, every
+ *   unobserved road cell being a source; off the raster 0).
+ *  d(g) = min over 8-connected cell paths q0 .. qn = g with S(q0) = 1 and every qi passable of the sum of step weights, 12 for
+ *   an axis step and 17 for a diagonal one (a diagonal step needs only its two end cells passable: the forecast must not
+ *   under-reach); d = 0 on sources.  12 dx + 5 dy <= 13 sqrt(dx^2 + dy^2): d / 13 never exceeds the Euclidean length of the
+ *   lattice path.
+ *  L[j] = isqrt(169 R2[j]), the reach in these units.  Distances beyond L[J-1] are not propagated.
+ *  A_geo(g) = min { j : d(g) <= L[j] } on road cells, 255 otherwise; d_arrival = max(A_geo, A of fo_scene_hidden_reach), 255
+ *   counting as later than every step: both over-approximate the same truth, the later arrival still does, and on open road
+ *   the two maps are equal.  d_cells, d_first, d_slack are computed from this map.
+ *  d_dist_or_null [win_ny][win_nx] uint16: d, 65535 = impassable or beyond L[J-1].  NULL: the distances stay in a workspace of
+ *   the context.
+ * Launches: the two of the Euclidean map, ceil(L[J-1] / 192) distance bands (at least one; at most 18), one merge, one for the
+ * trajectories with M > 0.  No launch waits for another workgroup, nothing is read back.  Refusals as fo_scene_hidden_reach,
+ * messages prefixed "fo_scene_hidden_reach_road:". */
+typedef struct {
+  fo_hidden_reach_t base;
+  uint16_t *d_dist_or_null;                 /* [win_ny][win_nx] d, 65535 = none */
+} fo_hidden_reach_road_t;
+int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream);
 
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least

@@ -2,7 +2,7 @@
 whole call, next to the visibility stage the forecast
 follows and the 720-ray first-seen future-visibility call on the same batch.
 
-    python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25]
+    python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -44,6 +44,7 @@ def main():
     ap.add_argument("--steps", type=int, default=5, help="steps of the drive before the timed calls")
     ap.add_argument("--v-max", type=float, default=13.9)
     ap.add_argument("--calls", type=int, default=25)
+    ap.add_argument("--metric", default="euclid", choices=("euclid", "road"), help="road: the reach follows the road (§5.10)")
     a = ap.parse_args()
     if a.scene == "city_grid":
         sc = SC.synthetic_urban_grid()
@@ -70,19 +71,22 @@ def main():
         sm.launch(ego, yaw, timestep=step_no[0])
         step_no[0] += 1
 
-    res = {"scene": a.scene, "M": M, "T": T, "memory": bool(a.memory), "window": [sm.window.nx, sm.window.ny],
+    res = {"scene": a.scene, "metric": a.metric, "M": M, "T": T, "memory": bool(a.memory), "window": [sm.window.nx, sm.window.ny],
            "build": N.build_id()[:12], "device": torch.cuda.get_device_name(0)}
     res["visibility_stage_ms"] = _median_ms(stage, a.calls)
-    out = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1)
+    out = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric)
     res["halo_cells"] = int(math.isqrt(int(out.r2[-1])))
-    res["map_only_ms"] = _median_ms(lambda: sm.hidden_reach(e, e, e, vehicle=veh, v_max=a.v_max, dt=0.1), a.calls)
-    res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1), a.calls)
+    res["map_only_ms"] = _median_ms(lambda: sm.hidden_reach(e, e, e, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric), a.calls)
+    res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric), a.calls)
     res["future_visibility_720_first_seen_ms"] = _median_ms(
         lambda: sm.future_visibility_ex(tx, ty, None, t_stride=5, n_rays=720, first_seen=True), a.calls)
     torch.cuda.synchronize()
     first = out.first.cpu().numpy()
     res["trajectories_meeting_hidden_traffic"] = int((first >= 0).sum())
     res["arrival_cells_reached"] = int((out.arrival.cpu().numpy() != 255).sum())
+    if a.metric == "road":
+        res["road_reach_units"] = int(out.reach[-1])
+        res["road_cells_within_reach"] = int((out.road_dist.cpu().numpy() != 65535).sum())
     print(json.dumps(res))
 
 
