@@ -19,9 +19,12 @@
 //                          rectangle's bounding box (one cell of slack: the float64 point-in-rectangle test decides) and
 //                          looks their arrival step up; first / slack are shuffle reductions over the G lanes
 // No atomics, no float arithmetic outside the footprint test, every output written with plain vector stores.
+// Two pieces are shared with the clearance (fo_hidden_clearance.hpp): fo_hr_cols_kernel is a template whose second instantiation
+// stores 169 D2 in place of the arrival step, and the footprint scan of the trajectory kernel is the function fo_hr_scan_footprint.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "fo_hip.h"
 
 namespace {
@@ -91,15 +94,29 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_rows_kernel(const HrMapArgs 
   }
 }
 
+struct HrKeyOut {                       // what the clearance's instantiation of the column pass takes in place of the table
+  int32_t r2_cap;
+  int32_t *key;                         // [ny][nx]: 169 D2 on road cells with D2 <= r2_cap, INT32_MAX elsewhere
+};
+
+// The column pass.  Two instantiations: Out = HrR2, the arrival map (binary search of R2[]), and Out = HrKeyOut, the key map
+// of fo_hidden_clearance.hpp (169 D2 itself, no table).
+// s_r2, J, out (table path) and kout (key path) stay declared at function scope although each instantiation uses only its own:
+// written so, Out = HrR2 compiles to the instructions fo_hr_cols_kernel had before it became a template (compared in the
+// gfx950 assembly); moving them into the `if constexpr` branches changes its register allocation.  The unused ones are removed
+// by the compiler (HrKeyOut: no static LDS).
 // dynamic LDS: (HR_TY + 2h) * HR_TX bytes
-__global__ __launch_bounds__(HR_THREADS) void fo_hr_cols_kernel(const HrMapArgs a, const HrR2 r2) {
+template <class Out>
+__global__ __launch_bounds__(HR_THREADS) void fo_hr_cols_kernel(const HrMapArgs a, const Out r2) {
+  constexpr bool KEY = !std::is_same<Out, HrR2>::value;
   extern __shared__ uint8_t hr_tile[];
-  __shared__ int32_t s_r2[HR_MAX_J];
+  __shared__ int32_t s_r2[KEY ? 1 : HR_MAX_J];
   const int tid = threadIdx.x, lane = tid & 63, h = a.h, J = a.J;
   const int x0 = blockIdx.x * HR_TX, y0 = blockIdx.y * HR_TY;
   const int rows = HR_TY + 2 * h;                   // grown rows y0 .. y0 + rows - 1 = window rows y0 - h .. y0 + HR_TY - 1 + h
   const int grows = a.ny + 2 * h;
-  for (int t = tid; t < J; t += HR_THREADS) s_r2[t] = r2.v[t];
+  if constexpr (!KEY)
+    for (int t = tid; t < J; t += HR_THREADS) s_r2[t] = r2.v[t];
   for (int t = tid; t < rows * HR_TX; t += HR_THREADS) {
     const int r = t >> 6, x = x0 + (t & 63);
     hr_tile[t] = (x < a.nx && y0 + r < grows) ? a.g[(size_t)(y0 + r) * a.nx + x] : (uint8_t)(h + 1);
@@ -107,12 +124,14 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_cols_kernel(const HrMapArgs 
   __syncthreads();
   const int x = x0 + lane;
   if (x >= a.nx) return;
-  const int r2max = s_r2[J - 1];
+  int r2max;
+  if constexpr (KEY) r2max = r2.r2_cap; else r2max = s_r2[J - 1];
   for (int ty = tid >> 6; ty < HR_TY; ty += HR_THREADS / 64) {
     const int y = y0 + ty;
     if (y >= a.ny) break;
     const size_t i = (size_t)y * a.nx + x;
     uint8_t out = 255;
+    int32_t kout = 0x7fffffff;
     if (a.cls[i] & 1) {
       const uint8_t *col = hr_tile + (ty + h) * HR_TX + lane;   // G(x, y)
       int best = (int)col[0] * (int)col[0];
@@ -122,16 +141,20 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_cols_kernel(const HrMapArgs 
         best = best < v0 ? best : v0;
         best = best < v1 ? best : v1;
       }
-      if (best <= r2max) {      // first j with D2 <= R2[j] (R2 is non-decreasing)
-        int lo = 0, hi = J - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi) >> 1;
-          if (best <= s_r2[mid]) hi = mid; else lo = mid + 1;
+      if (best <= r2max) {
+        if constexpr (KEY) {
+          kout = 169 * best;
+        } else {                // first j with D2 <= R2[j] (R2 is non-decreasing)
+          int lo = 0, hi = J - 1;
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (best <= s_r2[mid]) hi = mid; else lo = mid + 1;
+          }
+          out = (uint8_t)lo;
         }
-        out = (uint8_t)lo;
       }
     }
-    a.arrival[i] = out;
+    if constexpr (KEY) r2.key[i] = kout; else a.arrival[i] = out;
   }
 }
 
@@ -147,6 +170,45 @@ struct HrTrajArgs {
   const uint8_t *arrival;               // [ny][nx]
   int32_t *cells, *first, *slack;       // [M][T], [M], [M]
 };
+
+// The footprint of pose i of the trajectory arrays of `a` (HrTrajArgs, or the clearance's arguments: the same field names):
+// every world-raster cell of the rectangle's bounding box (one cell of slack, clipped to [lox, hix] x [loy, hiy]) whose centre
+// passes the float64 point-in-rectangle test gets f(v), v = map[cell] inside the window, outside it 0 on raster road and
+// `none` elsewhere.  The ONE statement of the test on the device: the reach and the clearance kernel both scan with it.
+template <class Args, class V, class F>
+__device__ __forceinline__ void fo_hr_scan_footprint(const Args &a, size_t i, const V *__restrict__ map, int none, int lox, int loy,
+                                                     int hix, int hiy, F &&f) {
+  const double c = a.heading[2 * i], s = a.heading[2 * i + 1];
+  const double cx = a.x[i] + a.wb * c, cy = a.y[i] + a.wb * s;
+  const double bx = fabs(c) * a.hl + fabs(s) * a.hw, by = fabs(s) * a.hl + fabs(c) * a.hw;
+  const double fx0 = (cx - bx - a.rx0) / a.cs - 0.5, fx1 = (cx + bx - a.rx0) / a.cs - 0.5;
+  const double fy0 = (cy - by - a.ry0) / a.cs - 0.5, fy1 = (cy + by - a.ry0) / a.cs - 0.5;
+  // NaN compares false: such a pose gets the empty range
+  int gx0 = lox, gx1 = lox - 1, gy0 = loy, gy1 = loy - 1;
+  if (fx0 <= (double)hix && fx1 >= (double)lox && fy0 <= (double)hiy && fy1 >= (double)loy) {
+    gx0 = fx0 > (double)lox ? (int)floor(fx0) - 1 : lox;
+    gx1 = fx1 < (double)hix ? (int)ceil(fx1) + 1 : hix;
+    gy0 = fy0 > (double)loy ? (int)floor(fy0) - 1 : loy;
+    gy1 = fy1 < (double)hiy ? (int)ceil(fy1) + 1 : hiy;
+    gx0 = gx0 < lox ? lox : gx0; gx1 = gx1 > hix ? hix : gx1;
+    gy0 = gy0 < loy ? loy : gy0; gy1 = gy1 > hiy ? hiy : gy1;
+  }
+  for (int gy = gy0; gy <= gy1; ++gy) {
+    const double ey = (a.ry0 + ((double)gy + 0.5) * a.cs) - cy;
+    const int wy = gy - a.iy0;
+    const bool row_in = wy >= 0 && wy < a.ny, row_on = gy >= 0 && gy < a.rny;
+    for (int gx = gx0; gx <= gx1; ++gx) {
+      const double ex = (a.rx0 + ((double)gx + 0.5) * a.cs) - cx;
+      const double u = ex * c + ey * s, w = ey * c - ex * s;
+      if (!(fabs(u) <= a.hl && fabs(w) <= a.hw)) continue;
+      const int wx = gx - a.ix0;
+      int v = none;
+      if (row_in && wx >= 0 && wx < a.nx) v = map[wy * a.nx + wx];
+      else if (row_on && gx >= 0 && gx < a.rnx) v = a.raster[(size_t)gy * a.rnx + gx] ? 0 : none;
+      f(v);
+    }
+  }
+}
 
 __global__ __launch_bounds__(HR_THREADS) void fo_hr_traj_kernel(const HrTrajArgs a) {
   const uint8_t *__restrict__ A = a.arrival;   // read through the caches (staged in LDS it was 3.7 x slower)
@@ -166,41 +228,13 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_traj_kernel(const HrTrajArgs
   for (int k = kl; k < a.T; k += G) {
     int n = 0;
     if (live && k < Lm) {
-      const size_t i = (size_t)m * a.T + k;
-      const double c = a.heading[2 * i], s = a.heading[2 * i + 1];
-      const double cx = a.x[i] + a.wb * c, cy = a.y[i] + a.wb * s;
-      const double bx = fabs(c) * a.hl + fabs(s) * a.hw, by = fabs(s) * a.hl + fabs(c) * a.hw;
-      const double fx0 = (cx - bx - a.rx0) / a.cs - 0.5, fx1 = (cx + bx - a.rx0) / a.cs - 0.5;
-      const double fy0 = (cy - by - a.ry0) / a.cs - 0.5, fy1 = (cy + by - a.ry0) / a.cs - 0.5;
-      // NaN compares false: such a pose gets the empty range
-      int gx0 = lox, gx1 = lox - 1, gy0 = loy, gy1 = loy - 1;
-      if (fx0 <= (double)hix && fx1 >= (double)lox && fy0 <= (double)hiy && fy1 >= (double)loy) {
-        gx0 = fx0 > (double)lox ? (int)floor(fx0) - 1 : lox;
-        gx1 = fx1 < (double)hix ? (int)ceil(fx1) + 1 : hix;
-        gy0 = fy0 > (double)loy ? (int)floor(fy0) - 1 : loy;
-        gy1 = fy1 < (double)hiy ? (int)ceil(fy1) + 1 : hiy;
-        gx0 = gx0 < lox ? lox : gx0; gx1 = gx1 > hix ? hix : gx1;
-        gy0 = gy0 < loy ? loy : gy0; gy1 = gy1 > hiy ? hiy : gy1;
-      }
-      for (int gy = gy0; gy <= gy1; ++gy) {
-        const double ey = (a.ry0 + ((double)gy + 0.5) * a.cs) - cy;
-        const int wy = gy - a.iy0;
-        const bool row_in = wy >= 0 && wy < a.ny, row_on = gy >= 0 && gy < a.rny;
-        for (int gx = gx0; gx <= gx1; ++gx) {
-          const double ex = (a.rx0 + ((double)gx + 0.5) * a.cs) - cx;
-          const double u = ex * c + ey * s, w = ey * c - ex * s;
-          if (!(fabs(u) <= a.hl && fabs(w) <= a.hw)) continue;
-          const int wx = gx - a.ix0;
-          int av = 255;
-          if (row_in && wx >= 0 && wx < a.nx) av = A[wy * a.nx + wx];
-          else if (row_on && gx >= 0 && gx < a.rnx) av = a.raster[(size_t)gy * a.rnx + gx] ? 0 : 255;
-          if (av != 255) {
-            const int d = av - k;
-            slack = slack < d ? slack : d;
-            n += av <= k;
-          }
+      fo_hr_scan_footprint(a, (size_t)m * a.T + k, A, 255, lox, loy, hix, hiy, [&](int av) {
+        if (av != 255) {
+          const int d = av - k;
+          slack = slack < d ? slack : d;
+          n += av <= k;
         }
-      }
+      });
       if (n > 0 && k < first) first = k;
     }
     if (live) a.cells[(size_t)m * a.T + k] = n;

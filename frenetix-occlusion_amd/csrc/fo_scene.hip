@@ -24,6 +24,7 @@
 //                          sums the counts before it; fo_flag_scan/scatter for very large windows)
 //   fo_hr_*_kernel         hidden-traffic reach forecast, an extension outside the step (fo_hidden_reach.hpp)
 //   fo_hr_road_*_kernel    its road metric: distance bands along the road, arrival merge (fo_hidden_reach_road.hpp)
+//   fo_hc_*_kernel         hidden-traffic clearance: the key map behind every reach table, its minimum per pose (fo_hidden_clearance.hpp)
 //   fo_spawn_flag_kernel   candidate cells (+ block counts), fo_spawn_predict_kernel (evenly spaced pick + heading +
 //                          predictions in the sweep's agent layout)
 #include <hip/hip_runtime.h>
@@ -34,6 +35,7 @@
 #include "fo_agent_rows.hpp"
 #include "fo_hidden_reach.hpp"
 #include "fo_hidden_reach_road.hpp"
+#include "fo_hidden_clearance.hpp"
 
 namespace {
 
@@ -2023,6 +2025,35 @@ int fo_scene_future_visibility_ex(fo_ctx *ctx, const fo_future_visibility_t *p, 
   return launch_future_visibility(ctx, a, p->M, sector, fs, seen_bytes, stream);
 }
 
+// floor(sqrt(v)) in integers (the halo h of a reach R2, the reach in road-distance units L of 169 R2)
+static int64_t hr_isqrt(int64_t v) {
+  int64_t l = (int64_t)sqrt((double)v);
+  while (l * l > v) --l;
+  while ((l + 1) * (l + 1) <= v) ++l;
+  return l;
+}
+
+// first half of the distance transform, for the forecast and the clearance alike: the workspace of the row distances and the rows launch
+static int hr_launch_rows(fo_ctx *ctx, Scene *sc, const HrMapArgs &a, hipStream_t s) {
+  if (int rc = fo_reserve(ctx, &sc->d_hr_g, &sc->cap_hr_g, (size_t)(a.ny + 2 * a.h) * a.nx)) return rc;
+  HrMapArgs m = a;
+  m.g = sc->d_hr_g;
+  const size_t lds_rows = (size_t)((a.nx + 2 * a.h + 63) / 64) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(fo_hr_rows_kernel, dim3(a.ny + 2 * a.h), dim3(HR_THREADS), lds_rows, s, m);
+  return FO_OK;
+}
+
+// the road distance up to lmax: a launch per band of B, fixed by the reach alone, nothing is read back (one launch also when the
+// reach is 0: the sources)
+static void hr_launch_bands(const HrMapArgs &a, uint16_t *d_dist, int lmax, hipStream_t s) {
+  const int bands = lmax > 0 ? (lmax + HRR_BAND - 1) / HRR_BAND : 1;
+  const dim3 tiles((a.nx + HRR_TILE - 1) / HRR_TILE, (a.ny + HRR_TILE - 1) / HRR_TILE);
+  for (int b = 1; b <= bands; ++b) {
+    const HrRoadBandArgs ba{a, d_dist, (b - 1) * HRR_BAND, b * HRR_BAND < lmax ? b * HRR_BAND : lmax};
+    hipLaunchKernelGGL(fo_hr_road_band_kernel, tiles, dim3(HR_THREADS), 0, s, ba);
+  }
+}
+
 // both metrics of the forecast: `road` adds the distance bands and the arrival merge between the map and the trajectories
 static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road, uint16_t *d_dist, const char *fn, void *stream) {
   if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
@@ -2045,9 +2076,7 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
   if (r2max >= (cap + 1) * (cap + 1))
     return fo_fail(ctx, FO_E_ARG, "%s: h_r2[J-1] = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
                    "(shorten the horizon or lower v_max; the reach is never cut short)", fn, r2max, cap);
-  int h = (int)sqrt((double)r2max);
-  while (h * h > r2max) --h;
-  while ((h + 1) * (h + 1) <= r2max) ++h;
+  const int h = (int)hr_isqrt(r2max);
   if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
   if (p->M > 0) {
     if (p->T < 1 || p->T > p->J)
@@ -2064,37 +2093,23 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int nx = p->win_nx, ny = p->win_ny;
   int rc;
-  if ((rc = fo_reserve(ctx, &sc->d_hr_g, &sc->cap_hr_g, (size_t)(ny + 2 * h) * nx))) return rc;
   if (road && !d_dist) {                // the caller does not want the distances: they live in a workspace of the context
     if ((rc = fo_reserve(ctx, &sc->d_hr_dist, &sc->cap_hr_dist, (size_t)ny * nx))) return rc;
     d_dist = sc->d_hr_dist;
   }
   hipStream_t s = (hipStream_t)stream;
   HrMapArgs a{sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_cls, p->d_hidden_or_null,
-              h, p->J, sc->d_hr_g, p->d_arrival};
+              h, p->J, nullptr, p->d_arrival};
+  if ((rc = hr_launch_rows(ctx, sc, a, s))) return rc;
+  a.g = sc->d_hr_g;
   HrR2 r2;
   for (int j = 0; j < HR_MAX_J; ++j) r2.v[j] = p->h_r2[j < p->J ? j : p->J - 1];
-  const size_t lds_rows = (size_t)((nx + 2 * h + 63) / 64) * sizeof(unsigned long long);
-  hipLaunchKernelGGL(fo_hr_rows_kernel, dim3(ny + 2 * h), dim3(HR_THREADS), lds_rows, s, a);
-  hipLaunchKernelGGL(fo_hr_cols_kernel, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
+  hipLaunchKernelGGL(fo_hr_cols_kernel<HrR2>, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
                      (size_t)(HR_TY + 2 * h) * HR_TX, s, a, r2);
   if (road) {
     HrR2 reach;                         // L[j] = isqrt(169 R2[j]): the reach in distance units (12 / 17 per step, 13 per cell)
-    for (int j = 0; j < HR_MAX_J; ++j) {
-      const int64_t v = (int64_t)169 * r2.v[j];
-      int64_t l = (int64_t)sqrt((double)v);
-      while (l * l > v) --l;
-      while ((l + 1) * (l + 1) <= v) ++l;
-      reach.v[j] = (int32_t)l;
-    }
-    const int lmax = reach.v[p->J - 1];
-    // a launch per band of B: fixed by the reach alone, nothing is read back (one launch also when the reach is 0: the sources)
-    const int bands = lmax > 0 ? (lmax + HRR_BAND - 1) / HRR_BAND : 1;
-    const dim3 tiles((nx + HRR_TILE - 1) / HRR_TILE, (ny + HRR_TILE - 1) / HRR_TILE);
-    for (int b = 1; b <= bands; ++b) {
-      const HrRoadBandArgs ba{a, d_dist, (b - 1) * HRR_BAND, b * HRR_BAND < lmax ? b * HRR_BAND : lmax};
-      hipLaunchKernelGGL(fo_hr_road_band_kernel, tiles, dim3(HR_THREADS), 0, s, ba);
-    }
+    for (int j = 0; j < HR_MAX_J; ++j) reach.v[j] = (int32_t)hr_isqrt((int64_t)169 * r2.v[j]);
+    hr_launch_bands(a, d_dist, reach.v[p->J - 1], s);
     const HrRoadArrivalArgs aa{p->d_cls, d_dist, p->d_arrival, nx * ny, p->J};
     hipLaunchKernelGGL(fo_hr_road_arrival_kernel, dim3((nx * ny + HR_THREADS - 1) / HR_THREADS), dim3(HR_THREADS), 0, s, aa, reach);
   }
@@ -2118,6 +2133,67 @@ int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream)
 
 int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream) {
   return hidden_reach_call(ctx, p ? &p->base : nullptr, true, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_road", stream);
+}
+
+// the clearance: the distance transform and the distance bands of the reach, run to a cap in place of a table's end
+int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_clearance";
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
+  if (!p) return fo_fail(ctx, FO_E_ARG, "%s: no parameters", fn);
+  Scene *sc = (Scene *)ctx->scene;
+  if (sc->map->P < 1 || !sc->map->d_raster) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
+  if (p->metric != FO_HIDDEN_CLEARANCE_EUCLID && p->metric != FO_HIDDEN_CLEARANCE_ROAD)
+    return fo_fail(ctx, FO_E_ARG, "%s: metric = %d (0 euclid, 1 road)", fn, p->metric);
+  if (!p->d_key) return fo_fail(ctx, FO_E_ARG, "%s: no buffer for the key map (d_key is required)", fn);
+  if (!p->d_cls) return fo_fail(ctx, FO_E_ARG, "%s: no cell classes (d_cls of the visibility stage)", fn);
+  if (p->win_nx < 1 || p->win_ny < 1 || p->win_nx > 32768 || p->win_ny > 32768)
+    return fo_fail(ctx, FO_E_ARG, "%s: window %d x %d outside [1, 32768]^2", fn, p->win_nx, p->win_ny);
+  if (p->r2_cap < 0) return fo_fail(ctx, FO_E_ARG, "%s: r2_cap = %d is negative", fn, p->r2_cap);
+  constexpr int cap = FO_HIDDEN_REACH_MAX_HALO;
+  if (p->r2_cap >= (cap + 1) * (cap + 1))
+    return fo_fail(ctx, FO_E_ARG, "%s: r2_cap = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
+                   "(shorten the horizon or lower v_cap; the reach is never cut short)", fn, p->r2_cap, cap);
+  const int h = (int)hr_isqrt(p->r2_cap);
+  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
+  if (p->M > 0) {
+    if (p->T < 1) return fo_fail(ctx, FO_E_ARG, "%s: T = %d (at least one sample with M > 0)", fn, p->T);
+    if (!p->d_x || !p->d_y || !p->d_heading)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0", fn);
+    if (!p->d_qmin) return fo_fail(ctx, FO_E_ARG, "%s: d_qmin [M][T] is required with M > 0", fn);
+    const double ext = HR_MAX_EXTENT * sc->map->cs;   // (NaN fails every comparison)
+    if (!(p->hl >= 0.0 && p->hl <= ext) || !(p->hw >= 0.0 && p->hw <= ext) || !(fabs(p->wb) <= ext))
+      return fo_fail(ctx, FO_E_ARG, "%s: half extents outside [0, %g m] or |wb| above it (hl = %g, hw = %g, wb = %g; "
+                     "FO_HIDDEN_REACH_MAX_HALF_EXTENT = %d cells)", fn, ext, p->hl, p->hw, p->wb, HR_MAX_EXTENT);
+  }
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int nx = p->win_nx, ny = p->win_ny;
+  const bool road = p->metric == FO_HIDDEN_CLEARANCE_ROAD;
+  uint16_t *d_dist = p->d_dist_or_null;
+  int rc;
+  if (road && !d_dist) {
+    if ((rc = fo_reserve(ctx, &sc->d_hr_dist, &sc->cap_hr_dist, (size_t)ny * nx))) return rc;
+    d_dist = sc->d_hr_dist;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  HrMapArgs a{sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_cls, p->d_hidden_or_null,
+              h, 0, nullptr, nullptr};
+  if ((rc = hr_launch_rows(ctx, sc, a, s))) return rc;
+  a.g = sc->d_hr_g;
+  hipLaunchKernelGGL(fo_hr_cols_kernel<HrKeyOut>, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
+                     (size_t)(HR_TY + 2 * h) * HR_TX, s, a, HrKeyOut{p->r2_cap, p->d_key});
+  if (road) {
+    hr_launch_bands(a, d_dist, (int)hr_isqrt((int64_t)169 * p->r2_cap), s);       // to Lcap = isqrt(169 r2_cap)
+    const HcMergeArgs ma{d_dist, p->d_key, nx * ny};
+    hipLaunchKernelGGL(fo_hc_road_merge_kernel, dim3((nx * ny + HR_THREADS - 1) / HR_THREADS), dim3(HR_THREADS), 0, s, ma);
+  }
+  if (p->M > 0) {
+    HcTrajArgs t{p->M, p->T, p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0,
+                 sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, nx, ny, p->d_key, p->d_qmin};
+    const size_t poses = (size_t)p->M * p->T;
+    hipLaunchKernelGGL(fo_hc_traj_kernel, dim3((unsigned)((poses + HR_THREADS - 1) / HR_THREADS)), dim3(HR_THREADS), 0, s, t);
+  }
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
 }
 
 // fo_scene_spawn; at (fo_step_run): the prediction kernel also writes its slots' rows of the sweep's agent table, and the

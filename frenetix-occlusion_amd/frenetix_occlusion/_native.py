@@ -34,7 +34,7 @@ EXPORTS = [
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
-    "fo_scene_hidden_reach_road",
+    "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance",
 ]
 
 
@@ -97,6 +97,18 @@ class HiddenReach(C.Structure):         # fo_hidden_reach_t
 
 class HiddenReachRoad(C.Structure):     # fo_hidden_reach_road_t
     _fields_ = [("base", HiddenReach), ("d_dist_or_null", C.c_void_p)]
+
+
+HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
+HIDDEN_CLEARANCE_METRIC = {"euclid": 0, "road": 1}   # FO_HIDDEN_CLEARANCE_EUCLID / _ROAD
+
+
+class HiddenClearance(C.Structure):     # fo_hidden_clearance_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                ("r2_cap", C.c_int32), ("metric", C.c_int32), ("d_cls", C.c_void_p), ("d_hidden_or_null", C.c_void_p),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("d_key", C.c_void_p), ("d_qmin", C.c_void_p), ("d_dist_or_null", C.c_void_p)]
 
 
 SPAWN_CELLS, SPAWN_RULES, SPAWN_BOTH = 0, 1, 2
@@ -191,6 +203,7 @@ def load():
     lib.fo_scene_future_visibility_ex.argtypes = [vp, C.POINTER(FutureVisibility), vp]
     lib.fo_scene_hidden_reach.argtypes = [vp, C.POINTER(HiddenReach), vp]
     lib.fo_scene_hidden_reach_road.argtypes = [vp, C.POINTER(HiddenReachRoad), vp]
+    lib.fo_scene_hidden_clearance.argtypes = [vp, C.POINTER(HiddenClearance), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -331,6 +331,25 @@ class FOInterface:
                                               margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate,
                                               metric=metric)
 
+    def hidden_clearance(self, trajectories, v_cap=None, margin=None, inflate=0.0, metric="euclid"):
+        """EXTENSION, not part of the reference: one device pass that answers :meth:`hidden_reach` for every hidden-user speed
+        up to ``v_cap`` and grades each candidate by the slowest hidden road user that could meet it
+        (:meth:`SensorModel.hidden_clearance`; returns its :class:`~frenetix_occlusion.sensor_model.HiddenClearance`: ``key``
+        map, ``qmin [M, T]``, ``.reach(v_max)`` -> (hit, first, slack), ``.critical_speed()`` -> ``[M]`` m/s).  Arguments and
+        defaults as for :meth:`hidden_reach` (``v_cap`` / ``margin``: ``accelerator.occlusion_memory``'s values).  How many
+        footprint cells are reached is not part of the result."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_clearance needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vehicle = _vehicle_tuple(self.vehicle_params)[:3]      # length, width, wb_rear_axle
+        return self.sensor_model.hidden_clearance(arr["x"], arr["y"], arr["theta"], vehicle=vehicle,
+                                                  v_cap=om["v_max"] if v_cap is None else v_cap,
+                                                  margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                  inflate=inflate, metric=metric)
+
     def _update_time_step(self, timestep):
         self.timestep = timestep
         self.sensor_model.timestep = timestep

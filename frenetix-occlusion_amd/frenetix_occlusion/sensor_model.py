@@ -308,6 +308,88 @@ class HiddenReach:
     SLACK_NONE = 2 ** 31 - 1
 
 
+@dataclass
+class HiddenClearance:
+    """what :meth:`SensorModel.hidden_clearance` returns (device tensors; DESIGN.md §5.10 "Clearance and critical speed"):
+    ``key [ny, nx]`` int32 over ``window`` -- ``169 D2`` ("euclid") or ``max(169 D2, d^2)`` ("road") on road cells within the cap,
+    ``NONE`` = INT32_MAX elsewhere; ``qmin [M, T]`` int32 -- the minimum of ``key`` over the ego rectangle at sample k, ``NONE``
+    where the footprint holds no road cell within the cap and for ``k >= lengths[m]``; ``dist [ny, nx]`` uint16 the road
+    distance (65535 = impassable or beyond ``isqrt(169 r2_cap)``; None for "euclid"); ``heading`` the (cos, sin) [M, T, 2] the
+    footprints were turned by (hand it to a later call of the same candidates as ``heading=``); ``r2_cap`` the cap in squared
+    cells: every reach table whose last entry is ``<= r2_cap`` is served.  ``dt``, ``margin``, ``cell_size`` are what the
+    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set.
+
+    For any such table ``A(g) <= j`` iff ``key(g) <= 169 R2[j]``, so ``cells > 0``, ``first`` and ``slack`` of
+    :meth:`SensorModel.hidden_reach` follow from ``qmin`` alone (:meth:`reach`).  The COUNT ``cells[m, k]`` itself does not:
+    ``qmin`` keeps the nearest footprint cell, not how many there are."""
+    key: torch.Tensor
+    qmin: torch.Tensor
+    dist: Optional[torch.Tensor]
+    window: CellWindow
+    heading: Optional[torch.Tensor]
+    r2_cap: int
+    metric: str = "euclid"
+    dt: float = 0.1
+    margin: float = 0.0
+    cell_size: float = 0.5
+    from_memory: bool = False
+
+    NONE = 2 ** 31 - 1
+    SLACK_NONE = 2 ** 31 - 1
+
+    def reach(self, v_max):
+        """``(hit [M, T] bool, first [M] int32, slack [M] int32)`` for a hidden road user of up to ``v_max`` m/s: ``hit`` is
+        ``cells > 0`` of ``hidden_reach(v_max=v_max)`` with the same metric, margin and ``dt``, ``first`` and ``slack`` are its
+        ``first`` and ``slack``, exactly.  Torch ops on the tensors' device, nothing is read back.  ValueError when the table
+        of ``v_max`` ends beyond ``r2_cap``."""
+        M, T = (int(v) for v in self.qmin.shape)
+        v_max = float(v_max)
+        if not v_max >= 0.0:
+            raise ValueError("reach: v_max >= 0")
+        r2 = hidden_reach_r2(v_max, self.dt, self.margin, self.cell_size, T)
+        if T and int(r2[-1]) > int(self.r2_cap):
+            raise ValueError(f"reach: the table of v_max = {v_max} m/s ends at R2 = {int(r2[-1])}, beyond r2_cap = {int(self.r2_cap)} "
+                             "(ask hidden_clearance for a larger v_cap)")
+        dev = self.qmin.device
+        thr = torch.as_tensor(169 * r2.astype(np.int64), device=dev)            # non-decreasing, < 2^31
+        q = self.qmin.to(torch.int64)
+        k = torch.arange(T, device=dev, dtype=torch.int64)
+        hit = q <= thr[None, :]
+        first = torch.where(hit, k[None, :], T).amin(dim=1, keepdim=False) if T else torch.zeros(M, dtype=torch.int64, device=dev)
+        first = torch.where(first >= T, -1, first).to(torch.int32)
+        j = torch.searchsorted(thr, q.contiguous())                             # min { j : q <= 169 R2[j] }, T = none
+        slack = torch.where(j < T, j - k[None, :], self.SLACK_NONE)
+        slack = (slack.amin(dim=1) if T else torch.full((M,), self.SLACK_NONE, dtype=torch.int64, device=dev)).to(torch.int32)
+        return hit, first, slack
+
+    def critical_speed(self):
+        """``v_crit [M]`` float64 (m/s): the slowest hidden road user that could meet the trajectory at all, ``+inf`` where nothing
+        lies within the cap.  Per sample, with ``r = sqrt(qmin / 169) cs``: at ``k = 0`` the value is 0 if
+        ``qmin <= 169 floor(margin^2 / cs^2)`` and ``+inf`` otherwise, at ``k >= 1`` it is ``max(0, r - margin) / (k dt)``;
+        ``v_crit`` is the minimum over the samples.
+
+        "euclid": exact -- ``D2 <= floor(X)`` iff ``D2 <= X``, so ``reach(v_crit (1 + 1e-9))`` hits and
+        ``reach(v_crit (1 - 1e-9))`` does not (up to the rounding of this float64 formula, around 1e-15 relative).
+        "road": the floor under ``169 R2`` makes it a LOWER bound -- no ``v_max < v_crit`` produces a hit, the smallest ``v_max``
+        that does may be larger: the conservative side."""
+        M, T = (int(v) for v in self.qmin.shape)
+        dev = self.qmin.device
+        inf = float("inf")
+        if T == 0:
+            return torch.full((M,), inf, dtype=torch.float64, device=dev)
+        q = self.qmin.to(torch.int64)
+        none = q == self.NONE
+        r = torch.sqrt(q.to(torch.float64) / 169.0) * self.cell_size
+        k = torch.arange(T, device=dev, dtype=torch.float64)
+        kdt = k * self.dt
+        kdt[0] = 1.0                                                             # (column 0 is replaced below)
+        v = torch.clamp(r - self.margin, min=0.0) / kdt[None, :]
+        r2_0 = int(hidden_reach_r2(0.0, self.dt, self.margin, self.cell_size, 1)[0])
+        v[:, 0] = torch.where(q[:, 0] <= 169 * r2_0, 0.0, inf)
+        v = torch.where(none, inf, v)
+        return v.amin(dim=1)
+
+
 class SensorModel:
     def __init__(self, lanelet_network, ref_path, sensor_radius=30, sensor_angle=90, debug=True, visualization=None,
                  ctx: Optional[N.Context] = None, n_rays=720, cell_size=0.5, device=0, routes=0,
@@ -894,6 +976,67 @@ class SensorModel:
         self._hr_inputs = (tx, ty, heading, tlen)      # (stay referenced until the next call, as in future_visibility_ex)
         return HiddenReach(arrival, cells, first, slack, r2, w, heading, hidden is not None, metric,
                            hidden_reach_road_units(r2), dist)
+
+    def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, inflate=0.0, lengths=None, metric="euclid",
+                         heading=None):
+        """Hidden-traffic clearance (``fo_scene_hidden_clearance``; DESIGN.md §5.10 "Clearance and critical speed"): ONE key
+        map and one minimum per pose that answer :meth:`hidden_reach` for every ``v_max <= v_cap``
+        (:meth:`HiddenClearance.reach`) and give the slowest hidden road user that could meet each trajectory
+        (:meth:`HiddenClearance.critical_speed`); returns a :class:`HiddenClearance`.  Arguments as for :meth:`hidden_reach`;
+        ``r2_cap`` is the last entry of the reach table of ``v_cap``.  ``heading``: the ``[M, T, 2]`` (cos, sin) tensor of an
+        earlier :class:`HiddenReach` / :class:`HiddenClearance` of the SAME candidates -- the host-side ``unit_headings`` pass
+        over ``theta`` is then skipped (``theta`` may be None).  The number of reached footprint cells (``cells`` of
+        ``hidden_reach``) is not derivable from the result, only whether it is positive."""
+        if metric not in HIDDEN_REACH_METRICS:
+            raise ValueError(f"hidden_clearance: metric {metric!r}, one of {HIDDEN_REACH_METRICS} is possible")
+        if self.window is None:
+            raise RuntimeError("hidden_clearance needs the cell classes of a previous launch()")
+        length, width, wb = (float(v) for v in tuple(vehicle)[:3])
+        v_cap, dt, inflate = float(v_cap), float(dt), float(inflate)
+        margin = math.sqrt(2.0) * self.cell_size if margin is None else float(margin)
+        if not (v_cap >= 0.0 and margin >= 0.0 and dt > 0.0):
+            raise ValueError("hidden_clearance: v_cap >= 0, margin >= 0 and dt > 0")
+        hl, hw = 0.5 * length + inflate, 0.5 * width + inflate
+        ext = N.HIDDEN_REACH_MAX_HALF_EXTENT * self.cell_size
+        if not (0.0 <= hl <= ext and 0.0 <= hw <= ext and abs(wb) <= ext):
+            raise ValueError(f"hidden_clearance: the inflated half extents and |wb_rear_axle| must lie in [0, {ext} m]")
+        M, T = (int(v) for v in x.shape)
+        if tuple(y.shape) != (M, T) or (heading is None and (theta is None or tuple(theta.shape) != (M, T))):
+            raise ValueError("hidden_clearance: x, y and theta must be [M, T]")
+        if heading is not None and tuple(heading.shape) != (M, T, 2):
+            raise ValueError("hidden_clearance: heading must be [M, T, 2]")
+        if not 1 <= T <= N.HIDDEN_REACH_MAX_J:
+            raise ValueError(f"hidden_clearance: {T} samples per trajectory, 1 .. {N.HIDDEN_REACH_MAX_J} are possible")
+        r2_cap = int(hidden_reach_r2(v_cap, dt, margin, self.cell_size, T)[-1])
+        if r2_cap >= (N.HIDDEN_REACH_MAX_HALO + 1) ** 2:
+            raise ValueError(f"hidden_clearance: a reach of {math.isqrt(r2_cap)} cells at the end of the horizon, at most "
+                             f"{N.HIDDEN_REACH_MAX_HALO} are possible (shorter horizon, lower v_cap or larger cells)")
+        if lengths is not None and tuple(np.shape(lengths)) != (M,):
+            raise ValueError("hidden_clearance: lengths must be [M]")
+        dev = self.device
+        as_dev = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64))).to(
+            dev, torch.float64).contiguous()
+        tx, ty = as_dev(x), as_dev(y)
+        heading = as_dev(unit_headings(theta) if heading is None else heading)
+        tlen = None
+        if lengths is not None:
+            tlen = (lengths if torch.is_tensor(lengths) else torch.as_tensor(np.ascontiguousarray(lengths, dtype=np.int32)))
+            tlen = tlen.to(dev, torch.int32).contiguous()
+        w = self.window
+        hidden = None         # this step's H_k when the occlusion memory ran in the stage that produced the classes
+        if self._om_plan is not None and self._om_prev_window is w:
+            hidden = self._om_buf[1 - self._om_cur]
+        key = torch.empty((w.ny, w.nx), dtype=torch.int32, device=dev)
+        qmin = torch.empty((M, T), dtype=torch.int32, device=dev)
+        dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev) if metric == "road" else None
+        p = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        args = N.HiddenClearance(M=M, T=T, d_x=p(tx), d_y=p(ty), d_heading=p(heading), d_len_or_null=p(tlen), hl=hl, hw=hw, wb=wb,
+                                 r2_cap=r2_cap, metric=N.HIDDEN_CLEARANCE_METRIC[metric], d_cls=self.cell_class.data_ptr(),
+                                 d_hidden_or_null=p(hidden), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
+                                 d_key=key.data_ptr(), d_qmin=p(qmin), d_dist_or_null=p(dist))
+        self.ctx.call("fo_scene_hidden_clearance", C.byref(args), N.current_stream(self._dev_index))
+        self._hc_inputs = (tx, ty, heading, tlen)      # (stay referenced until the next call, as in hidden_reach)
+        return HiddenClearance(key, qmin, dist, w, heading, r2_cap, metric, dt, margin, self.cell_size, hidden is not None)
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

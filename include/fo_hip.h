@@ -372,6 +372,53 @@ typedef struct {
 } fo_hidden_reach_road_t;
 int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic CLEARANCE (DESIGN.md §5.10 "Clearance and critical speed") -- one key
+ * map and one minimum per pose that answer the forecast above for EVERY hidden-user speed up to a cap, and the slowest hidden
+ * road user that could meet a trajectory at all.  Called like fo_scene_hidden_reach, whose window, class bytes, hidden mask,
+ * raster, sources S(q), passable set, road distance d (12 / 17 per step, permissive diagonals), footprint (headings handed
+ * over as data), d_len_or_null and rule for cells outside the window it takes unchanged.  Integers only, apart from the
+ * footprint test.  NONE = FO_HIDDEN_CLEARANCE_NONE = INT32_MAX.
+ *  r2_cap >= 0, squared cells: h = isqrt(r2_cap) <= FO_HIDDEN_REACH_MAX_HALO, Lcap = isqrt(169 r2_cap).  The call serves every
+ *   reach table with R2[J-1] <= r2_cap.
+ *  d_key [ny][nx] int32: D2(g) is searched over the window grown by h and is exact whenever D2 <= r2_cap.  A cell that is not
+ *   road (!(c & 1)) or has D2 > r2_cap gets NONE.  metric FO_HIDDEN_CLEARANCE_EUCLID: key = 169 D2(g).
+ *   FO_HIDDEN_CLEARANCE_ROAD: key = max(169 D2(g), d(g)^2), NONE when d(g) > Lcap or g cannot be reached over passable cells.
+ *   A cell outside the window counts as key = 0 if it is on the raster and road, else NONE.
+ *   (169 * 2 * 254^2 and (13 * 254 + 12)^2 are below 2^31.)
+ *  d_qmin [M][T] int32: min of key over the footprint cells of pose (m, k); NONE if the footprint holds no road cell within the
+ *   cap, and for k >= len[m].
+ *  The tie: for either metric and every non-decreasing table with R2[J-1] <= r2_cap, A(g) <= j iff key(g) <= 169 R2[j]
+ *   (d <= isqrt(x) iff d^2 <= x), so with j(q) = min { j : q <= 169 R2[j] }, 255 = none:
+ *   d_cells[m][k] > 0 iff qmin[m][k] <= 169 R2[k];  d_first[m] = min { k : qmin[m][k] <= 169 R2[k] }, -1 = none;
+ *   d_slack[m] = min over k with j(qmin[m][k]) != 255 of j(qmin[m][k]) - k, INT32_MAX = none.
+ *   The COUNT d_cells[m][k] is not derivable from qmin.
+ *  d_dist_or_null [ny][nx] uint16 (road only): d, 65535 = impassable or beyond Lcap.  NULL: the distances stay in a workspace
+ *   of the context.
+ * With M = 0 only the map is computed.  Launches: rows and columns of the distance transform; road: ceil(Lcap / 192) distance
+ * bands (at least one, at most 18) and one merge; one for the poses with M > 0.  No atomics, no launch waits for another
+ * workgroup, nothing is read back.  One call at a time per context (the workspaces of fo_scene_hidden_reach).
+ * FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_clearance:"): r2_cap negative or isqrt(r2_cap) >
+ * FO_HIDDEN_REACH_MAX_HALO; an unknown metric; no d_cls or d_key; M < 0; with M > 0: T < 1, no d_x / d_y / d_heading / d_qmin, or
+ * hl, hw or |wb| negative, NaN or above FO_HIDDEN_REACH_MAX_HALF_EXTENT cell sizes; a window outside [1, 32768]^2. */
+#define FO_HIDDEN_CLEARANCE_NONE 2147483647
+#define FO_HIDDEN_CLEARANCE_EUCLID 0
+#define FO_HIDDEN_CLEARANCE_ROAD 1
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* half length, half width (inflated by the caller), rear axle -> centre */
+  int32_t r2_cap, metric;
+  const uint8_t *d_cls;                     /* [win_ny][win_nx] */
+  const uint8_t *d_hidden_or_null;          /* [win_ny][win_nx] */
+  int32_t win_ix0, win_iy0, win_nx, win_ny;
+  int32_t *d_key;                           /* [win_ny][win_nx] */
+  int32_t *d_qmin;                          /* [M][T] */
+  uint16_t *d_dist_or_null;                 /* [win_ny][win_nx] d, 65535 = none (road only) */
+} fo_hidden_clearance_t;
+int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

@@ -3,6 +3,11 @@ whole call, next to the visibility stage the forecast
 follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
+                                       [--clearance]
+
+``--clearance``: one ``hidden_clearance`` call at ``v_cap = --v-max`` plus ``.reach`` for three speeds (2, 7 m/s and the cap)
+against three ``hidden_reach`` calls at those speeds, and the clearance split by stage (key map alone, whole call with and
+without heading reuse, the three derivations).
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -45,6 +50,7 @@ def main():
     ap.add_argument("--v-max", type=float, default=13.9)
     ap.add_argument("--calls", type=int, default=25)
     ap.add_argument("--metric", default="euclid", choices=("euclid", "road"), help="road: the reach follows the road (§5.10)")
+    ap.add_argument("--clearance", action="store_true", help="time hidden_clearance + .reach x 3 against three hidden_reach calls")
     a = ap.parse_args()
     if a.scene == "city_grid":
         sc = SC.synthetic_urban_grid()
@@ -80,6 +86,38 @@ def main():
     res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric), a.calls)
     res["future_visibility_720_first_seen_ms"] = _median_ms(
         lambda: sm.future_visibility_ex(tx, ty, None, t_stride=5, n_rays=720, first_seen=True), a.calls)
+    if a.clearance:
+        speeds = (2.0, 7.0, a.v_max)
+        hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, **kw)
+        got = hc()
+
+        def three_reach_calls():
+            for v in speeds:
+                sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric)
+
+        def derive(c=got):
+            for v in speeds:
+                c.reach(v)
+
+        res["speeds"] = list(speeds)
+        res["three_hidden_reach_calls_ms"] = _median_ms(three_reach_calls, a.calls)
+        res["clearance_plus_three_reach_ms"] = _median_ms(lambda: derive(hc()), a.calls)
+        res["clearance_reused_heading_plus_three_reach_ms"] = _median_ms(lambda: derive(hc(heading=got.heading)), a.calls)
+        res["clearance_call_ms"] = _median_ms(hc, a.calls)
+        res["clearance_call_reused_heading_ms"] = _median_ms(lambda: hc(heading=got.heading), a.calls)
+        res["clearance_map_only_ms"] = _median_ms(
+            lambda: sm.hidden_clearance(e, e, e, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric), a.calls)
+        res["three_reach_derivations_ms"] = _median_ms(derive, a.calls)
+        res["critical_speed_ms"] = _median_ms(got.critical_speed, a.calls)
+        # the two ways agree (exact integers), and what the critical speed says of the batch
+        for v in speeds:
+            r = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric)
+            hit, f, sl = got.reach(v)
+            assert torch.equal(hit, r.cells > 0) and torch.equal(f, r.first) and torch.equal(sl, r.slack), v
+        vc = got.critical_speed()
+        fin = vc[torch.isfinite(vc)]
+        res["trajectories_with_finite_critical_speed"] = int(fin.numel())
+        res["critical_speed_quartiles"] = [float(torch.quantile(fin, q)) for q in (0.25, 0.5, 0.75)] if fin.numel() else None
     torch.cuda.synchronize()
     first = out.first.cpu().numpy()
     res["trajectories_meeting_hidden_traffic"] = int((first >= 0).sum())
