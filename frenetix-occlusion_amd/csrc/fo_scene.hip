@@ -22,6 +22,8 @@
 //                          workgroup per obstacle (5 mm skin)
 //   fo_flag_compact_kernel deterministic stream compaction in one launch (ballot prefix inside a block, every block
 //                          sums the counts before it; fo_flag_scan/scatter for very large windows)
+//   fo_occlusion_memory_kernel / fo_occlusion_memory_road_kernel   occlusion memory, an extension: one launch between the
+//                          settlement and the compaction when armed (below; the road metric in fo_occlusion_memory_road.hpp)
 //   fo_hr_*_kernel         hidden-traffic reach forecast, an extension outside the step (fo_hidden_reach.hpp)
 //   fo_hr_road_*_kernel    its road metric: distance bands along the road, arrival merge (fo_hidden_reach_road.hpp)
 //   fo_hc_*_kernel         hidden-traffic clearance: the key map behind every reach table, its minimum per pose (fo_hidden_clearance.hpp)
@@ -34,6 +36,7 @@
 #include "fo_prep_traj.hpp"
 #include "fo_agent_rows.hpp"
 #include "fo_hidden_reach.hpp"
+#include "fo_occlusion_memory_road.hpp"
 #include "fo_hidden_reach_road.hpp"
 #include "fo_hidden_clearance.hpp"
 
@@ -110,6 +113,7 @@ struct Scene {
   size_t cap_rule_lab = 0, cap_rule_cnt = 0;
   // occlusion memory (fo_scene_set_occlusion_memory): armed for the next visibility stage only, caller-owned buffers
   bool om_armed = false;
+  bool om_road = false;   // the armed call asked for the road metric (fo_scene_set_occlusion_memory_road)
   fo_occlusion_memory_t om{};
   // hidden-traffic reach forecast (fo_scene_hidden_reach): row distances of the grown window, allocated by its first call
   uint8_t *d_hr_g = nullptr;
@@ -1904,9 +1908,23 @@ static int scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head
       while ((a.h + 1) * (a.h + 1) <= m.r2) ++a.h;
       a.pix0 = m.prev_ix0; a.piy0 = m.prev_iy0; a.pnx = m.prev_nx; a.pny = m.prev_ny; a.prev = m.d_prev;
     }
-    hipLaunchKernelGGL(fo_occlusion_memory_kernel, dim3((win_nx + OM_TX - 1) / OM_TX, (win_ny + OM_TY - 1) / OM_TY), dim3(256), 0, s,
-                       sc->map->d_raster, sc->map->rnx, sc->map->rny, win_ix0, win_iy0, win_nx, win_ny, d_cls, sc->d_flags,
-                       sc->d_blk, a);
+    if (sc->om_road && !a.reset) {   // (a reset step is the disc kernel's: bit-identical to the Euclidean memory)
+      OccMemRoadArgs ra;
+      ra.r2 = a.r2; ra.h = a.h; ra.pix0 = a.pix0; ra.piy0 = a.piy0; ra.pnx = a.pnx; ra.pny = a.pny; ra.prev = a.prev; ra.cur = a.cur;
+      ra.L = 13 * a.h;               // isqrt(169 r2) >= 13 isqrt(r2), corrected upwards
+      while ((ra.L + 1) * (ra.L + 1) <= 169 * a.r2) ++ra.L;
+      ra.n = ra.L / 12;
+      const dim3 rg((win_nx + OMR_TILE - 1) / OMR_TILE, (win_ny + OMR_TILE - 1) / OMR_TILE);
+#define FO_LAUNCH_OMR(OWN_, NCOL_)                                                                                                \
+  hipLaunchKernelGGL((fo_occlusion_memory_road_kernel<OWN_, NCOL_>), rg, dim3(256), occ_mem_road_lds(ra.n), s, sc->map->d_raster, \
+                     sc->map->rnx, sc->map->rny, win_ix0, win_iy0, win_nx, win_ny, d_cls, sc->d_flags, sc->d_blk, ra)
+      if (ra.n <= OMR_SMALL_N) FO_LAUNCH_OMR(OMR_SMALL_OWN, 1); else FO_LAUNCH_OMR(OMR_LARGE_OWN, 2);
+#undef FO_LAUNCH_OMR
+    } else {
+      hipLaunchKernelGGL(fo_occlusion_memory_kernel, dim3((win_nx + OM_TX - 1) / OM_TX, (win_ny + OM_TY - 1) / OM_TY), dim3(256), 0, s,
+                         sc->map->d_raster, sc->map->rnx, sc->map->rny, win_ix0, win_iy0, win_nx, win_ny, d_cls, sc->d_flags,
+                         sc->d_blk, a);
+    }
   }
   FO_HIP_TRY(ctx, hipGetLastError());
   if (sf_in) {
@@ -1932,27 +1950,37 @@ int fo_scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head_x, 
                           d_cls, d_occ_idx, d_n_occ, stream, nullptr, nullptr);
 }
 
-int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om) {
+// fo_scene_set_occlusion_memory / _road: the same structure, checks and refusals; the later call decides the metric
+static int set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om, bool road, const char *fn) {
   if (!ctx) return FO_E_ARG;
   if (ctx->scene) ((Scene *)ctx->scene)->om_armed = false;
   if (!om) return FO_OK;   // off
-  if (!ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_occlusion_memory: call fo_scene_set_map first");
+  if (!ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
   Scene *sc = (Scene *)ctx->scene;
   constexpr int cap = FO_OCCLUSION_MEMORY_MAX_HALO;
   if (om->r2 < 0 || om->r2 > cap * cap)
-    return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: r2 = %d outside [0, %d] (a reach of at most %d cells)", om->r2,
+    return fo_fail(ctx, FO_E_ARG, "%s: r2 = %d outside [0, %d] (a reach of at most %d cells)", fn, om->r2,
                    cap * cap, cap);
-  if (!om->d_cur || om->cur_bytes < 1) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: no buffer for this step");
+  if (!om->d_cur || om->cur_bytes < 1) return fo_fail(ctx, FO_E_ARG, "%s: no buffer for this step", fn);
   if (!om->reset) {
     if (!om->d_prev || om->d_prev == om->d_cur || om->prev_nx < 1 || om->prev_ny < 1)
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: the previous step needs a window and a buffer of its own");
+      return fo_fail(ctx, FO_E_ARG, "%s: the previous step needs a window and a buffer of its own", fn);
     if (om->prev_bytes < (int64_t)om->prev_nx * om->prev_ny)
-      return fo_fail(ctx, FO_E_ARG, "fo_scene_set_occlusion_memory: the previous buffer holds %lld bytes, its window %d x %d cells",
-                     (long long)om->prev_bytes, om->prev_nx, om->prev_ny);
+      return fo_fail(ctx, FO_E_ARG, "%s: the previous buffer holds %lld bytes, its window %d x %d cells",
+                     fn, (long long)om->prev_bytes, om->prev_nx, om->prev_ny);
   }
   sc->om = *om;
   sc->om_armed = true;
+  sc->om_road = road;
   return FO_OK;
+}
+
+int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om) {
+  return set_occlusion_memory(ctx, om, false, "fo_scene_set_occlusion_memory");
+}
+
+int fo_scene_set_occlusion_memory_road(fo_ctx *ctx, const fo_occlusion_memory_t *om) {
+  return set_occlusion_memory(ctx, om, true, "fo_scene_set_occlusion_memory_road");
 }
 
 // launch of fo_future_visibility_kernel: RPT by the ray count, the open-fan and first-seen forms by the caller

@@ -34,7 +34,7 @@ EXPORTS = [
     "fo_scene_candidate_count", "fo_scene_set_topology", "fo_scene_spawn_rules", "fo_step_run", "fo_step_mirror_wait",
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
-    "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance",
+    "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
 ]
 
 
@@ -215,6 +215,7 @@ def load():
     lib.fo_scene_set_centerlines.argtypes = [vp, C.c_int, ip, dp]
     lib.fo_scene_set_shadow_length.argtypes = [vp, C.c_double]
     lib.fo_scene_set_occlusion_memory.argtypes = [vp, C.POINTER(OcclusionMemory)]
+    lib.fo_scene_set_occlusion_memory_road.argtypes = [vp, C.POINTER(OcclusionMemory)]
     lib.fo_scene_spawn_rule_agents.argtypes = ([vp, C.c_int, dp, ip, C.c_int, C.POINTER(RuleAgentTypes), C.c_int, dp, C.c_int]
                                                + [D] * 3 + [dp] * 8 + [ip, ip, vp])
     for name in EXPORTS:

@@ -45,6 +45,16 @@ def occlusion_memory_config(acc):
     return out
 
 
+def occlusion_memory_metric(acc):
+    """``accelerator.occlusion_memory_metric`` of a loaded configuration: ``"euclid"`` (the default) or ``"road"``"""
+    metric = (acc or {}).get("occlusion_memory_metric", "euclid")
+    if metric is None:
+        metric = "euclid"
+    if metric not in ("euclid", "road"):
+        raise ValueError(f"accelerator.occlusion_memory_metric: 'euclid' or 'road', not {metric!r}")
+    return metric
+
+
 class FOInterface:
     def __init__(self, scenario, reference_path, vehicle_params, dt, config_path=None, cosy_cl=None, share_map_with=None):
         """Signature of the reference (interface.py:69) plus ``share_map_with``: another FOInterface of the same scenario
@@ -114,9 +124,11 @@ class FOInterface:
         # EXTENSION (accelerator.occlusion_memory, off by default): occluded cells seen empty since a hidden road user
         # could have got there are no longer occluded (SensorModel.enable_occlusion_memory)
         self.occlusion_memory = occlusion_memory_config(acc)
+        self.occlusion_memory_metric = occlusion_memory_metric(acc)
         if self.occlusion_memory["enabled"]:
             self.sensor_model.enable_occlusion_memory(v_max=self.occlusion_memory["v_max"],
-                                                      margin=self.occlusion_memory["margin"], dt=self.dt)
+                                                      margin=self.occlusion_memory["margin"], dt=self.dt,
+                                                      metric=self.occlusion_memory_metric)
 
     # ---------------------------------------------------------------------------------------- reference API
     def reset_occlusion_memory(self):

@@ -147,6 +147,9 @@ class CellWindow:
         return np.where(ok, iy * self.nx + ix, -1)
 
 
+OCCLUSION_MEMORY_METRICS = ("euclid", "road")
+
+
 def occlusion_memory_r2(v_max, dt_s, margin, cell_size):
     """R2 = floor(rho^2 / cs^2), rho = v_max * dt_s + margin, in float64: the reach of the occlusion memory as a squared
     cell count, so that device and host model decide membership in D = {dx^2 + dy^2 <= R2} in integers"""
@@ -455,6 +458,7 @@ class SensorModel:
         self._om_prev_window = None    # window of the other buffer's H
         self._om_host = None
         self.occlusion_memory_reset_reason = None
+        self.occlusion_memory_metric = "euclid"
         if share_map_with is not None:
             self._share_map(share_map_with)
         else:
@@ -571,10 +575,15 @@ class SensorModel:
                       off.ctypes.data, lan.ctypes.data, kind.ctypes.data)
 
     # ---- occlusion memory (extension)
-    def enable_occlusion_memory(self, enabled=True, v_max=13.9, margin=None, dt=0.1):
+    def enable_occlusion_memory(self, enabled=True, v_max=13.9, margin=None, dt=0.1, metric="euclid"):
         """keep road cells seen empty out of the occluded area until a hidden road user moving at ``v_max`` (m/s) could
         have reached them; ``margin`` (m, None = sqrt(2) cell sizes) widens the reach, ``dt`` is the length of one
-        timestep (s).  Every step with a timestep then advances the memory; the first step after this call is a reset."""
+        timestep (s).  Every step with a timestep then advances the memory; the first step after this call is a reset.
+        ``metric``: ``"euclid"`` (the disc, also across cells that are not road) or ``"road"`` (the disc and the distance
+        along passable cells, DESIGN.md §5.9 "Road metric": hidden traffic does not cross a building block)."""
+        if metric not in OCCLUSION_MEMORY_METRICS:
+            raise ValueError(f"occlusion memory: metric must be one of {OCCLUSION_MEMORY_METRICS}, not {metric!r}")
+        self.occlusion_memory_metric = metric
         if not enabled:
             self._om_plan, self._om_buf, self._om_prev_window, self._om_host = None, None, None, None
             self.occlusion_memory_reset_reason = None
@@ -603,7 +612,7 @@ class SensorModel:
         return self._om_host
 
     def _occlusion_memory_arm(self, w, timestep):
-        """arm the context's next visibility stage (fo_scene_set_occlusion_memory); returns the commit to call once the
+        """arm the context's next visibility stage (fo_scene_set_occlusion_memory, or its _road form); returns the commit to call once the
         stage has been queued, or None while the memory is off"""
         plan = self._om_plan
         if plan is None:
@@ -622,7 +631,9 @@ class SensorModel:
         if reason is None:
             m.prev_ix0, m.prev_iy0, m.prev_nx, m.prev_ny = pw.ix0, pw.iy0, pw.nx, pw.ny
             m.d_prev, m.prev_bytes = prev.data_ptr(), prev.numel()
-        self.ctx._check(self.ctx._lib.fo_scene_set_occlusion_memory(self.ctx._h, C.byref(m)))
+        arm = (self.ctx._lib.fo_scene_set_occlusion_memory_road if self.occlusion_memory_metric == "road"
+               else self.ctx._lib.fo_scene_set_occlusion_memory)
+        self.ctx._check(arm(self.ctx._h, C.byref(m)))
 
         def commit():
             plan.commit(timestep)

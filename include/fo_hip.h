@@ -252,6 +252,20 @@ typedef struct {
 } fo_occlusion_memory_t;
 int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om);
 
+/* EXTENSION: the occlusion memory under the road metric (DESIGN.md §5.9 "Road metric").  The same structure, checks and
+ * refusals as fo_scene_set_occlusion_memory, and it too arms the NEXT visibility stage only; NULL disarms; of the two arming
+ * calls the later one decides.  Integers only.  With P the P of the call above:
+ *  Pass(q) = P(q) or road(q), road = the world raster's road bit, 0 off the raster.
+ *  d(g) = min over 8-connected cell paths q0 .. qn = g with P(q0) = 1 and Pass(qi) for every i >= 1 (g included) of 12 per
+ *   axis step and 17 per diagonal step (a diagonal step asks for its two end cells only); d = 0 where P = 1.
+ *  L = isqrt(169 r2) (<= 416); a path of cost <= L has at most n = L / 12 <= 34 steps, so only cells within n cells of g matter.
+ *  An occluded cell g keeps H(g) = 1 iff P(g + d) = 1 for some dx^2 + dy^2 <= r2 (the disc test above) AND d(g) <= L; visible
+ *   cells give 0, cells that are neither the road bit, as above.  Cell by cell H_road <= H_euclid, with equality where every cell
+ *   within n of g is passable.
+ * reset != 0: the stage is bit-identical to one armed by fo_scene_set_occlusion_memory with reset != 0 (and launches that
+ * call's kernel).  Otherwise one launch of fo_occlusion_memory_road_kernel in place of the disc kernel. */
+int fo_scene_set_occlusion_memory_road(fo_ctx *ctx, const fo_occlusion_memory_t *om);
+
 /* EXTENSION, not part of the reference: how much of the currently occluded area each candidate trajectory
  * will come to see.  d_x / d_y [M][T] as for fo_sweep_run; pose (m, k) = sample k * t_stride, K = ceil(T / t_stride).
  * From every pose a full fan of n_rays (<= 768: the 720-ray fan of the visibility stage fits) rays of length r along d_dirs [n_rays][2] (world-aligned, counter-
