@@ -1579,6 +1579,9 @@ int ensure_cells(fo_ctx *ctx, Scene *sc, size_t cells) {
 
 // flags -> ascending indices (out) + count (d_total)
 // (sf: candidate flags of the phantom sampler in the same launch, fo_step_run; *sf_done says whether that happened)
+// Up to 2048 blocks of 256 cells: the one-launch kernel.  Beyond that -- a window of 725 x 725 cells or more, which at the 0.5 m
+// cell is any sensor radius above 120.5 m (SensorModel._window_for: ceil(3 r / cs) + 1 cells per side) -- the scan + scatter
+// pair, and the caller flags the sampler's candidates in a launch of its own.  tests/test_scene_forms_gpu.py runs both sides.
 int compact(fo_ctx *ctx, Scene *sc, const uint8_t *flags, const int32_t *blk, int n, int32_t *out, int32_t *d_total,
             hipStream_t s, const SpawnFlagArgs *sf = nullptr, bool *sf_done = nullptr) {
   const int nb = (n + 255) / 256;  // block counts were written by the kernel that produced the flags

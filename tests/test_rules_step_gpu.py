@@ -107,7 +107,7 @@ def _scenes():
 
 
 def _stack(torch, lanelets, obstacles, path, intersections, timestep, M=192, T=31, mode="rules", seed=3, ego=None, yaw=0.0,
-           out_mode="pair"):
+           out_mode="pair", radius=50.0, n_rays=720):
     from frenetix_occlusion import _native as N
     from frenetix_occlusion import synthetic as SY
     from frenetix_occlusion.sensor_model import SensorModel
@@ -122,7 +122,7 @@ def _stack(torch, lanelets, obstacles, path, intersections, timestep, M=192, T=3
     ctx = N.Context(0)
     obs = FOObstacles(obstacles)
     obs.update(timestep)
-    sm = SensorModel(lanelets, path, sensor_radius=50.0, sensor_angle=360.0, n_rays=720, ctx=ctx, routes=3,
+    sm = SensorModel(lanelets, path, sensor_radius=radius, sensor_angle=360.0, n_rays=n_rays, ctx=ctx, routes=3,
                      intersections=intersections)
     sl = SpawnLocator(None, path, cfg, sm, fo_obstacles=obs, dt=0.1, horizon=(T - 1) * 0.1)
     sw = MetricSweep(VEH, 0.1, thresholds={"harm": 0.1, "risk": 1}, ctx=ctx)

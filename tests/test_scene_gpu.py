@@ -129,8 +129,15 @@ def _check_step(torch, oracle, sc, ego, v_ego, timestep, sensor_angle=360.0, n_r
         np.testing.assert_allclose(b.yaw.cpu().numpy()[:n_ref], yl, rtol=0, atol=1e-12)
         assert np.array_equal(b.v.cpu().numpy()[:n_ref], vl)
         np.testing.assert_allclose(b.cov.cpu().numpy()[:n_ref], cov, rtol=1e-13, atol=0)
+    # what the form tests (tests/test_scene_forms_gpu.py) read: the sizes the host picks the kernel form by, the highest hit id,
+    # and the device buffers themselves
+    got = dict(range=sm.range.cpu().numpy().copy(), hit_id=sm.hit_id.cpu().numpy().copy(),
+               ring=sm.visible_area.ring.cpu().numpy().copy(), cell_class=sm.cell_class.cpu().numpy().copy(),
+               occluded=sm.occluded_cells().cpu().numpy().copy(),
+               visible=np.array([o.current_visible for o in obst], dtype=np.uint8), spawn_cell=b.cell.cpu().numpy().copy())
     return dict(n_spawn=n_ref, n_cand=n_cand, n_occ=len(occ_ref), vis_cells=int(((cls_ref & 2) != 0).sum()),
-                skipped=0 if skip is None else int(skip.sum()), n_exact=n_exact)
+                skipped=0 if skip is None else int(skip.sum()), n_exact=n_exact, E=len(geo.edges), O=len(flags), nx=w.nx,
+                ny=w.ny, skip_passed=sm.edge_skip is not None, hit_max=int(hid_ref.max()), got=got)
 
 
 @pytest.mark.parametrize("timestep", [0, 8, 25, 60])
