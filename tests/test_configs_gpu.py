@@ -253,11 +253,23 @@ def test_failed_planning_step_leaves_no_half_written_agent_set(torch_cuda):
 
 @pytest.mark.parametrize("routes,footprint", [(0, "polygon"), (2, "circle")])
 def test_planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, routes, footprint):
+    _planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, routes, footprint, 31)
+
+
+@pytest.mark.parametrize("T", [64, 65, 130])
+@pytest.mark.parametrize("routes,footprint", [(0, "polygon"), (2, "circle")])
+def test_planning_step_in_one_native_call_equals_the_stage_calls_at_long_horizons(torch_cuda, routes, footprint, T):
+    _planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, routes, footprint, T)
+
+
+def _planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, routes, footprint, T):
     """fo_step_run / PlanningStep (one FFI crossing per planning step, eight launches: the fan and the tile table inside the ray kernel, the
     candidate flags inside the first compaction, the agent table written by the prediction kernel) gives the bits of the
     five stage calls: cost vectors, flags, pair scalars, phantom set and cell classes, over several ego poses (window
     origin, spawn range and heading change from step to step); with and without route predictions (R slots per
-    phantom), polygonal and circular sensor footprint (range and half-fan tables written or not)"""
+    phantom), polygonal and circular sensor footprint (range and half-fan tables written or not).  Horizons of 64 / 65 / 130
+    samples, with the full per-step lists: beyond 64 samples the prediction kernel reads its own predictions back for the agent
+    table's rows instead of writing them from registers (tests/test_rules_step_gpu.py has the rule stage's half)"""
     import yaml
     torch = torch_cuda
     from frenetix_occlusion import _native as N
@@ -268,7 +280,8 @@ def test_planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, rou
     from frenetix_occlusion.spawn_locator import SpawnLocator
     from frenetix_occlusion.step import PlanningStep
     from frenetix_occlusion.sweep import MetricSweep
-    M, A, T = 2000, 32, 31
+    M, A = (2000 if T == 31 else 256), 32
+    out_mode = "pair" if T == 31 else "full"
     sc = SC.load_geometry_npz(os.path.join(GOLDEN, "scenario1_geometry.npz"))
     ego0 = sc.ego_initial
     with open(os.path.join(os.path.dirname(interface.__file__), "config", "config.yaml")) as f:
@@ -286,11 +299,11 @@ def test_planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, rou
         sm = SensorModel(sc.lanelets, ref, sensor_radius=50.0, sensor_angle=360.0, n_rays=720, cell_size=0.5, ctx=ctx,
                          routes=routes, footprint=footprint)
         sm.upload_obstacles(sc.obstacle_arrays(0)[:3])
-        sl = SpawnLocator(None, ref, cfg, sm, dt=0.1, horizon=(T - 1) * 0.1)
-        assert sl.R == max(routes, 1)
+        sl = SpawnLocator(None, ref, cfg, sm, dt=0.1, horizon=(T - 1) * 0.1 + 0.05)
+        assert sl.R == max(routes, 1) and sl.T == T
         sw = MetricSweep(S.VEHICLE_BMW320I, 0.1, thresholds={"harm": 0.1, "risk": 1}, ctx=ctx)
         tr = [torch.as_tensor(traj[k]).cuda() for k in ("x", "y", "theta", "v", "a")]
-        ps = PlanningStep(sm, sl, sw, *tr, mode="pair") if how == "one-call" else None
+        ps = PlanningStep(sm, sl, sw, *tr, mode=out_mode) if how == "one-call" else None
         got = []
         for i in range(4):
             ego = ego0[:2] + 1.3 * i * np.array([math.cos(yaw0), math.sin(yaw0)])
@@ -300,18 +313,20 @@ def test_planning_step_in_one_native_call_equals_the_stage_calls(torch_cuda, rou
             else:
                 sm.launch(ego, yaw)
                 sw.set_agents(*sl.sample(ego, yaw, v).sweep_args(), check=False)
-                out = sw.run(*tr, mode="pair")
+                out = sw.run(*tr, mode=out_mode)
             torch.cuda.synchronize()
             # (the fan tables too: the one-call step writes them inside the ray kernel, whose workgroups may be a single wave
             # -- a table left partly unwritten would only show at the few rim cells that consult it)
             fan_d, fan_r, fan_h = sm._fan_buffers()
             tables = np.concatenate([t.cpu().numpy().ravel() for t in ([fan_d, fan_r, fan_h] if footprint == "polygon" else [fan_d])])
             got.append((out.cost.cpu().numpy().copy(), out.safe.cpu().numpy().copy(), out.pair_f.cpu().numpy().copy(),
-                        sm.cell_class.cpu().numpy().copy(), sl.batch.pos.cpu().numpy().copy(), int(sl.batch.n.item()), tables))
+                        sm.cell_class.cpu().numpy().copy(), sl.batch.pos.cpu().numpy().copy(), int(sl.batch.n.item()), tables)
+                       + ((out.lists_raw.cpu().numpy().copy(), sl.batch.len.cpu().numpy().copy(), sl.batch.yaw.cpu().numpy().copy(),
+                           sl.batch.v.cpu().numpy().copy(), out.pair_i.cpu().numpy().copy()) if T != 31 else ()))
         results[how] = got
     for a, b in zip(results["stages"], results["one-call"]):
         assert a[5] == b[5] and a[5] > 0
-        for x, y in zip(a[:5] + (a[6],), b[:5] + (b[6],)):
+        for x, y in zip(a[:5] + a[6:], b[:5] + b[6:]):
             assert np.array_equal(x, y, equal_nan=True)
     assert not np.array_equal(results["stages"][0][3], results["stages"][3][3])      # the steps did differ
 

@@ -124,7 +124,8 @@ def _stack(torch, lanelets, obstacles, path, intersections, timestep, M=192, T=3
     obs.update(timestep)
     sm = SensorModel(lanelets, path, sensor_radius=radius, sensor_angle=360.0, n_rays=n_rays, ctx=ctx, routes=3,
                      intersections=intersections)
-    sl = SpawnLocator(None, path, cfg, sm, fo_obstacles=obs, dt=0.1, horizon=(T - 1) * 0.1)
+    sl = SpawnLocator(None, path, cfg, sm, fo_obstacles=obs, dt=0.1, horizon=(T - 1) * 0.1 + 0.05)
+    assert sl.T == T
     sw = MetricSweep(VEH, 0.1, thresholds={"harm": 0.1, "risk": 1}, ctx=ctx)
     traj = SY.make_trajectories(M, T, 0.1, seed=seed, ego_pos=ego, ego_yaw=yaw)
     tr = [torch.as_tensor(traj[k]).cuda() for k in ("x", "y", "theta", "v", "a")]
@@ -271,10 +272,24 @@ def test_one_call_rules_step_equals_the_sweep_over_the_host_built_agents(torch_c
 
 @pytest.mark.parametrize("mode", ["rules", "both"])
 def test_one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode):
+    _one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode, 31)
+
+
+@pytest.mark.parametrize("T", [64, 65, 130])
+@pytest.mark.parametrize("mode", ["rules", "both"])
+def test_one_call_step_with_rules_equals_the_stage_calls_at_long_horizons(torch_cuda, mode, T):
+    _one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode, T)
+
+
+def _one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode, T):
     """fo_step_run with the rule stage against the same stages queued one by one (fo_scene_fan / fo_scene_visibility /
     fo_scene_spawn / fo_scene_spawn_rules / fo_scene_spawn_rule_agents / fo_sweep_set_agents / fo_sweep_run): every output
-    bit for bit, over several steps of scenario 1"""
+    bit for bit, over several steps of scenario 1.  Horizons of 64 / 65 / 130 samples (with the full per-step lists): up to 64
+    samples the prediction kernels write the sweep's agent-table rows from registers, a lane per sample; beyond, they read their
+    own predictions back (fo_agent_row behind the block fence) and every lane raises the agent's longest-step key -- this is the
+    only test of that form"""
     torch = torch_cuda
+    out_mode = "pair" if T == 31 else "full"
     from frenetix_occlusion import scenario as S
     sc = S.load_geometry_npz(os.path.join(GOLDEN, "scenario1_geometry.npz"))
     ego0 = sc.ego_initial
@@ -282,7 +297,8 @@ def test_one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode):
     path = ego0[None, :2] + np.linspace(-5.0, 80.0, 171)[:, None] * np.array([[math.cos(yaw), math.sin(yaw)]])
     got = {}
     for how in ("stages", "one-call"):
-        k = _stack(torch, sc.lanelets, sc.obstacles, path, sc.intersections, 0, mode=mode, ego=ego0[:2], yaw=yaw, M=500)
+        k = _stack(torch, sc.lanelets, sc.obstacles, path, sc.intersections, 0, mode=mode, ego=ego0[:2], yaw=yaw, M=500 if T == 31 else 192,
+                   T=T, out_mode=out_mode)
         ps = k.step() if how == "one-call" else None
         res = []
         for step in (0, 8, 25, 60):
@@ -295,11 +311,12 @@ def test_one_call_step_with_rules_equals_the_stage_calls(torch_cuda, mode):
                 k.sm.launch(ego, yaw)
                 k.sl.find_spawn_points(ego, yaw, None, float(ego0[3]), lazy=True)
                 k.sw.set_agents(*k.sl.batch.sweep_args(), check=False)
-                out = k.sw.run(*k.tr, mode="pair")
+                out = k.sw.run(*k.tr, mode=out_mode)
             torch.cuda.synchronize()
             b = k.sl.batch
+            assert b.pos.shape[1] == T
             res.append([t.cpu().numpy().copy() for t in (out.cost, out.safe, out.pair_f, out.pair_i, k.sm.cell_class, b.pos, b.yaw,
-                                                          b.v, b.len, b.type, b.head)])
+                                                          b.v, b.len, b.type, b.head) + ((out.lists_raw,) if T != 31 else ())])
         got[how] = res
     n_rule = 0
     for a, b in zip(got["stages"], got["one-call"]):
