@@ -47,14 +47,12 @@ def _hip_sweep(torch, traj, agents, veh, dt, metrics=None, thr=None, mode="full"
     return res
 
 
-def _compare(oracle, ref, got, atol=ATOL):
-    """ref = oracle output dict, got = HIP output dict (both in oracle layout)."""
-    PF, PI, C = oracle.PF, oracle.PI, oracle.COST
-    worst = 0.0
-    # Plateaus of the collision probability: several samples within 2 atol of the pair's maximum (a tight covariance
-    # whose box probabilities saturate; float noise of the two implementations then decides np.argmax's "first
-    # maximum", hr.py:81).  harm_with_cp = obst_harm[argmax cp] is discontinuous there: on such pairs it is checked
-    # against the oracle's harm at the index the HIP side picked instead.
+def _cp_plateau(oracle, ref, got, atol=ATOL):
+    """[M,A] mask of the pairs whose collision probability has a plateau: several samples within 2 atol of the pair's
+    maximum (a tight covariance whose box probabilities saturate; float noise of the two implementations then decides
+    np.argmax's "first maximum", hr.py:81).  harm_with_cp = obst_harm[argmax cp] is discontinuous there: on such pairs it is
+    checked -- here -- against the oracle's harm at the index the HIP side picked instead."""
+    PF, PI = oracle.PF, oracle.PI
     have_lists = "lists" in ref and ref["lists"] is not None and ref["lists"].shape[-1] > 0
     plateau = np.zeros(ref["pair_f"].shape[:2], dtype=bool)
     if have_lists:
@@ -65,6 +63,27 @@ def _compare(oracle, ref, got, atol=ATOL):
             oh = np.take_along_axis(ref["lists"][:, :, oracle.LST["obst_harm"], :], gi[..., None], axis=-1)[..., 0]
             hw = got["pair_f"][..., PF["max_obst_harm_with_cp"]]
             assert np.all(np.abs(hw - oh)[plateau] <= atol), "max_obst_harm_with_cp on a cp plateau"
+    return plateau
+
+
+def _assert_argmax(vals, mxv, ri, gi, atol, name):
+    """argmax-type indices (vals [..., n] the oracle's values, mxv [...] its maximum, ri / gi [...] the oracle's and the HIP
+    side's index): equal wherever the maximum is numerically significant and unique; elsewhere the HIP index must at least
+    point at a value within atol of the oracle's maximum"""
+    picked = np.take_along_axis(vals, gi[..., None].astype(np.int64), axis=-1)[..., 0]
+    ok = np.isnan(mxv) | (np.abs(picked - mxv) <= atol)
+    assert ok.all(), name
+    # ... and unique: on a plateau (several samples within 2 atol of the maximum -- e.g. a tight covariance
+    # whose box probabilities saturate) the first-maximum rule may pick another sample of the plateau
+    sig = (np.nan_to_num(mxv) > 1e-9) & ((np.abs(vals - mxv[..., None]) <= 2 * atol).sum(axis=-1) == 1)
+    assert np.array_equal(ri[sig], gi[sig]), name
+
+
+def _compare(oracle, ref, got, atol=ATOL):
+    """ref = oracle output dict, got = HIP output dict (both in oracle layout)."""
+    PF, PI, C = oracle.PF, oracle.PI, oracle.COST
+    worst = 0.0
+    plateau = _cp_plateau(oracle, ref, got, atol)
     # float pair scalars
     for name in ("dce", "ttc", "ttce", "max_ego_risk", "max_obst_risk", "max_obst_harm_with_cp", "max_ego_harm",
                  "max_obst_harm", "max_collision_probability"):
@@ -80,21 +99,11 @@ def _compare(oracle, ref, got, atol=ATOL):
     # integer outputs: exact
     assert np.array_equal(ref["pair_i"][..., PI["time_dce"]], got["pair_i"][..., PI["time_dce"]])
     assert np.array_equal(ref["pair_i"][..., PI["hr_valid"]], got["pair_i"][..., PI["hr_valid"]])
-    # argmax-type indices: equal wherever the maximum is numerically significant; elsewhere the HIP index must at
-    # least point at a value within atol of the oracle's maximum
     if "lists" in ref and ref["lists"] is not None and ref["lists"].shape[-1] > 0:
         for idx_name, lst, mx in (("max_obst_risk_index", oracle.LST["obst_risk"], "max_obst_risk"),
                                   ("cp_argmax", oracle.LST["cp"], "max_collision_probability")):
-            ri, gi = ref["pair_i"][..., PI[idx_name]], got["pair_i"][..., PI[idx_name]]
-            vals = ref["lists"][:, :, lst, :]
-            picked = np.take_along_axis(vals, gi[..., None].astype(np.int64), axis=-1)[..., 0]
-            mxv = ref["pair_f"][..., PF[mx]]
-            ok = np.isnan(mxv) | (np.abs(picked - mxv) <= atol)
-            assert ok.all(), idx_name
-            # ... and unique: on a plateau (several samples within 2 atol of the maximum -- e.g. a tight covariance
-            # whose box probabilities saturate) the first-maximum rule may pick another sample of the plateau
-            sig = (np.nan_to_num(mxv) > 1e-9) & ((np.abs(vals - mxv[..., None]) <= 2 * atol).sum(axis=-1) == 1)
-            assert np.array_equal(ri[sig], gi[sig]), idx_name
+            _assert_argmax(ref["lists"][:, :, lst, :], ref["pair_f"][..., PF[mx]], ref["pair_i"][..., PI[idx_name]],
+                           got["pair_i"][..., PI[idx_name]], atol, idx_name)
         a, b = ref["lists"], got["lists"]
         assert np.array_equal(np.isnan(a), np.isnan(b))
         fin = np.isfinite(a)
