@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include <type_traits>
 #include "fo_hip.h"
+#include "fo_scene_state.hpp"
 
 namespace {
 
@@ -248,6 +249,16 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_traj_kernel(const HrTrajArgs
     a.first[m] = first == 0x7fffffff ? -1 : first;
     a.slack[m] = slack;
   }
+}
+
+// first half of the distance transform, for the forecast and the clearance alike: the workspace of the row distances and the rows launch
+int hr_launch_rows(fo_ctx *ctx, Scene *sc, const HrMapArgs &a, hipStream_t s) {
+  if (int rc = fo_reserve(ctx, &sc->d_hr_g, &sc->cap_hr_g, (size_t)(a.ny + 2 * a.h) * a.nx)) return rc;
+  HrMapArgs m = a;
+  m.g = sc->d_hr_g;
+  const size_t lds_rows = (size_t)((a.nx + 2 * a.h + 63) / 64) * sizeof(unsigned long long);
+  hipLaunchKernelGGL(fo_hr_rows_kernel, dim3(a.ny + 2 * a.h), dim3(HR_THREADS), lds_rows, s, m);
+  return FO_OK;
 }
 
 }  // namespace

@@ -18,11 +18,10 @@
 // share a dword, which broadcasts: no bank conflict).  Every output is written with plain vector stores.
 #pragma once
 #include "fo_hidden_reach.hpp"
+#include "fo_scene_plan.hpp"   // HRR_HALO (ring staged around a tile = steps a band can hold), HRR_BAND = 12 HRR_HALO (B), reach_bands
 
 namespace {
 
-constexpr int HRR_HALO = 16;                         // ring staged around a tile = steps a band can hold
-constexpr int HRR_BAND = 12 * HRR_HALO;              // B
 constexpr int HRR_TILE = 32;                         // tile edge
 constexpr int HRR_REGION = HRR_TILE + 2 * HRR_HALO;  // staged edge: 64 = the lanes of a wave
 constexpr int HRR_STRIDE = HRR_REGION + 2;           // + a border of "none" on every side: a neighbour read needs no bounds test
@@ -135,6 +134,17 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_road_arrival_kernel(const Hr
   }
   const int e = a.arrival[i];
   a.arrival[i] = (uint8_t)(geo > e ? geo : e);
+}
+
+// the road distance up to lmax: a launch per band of B, fixed by the reach alone, nothing is read back (one launch also when the
+// reach is 0: the sources)
+void hr_launch_bands(const HrMapArgs &a, uint16_t *d_dist, int lmax, hipStream_t s) {
+  const int bands = reach_bands(lmax);
+  const dim3 tiles((a.nx + HRR_TILE - 1) / HRR_TILE, (a.ny + HRR_TILE - 1) / HRR_TILE);
+  for (int b = 1; b <= bands; ++b) {
+    const HrRoadBandArgs ba{a, d_dist, (b - 1) * HRR_BAND, b * HRR_BAND < lmax ? b * HRR_BAND : lmax};
+    hipLaunchKernelGGL(fo_hr_road_band_kernel, tiles, dim3(HR_THREADS), 0, s, ba);
+  }
 }
 
 }  // namespace

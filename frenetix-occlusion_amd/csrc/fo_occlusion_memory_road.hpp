@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "fo_hip.h"
+#include "fo_scene_plan.hpp"   // OMR_SMALL_N, omr_small
 
 namespace {
 
@@ -31,7 +32,7 @@ constexpr int OMR_MAX_N = 34;                                  // isqrt(169 * 32
 constexpr int OMR_MAX_REGION = OMR_TILE + 2 * OMR_MAX_N;       // staged edge at the cap: 100
 // two shapes of the one kernel, chosen by n on the host: OWN staged rows per wave (4 OWN >= R; the rows past R are walls, so
 // the unrolled relaxation needs no row test) and NCOL staged columns per lane (64 NCOL >= R)
-constexpr int OMR_SMALL_N = 16, OMR_SMALL_OWN = 16, OMR_LARGE_OWN = 25;
+constexpr int OMR_SMALL_OWN = 16, OMR_LARGE_OWN = 25;   // (OMR_SMALL_N, the largest n of the small shape: fo_scene_plan.hpp)
 static_assert(4 * OMR_SMALL_OWN >= OMR_TILE + 2 * OMR_SMALL_N && 4 * OMR_LARGE_OWN >= OMR_MAX_REGION, "every staged row has a wave");
 constexpr int OMR_OPEN = 65534, OMR_WALL = 65535;
 static_assert(OMR_MAX_N == 416 / 12 && 416 * 416 <= 169 * FO_OCCLUSION_MEMORY_MAX_HALO * FO_OCCLUSION_MEMORY_MAX_HALO &&
@@ -50,7 +51,7 @@ struct OccMemRoadArgs {
 
 // dynamic LDS of a launch: [4 OWN + 2][32 + 2 n + 2] uint16 (5.5 KB at n = 4, 20.8 KB at the cap)
 inline size_t occ_mem_road_lds(int n) {
-  const size_t own = n <= OMR_SMALL_N ? OMR_SMALL_OWN : OMR_LARGE_OWN;
+  const size_t own = omr_small(n) ? OMR_SMALL_OWN : OMR_LARGE_OWN;
   return (4 * own + 2) * (size_t)(OMR_TILE + 2 * n + 2) * sizeof(uint16_t);
 }
 

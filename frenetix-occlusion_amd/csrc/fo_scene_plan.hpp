@@ -1,0 +1,51 @@
+// fo_scene_plan.hpp -- the host decisions of the scene stage as functions of plain integers: which form of a kernel a call
+// takes, and the reaches the hidden-traffic extensions derive from a squared radius.  Host-only integer arithmetic, no HIP
+// header: fo_scene.hip includes it first, the device headers take the constants below from here, and a host compiler builds it
+// alone (tests/test_scene_plan_cpu.py, next to the Python restatement tests/scene_forms.expected_form).
+#pragma once
+#include <cmath>
+#include <cstdint>
+
+namespace {
+
+constexpr int SCENE_CHUNK = 64;            // boundary pieces per chunk box (a lane each)
+constexpr int RAY_WAVES = 5;               // waves of a ray / probe / settle workgroup ...
+constexpr int COMPACT_BLOCK = 256;         // window cells per block count of the compaction
+constexpr int COMPACT_ONE_LAUNCH = 2048;   // block counts the one-launch compaction sums per block
+constexpr int FV_THREADS = 256;            // threads per pose of the future visibility
+constexpr int HRR_HALO = 16;               // ring staged around a tile of the road distance = steps a band can hold
+constexpr int HRR_BAND = 12 * HRR_HALO;    // B: distance units per band launch (12 per axis step)
+constexpr int OMR_SMALL_N = 16;            // largest halo of the road occlusion memory's small form
+
+// ... or one: the boundary soup is a single group of chunk boxes (<= 64 chunks = 4 096 pieces: only the first wave of five would
+// have pieces to scan) and the obstacle sides fit a wave; forced: FO_SCENE_FIVE_WAVES is set
+inline int ray_waves(int E, int O, bool forced) {
+  return (E + SCENE_CHUNK - 1) / SCENE_CHUNK <= 64 && 4 * O <= 64 && !forced ? 1 : RAY_WAVES;
+}
+
+// scan + scatter instead of the one-launch compaction: more than 2 048 blocks of 256 cells -- a window of 725 x 725 cells or
+// more, which at the 0.5 m cell is any sensor radius above 120.5 m (SensorModel._window_for: ceil(3 r / cs) + 1 cells per side)
+inline bool compact_two_launches(int cells) { return (cells + COMPACT_BLOCK - 1) / COMPACT_BLOCK > COMPACT_ONE_LAUNCH; }
+
+// rays a thread of the future visibility walks (tid, tid + 256, ...)
+inline int fv_rays_per_thread(int n_rays) { return (n_rays + FV_THREADS - 1) / FV_THREADS; }
+
+// floor(sqrt(v)), v >= 0: the float guess corrected both ways
+inline int64_t isqrt(int64_t v) {
+  int64_t l = (int64_t)std::sqrt((double)v);
+  while (l * l > v) --l;
+  while ((l + 1) * (l + 1) <= v) ++l;
+  return l;
+}
+
+// a hidden road user's reach of r2 (cells squared): h cells of halo; L distance units along the road (12 per axis step, 17 per
+// diagonal one, 13 per cell); a path of cost <= L has at most L / 12 steps
+inline int reach_cells(int r2) { return (int)isqrt(r2); }
+inline int road_reach(int r2) { return (int)isqrt((int64_t)169 * r2); }
+inline int road_steps(int L) { return L / 12; }
+// band launches of the road distance up to L (one also when the reach is 0: the sources)
+inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
+// the road occlusion memory's form by its halo n = road_steps(L)
+inline bool omr_small(int n) { return n <= OMR_SMALL_N; }
+
+}  // namespace

@@ -1,6 +1,7 @@
 // fo_spawn_rules.hpp -- the reference's three spawn rule families on the per-step cell classes, on the device.
-// Included at the end of fo_scene.hip (one translation unit: the kernels read the static map), compiled with
-// -ffp-contract=off like the rest of the scene stage.
+// Included by fo_scene.hip with the other parts of the scene stage (one translation unit: the kernels read the static map of
+// fo_scene_state.hpp, the rule agents share the prediction slot of fo_spawn_predict.hpp), compiled with -ffp-contract=off like
+// the rest of the scene stage.
 //
 // Replaces SpawnLocator.find_spawn_points' rule functions (ref: spawn_locator.py:80-139):
 //   pedestrian behind a visible static obstacle   spawn_locator.py:323-476
@@ -21,6 +22,9 @@
 // Launch shape: one workgroup for the turn rule + one per obstacle (static rule: a wave; dynamic rule: 1 024 threads and
 // 100 KB of LDS for the 97 x 97 candidate lattice), then one small workgroup that applies what depends on the order of
 // the obstacles (sorted by distance, the maxima of the YAML, 5 m between pedestrians) and writes the spawn points.
+#pragma once
+#include "fo_scene_state.hpp"
+#include "fo_spawn_predict.hpp"
 
 namespace {
 
@@ -1814,10 +1818,7 @@ int fo_scene_set_topology(fo_ctx *ctx, int P, const double *h_left0, const int32
     if (h_inter_lanelet[e] < 0 || h_inter_lanelet[e] >= P) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_topology: intersection entry %d out of range", e);
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   StaticMap *m = sc->map;
-  for (void **p : {(void **)&m->d_left0, (void **)&m->d_pred0, (void **)&m->d_adj_left, (void **)&m->d_inter_off,
-                   (void **)&m->d_inter_lanelet, (void **)&m->d_inter_kind}) {
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-  }
+  m->free_tables(MAP_TOPOLOGY);
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_left0, sizeof(double) * 2 * P));
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_pred0, sizeof(int32_t) * P));
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_adj_left, sizeof(int32_t) * P));
@@ -1930,8 +1931,7 @@ int fo_scene_set_centerlines(fo_ctx *ctx, int P, const int32_t *h_off, const dou
   if (m->refs.load() > 1)
     return fo_fail(ctx, FO_E_STATE, "fo_scene_set_centerlines: the static map is shared (fo_scene_share_map); set the centre lines on the owner before sharing");
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  for (void **q : {(void **)&m->d_center_off, (void **)&m->d_center_xy})
-    if (*q) { (void)hipFree(*q); *q = nullptr; }
+  m->free_tables(MAP_CENTERLINES);
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_center_off, sizeof(int32_t) * (P + 1)));
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_center_xy, sizeof(double) * 2 * (size_t)(NV > 0 ? NV : 1)));
   FO_HIP_TRY(ctx, hipMemcpy(m->d_center_off, h_off, sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice));

@@ -2,7 +2,8 @@
 kernel form, restated.  Shared by tests/test_scene_forms_cpu.py (the oracle alone: is every scene what it is meant to be)
 and tests/test_scene_forms_gpu.py (device == oracle in every form).  Nothing here touches a GPU.
 
-The switches (scene_visibility and compact() in fo_scene.hip):
+The switches (ray_waves and compact_two_launches in csrc/fo_scene_plan.hpp, taken by scene_visibility in fo_scene.hip through
+launch_rays / launch_settle / compact of fo_scene_rays.hpp / fo_scene_grid.hpp / fo_scene_compact.hpp):
   NW    fo_rays_kernel / fo_settle_kernel<SKIP, NW>: one wave per workgroup iff the map has at most 64 chunks of 64 boundary
         pieces (E <= 4096) and at most 16 obstacles and FO_SCENE_FIVE_WAVES is unset; five waves otherwise
   SKIP  a hole-skip table was passed (a hole ring of the road union enclosed by the sensor footprint)
