@@ -29,7 +29,9 @@
 //                                            for very large windows); fo_spawn_flag_kernel  candidate cells (+ block counts)
 //   fo_spawn_predict.hpp     fo_spawn_predict_kernel  evenly spaced pick + heading + predictions in the sweep's agent layout
 //   fo_spawn_rules.hpp       fo_spawn_rules_kernel, fo_spawn_rules_select_kernel, fo_spawn_rule_predict_kernel  the reference's
-//                                            three spawn rule families on the cell classes, and their agents
+//                                            three spawn rule families on the cell classes, and their agents (the families and
+//                                            what they ask of cells, polygons and frames: fo_rule_*.hpp; fo_rule_plan.hpp: the
+//                                            entry's decisions as plain functions of integers)
 //   fo_occlusion_memory.hpp  fo_occlusion_memory_kernel  occlusion memory, an extension: one launch between the settlement and
 //                                            the compaction when armed (fo_occlusion_memory_road_kernel, the road metric:
 //                                            fo_occlusion_memory_road.hpp)
@@ -202,6 +204,65 @@ int fo_scene_set_routes(fo_ctx *ctx, int P, int R, const int32_t *h_first, const
   }
   sc->map->R = R;
   sc->map->n_lanelets = P;
+  return FO_OK;
+}
+
+// the lanelet topology and the centre lines the spawn rule families read (fo_spawn_rules.hpp)
+int fo_scene_set_topology(fo_ctx *ctx, int P, const double *h_left0, const int32_t *h_pred0, const int32_t *h_adj_left,
+                          int n_inter, const int32_t *h_inter_off, const int32_t *h_inter_lanelet,
+                          const uint8_t *h_inter_kind) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_topology: call fo_scene_set_map first");
+  Scene *sc = (Scene *)ctx->scene;
+  if (P != sc->map->P || !h_left0 || !h_pred0 || !h_adj_left || n_inter < 0 || (n_inter > 0 && (!h_inter_off || !h_inter_lanelet || !h_inter_kind)))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_set_topology: bad arguments (P=%d, the map has %d lanelets)", P, sc->map->P);
+  if (sc->map->refs.load() > 1)
+    return fo_fail(ctx, FO_E_STATE, "fo_scene_set_topology: the static map is shared (fo_scene_share_map); set the topology on the owner before sharing");
+  for (int p = 0; p < P; ++p)
+    if (h_pred0[p] < -1 || h_pred0[p] >= P || h_adj_left[p] < -1 || h_adj_left[p] >= P)
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_set_topology: lanelet index out of range at %d", p);
+  const int n_e = n_inter > 0 ? h_inter_off[n_inter] : 0;
+  for (int e = 0; e < n_e; ++e)
+    if (h_inter_lanelet[e] < 0 || h_inter_lanelet[e] >= P) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_topology: intersection entry %d out of range", e);
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  StaticMap *m = sc->map;
+  m->free_tables(MAP_TOPOLOGY);
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_left0, sizeof(double) * 2 * P));
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_pred0, sizeof(int32_t) * P));
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_adj_left, sizeof(int32_t) * P));
+  FO_HIP_TRY(ctx, hipMemcpy(m->d_left0, h_left0, sizeof(double) * 2 * P, hipMemcpyHostToDevice));
+  FO_HIP_TRY(ctx, hipMemcpy(m->d_pred0, h_pred0, sizeof(int32_t) * P, hipMemcpyHostToDevice));
+  FO_HIP_TRY(ctx, hipMemcpy(m->d_adj_left, h_adj_left, sizeof(int32_t) * P, hipMemcpyHostToDevice));
+  m->n_inter = n_inter;
+  if (n_inter > 0) {
+    FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_inter_off, sizeof(int32_t) * (n_inter + 1)));
+    FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_inter_lanelet, sizeof(int32_t) * (n_e > 0 ? n_e : 1)));
+    FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_inter_kind, (size_t)(n_e > 0 ? n_e : 1)));
+    FO_HIP_TRY(ctx, hipMemcpy(m->d_inter_off, h_inter_off, sizeof(int32_t) * (n_inter + 1), hipMemcpyHostToDevice));
+    if (n_e > 0) {
+      FO_HIP_TRY(ctx, hipMemcpy(m->d_inter_lanelet, h_inter_lanelet, sizeof(int32_t) * n_e, hipMemcpyHostToDevice));
+      FO_HIP_TRY(ctx, hipMemcpy(m->d_inter_kind, h_inter_kind, (size_t)n_e, hipMemcpyHostToDevice));
+    }
+  }
+  return FO_OK;
+}
+
+int fo_scene_set_centerlines(fo_ctx *ctx, int P, const int32_t *h_off, const double *h_xy) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_centerlines: call fo_scene_set_map first");
+  Scene *sc = (Scene *)ctx->scene;
+  StaticMap *m = sc->map;
+  if (P != m->P || !h_off || h_off[0] != 0) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_centerlines: bad arguments (P=%d, the map has %d lanelets)", P, m->P);
+  for (int p = 0; p < P; ++p)
+    if (h_off[p + 1] < h_off[p]) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_centerlines: offsets must not decrease (lanelet %d)", p);
+  const int NV = h_off[P];
+  if (NV > 0 && !h_xy) return fo_fail(ctx, FO_E_ARG, "fo_scene_set_centerlines: null vertex table");
+  if (m->refs.load() > 1)
+    return fo_fail(ctx, FO_E_STATE, "fo_scene_set_centerlines: the static map is shared (fo_scene_share_map); set the centre lines on the owner before sharing");
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  m->free_tables(MAP_CENTERLINES);
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_center_off, sizeof(int32_t) * (P + 1)));
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_center_xy, sizeof(double) * 2 * (size_t)(NV > 0 ? NV : 1)));
+  FO_HIP_TRY(ctx, hipMemcpy(m->d_center_off, h_off, sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice));
+  if (NV > 0) FO_HIP_TRY(ctx, hipMemcpy(m->d_center_xy, h_xy, sizeof(double) * 2 * (size_t)NV, hipMemcpyHostToDevice));
   return FO_OK;
 }
 
@@ -655,6 +716,135 @@ int fo_scene_spawn(fo_ctx *ctx, const uint8_t *d_cls, int win_ix0, int win_iy0, 
   p.d_cell = d_cell; p.d_pos0 = d_pos0; p.d_yaw0 = d_yaw0; p.d_n = d_n; p.d_pos = d_pos; p.d_yaw = d_yaw; p.d_v = d_v; p.d_cov = d_cov;
   p.d_shape = d_shape; p.d_raw_dims = d_raw_dims; p.d_type = d_type; p.d_len = d_len;
   return scene_spawn(ctx, p, stream, nullptr);
+}
+
+// ---- the spawn rule families (fo_spawn_rules.hpp; the decisions below: fo_rule_plan.hpp)
+// the static map's side of a RuleView (raster, lane headings, lanelet polygons, topology); the caller adds the step's window of
+// classes and the frame table
+static RuleView rule_view_of(const StaticMap *m) {
+  RuleView v{};
+  v.x0 = m->x0; v.y0 = m->y0; v.cs = m->cs; v.lane_yaw = m->d_lane_yaw; v.rnx = m->rnx; v.rny = m->rny;
+  v.P = m->P; v.poly_off = m->d_poly_off; v.poly_xy = m->d_poly_xy; v.poly_box = m->d_poly_box;
+  v.left0 = m->d_left0; v.pred0 = m->d_pred0; v.adj_left = m->d_adj_left;
+  v.n_inter = m->n_inter; v.inter_off = m->d_inter_off; v.inter_lanelet = m->d_inter_lanelet; v.inter_kind = m->d_inter_kind;
+  return v;
+}
+
+// (label_nodes: an environment switch, set by the entry)
+static RuleParams rule_params_of(const fo_spawn_rule_params_t &p) {
+  RuleParams pr{};
+  pr.ego_x = p.ego_x; pr.ego_y = p.ego_y; pr.ego_yaw = p.ego_yaw; pr.ego_s = p.ego_s; pr.ego_d = p.ego_d;
+  pr.s_threshold = p.s_threshold; pr.ped_width = p.ped_width; pr.ped_length = p.ped_length;
+  pr.intention = p.intention; pr.win_i0 = p.win_i0; pr.win_i1 = p.win_i1;
+  pr.behind_static = p.behind_static; pr.behind_turn = p.behind_turn; pr.behind_dynamic = p.behind_dynamic;
+  pr.max_static = p.max_static; pr.max_dynamic = p.max_dynamic;
+  return pr;
+}
+
+int fo_scene_spawn_rules(fo_ctx *ctx, const uint8_t *d_cls, int win_ix0, int win_iy0, int win_nx, int win_ny, int n_path,
+                         const double *d_path6, int O, const double *d_ocorn, const double *d_ocen, const double *d_oyaw,
+                         const double *d_odims, const uint8_t *d_oflags, const uint8_t *d_obst_vis,
+                         const fo_spawn_rule_params_t *params, int max_out, double *d_out, int32_t *d_n_out, void *stream) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rules: call fo_scene_set_map first");
+  Scene *sc = (Scene *)ctx->scene;
+  StaticMap *m = sc->map;
+  if (!d_cls || !params || !d_out || !d_n_out || max_out < 1 || win_nx < 1 || win_ny < 1 || n_path < 2 || !d_path6 || O < 0 ||
+      (O > 0 && (!d_ocorn || !d_ocen || !d_oyaw || !d_odims || !d_oflags || !d_obst_vis)))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: bad arguments (n_path=%d O=%d max_out=%d)", n_path, O, max_out);
+  if (!m->d_poly_off) return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rules: the map holds no lanelet polygons");
+  if (params->win_i0 < 0 || params->win_i1 > n_path || params->win_i1 < params->win_i0)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: reference window [%d, %d) outside the path", params->win_i0, params->win_i1);
+  if (params->frame != 0 && params->frame != 1)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: frame = %d (0 the polyline frame, 1 the caller's frame)", params->frame);
+  // table space the host can see (what only the device can -- a sampled line longer than RL_MAXSAMP cells / 8 -- comes back as
+  // *d_n_out = -1): a rule that ran short would leave out a point the reference finds, unnoticed
+  const int nw = params->win_i1 - params->win_i0;
+  const bool dynamic_on = rule_dynamic_on(params->behind_dynamic, params->intention);
+  if (rule_turn_window_over(params->behind_turn, params->intention, nw))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: the reference window holds %d path vertices, the turn rule %d "
+                   "(thin the path out: the window is 40 m)", nw, RL_TURNW);
+  if (rule_max_static_over(params->behind_static, params->max_static))
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: max_static = %d, the selection compares the pedestrians of at most %d obstacles", params->max_static, RL_MAXPED);
+  if (dynamic_on) {
+    if (rule_lanelets_over(m->P))
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: %d lanelets, the dynamic-obstacle rule holds flags for %d", m->P, RL_LAT * RL_LAT);
+    if (rule_fifth_over(nw))
+      return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: the reference window holds %d path vertices, the dynamic-obstacle rule "
+                     "asks every fifth of at most %d", nw, 5 * RL_FIFTHV);
+  }
+  const int can = rule_capacity(params->behind_dynamic, params->max_dynamic, params->behind_static, params->max_static, params->behind_turn);
+  if (max_out < can)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rules: max_out = %d cannot hold the %d spawn points max_dynamic = %d / "
+                   "max_static = %d allow", max_out, can, params->max_dynamic, params->max_static);
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  hipStream_t s = (hipStream_t)stream;
+  int rc;
+  if ((rc = fo_reserve(ctx, &sc->d_rule_rec, &sc->cap_rule_rec, (size_t)(O + 1) * RL_REC))) return rc;
+  RuleView v = rule_view_of(m);
+  v.cls = d_cls; v.ix0 = win_ix0; v.iy0 = win_iy0; v.nx = win_nx; v.ny = win_ny;
+  v.path = d_path6; v.n_path = n_path; v.frame = params->frame;
+  RuleParams pr = rule_params_of(*params);
+  {  // (looked at on every call, like the other knobs: a test runs both labelling forms in one process)
+    const char *e = fo_getenv(fo_env_any("FO_SCENE_"), "FO_SCENE_RULE_NODES");
+    pr.label_nodes = e && e[0] == '1';
+  }
+  {  // lattice hand-off of the dynamic rule: [O][97 x 97] labels + a counter per obstacle (zero between launches)
+    const size_t cap0 = sc->cap_rule_cnt;
+    if ((rc = fo_reserve(ctx, &sc->d_rule_lab, &sc->cap_rule_lab, (size_t)(O > 0 ? O : 1) * RL_LAT * RL_LAT))) return rc;
+    if ((rc = fo_reserve(ctx, &sc->d_rule_cnt, &sc->cap_rule_cnt, (size_t)(O > 0 ? O : 1)))) return rc;
+    if (sc->cap_rule_cnt != cap0) FO_HIP_TRY(ctx, hipMemsetAsync(sc->d_rule_cnt, 0, sc->cap_rule_cnt * sizeof(int), s));
+  }
+  const int n_dyn = rule_helped(params->n_dynamic_plus1, O, dynamic_on);
+  hipLaunchKernelGGL(fo_spawn_rules_kernel, dim3(rule_grid(O, n_dyn)), dim3(RL_THREADS), 0, s, v, pr, O, d_ocorn, d_ocen, d_oyaw,
+                     d_odims, d_oflags, d_obst_vis, sc->d_rule_rec, sc->d_rule_lab, sc->d_rule_cnt, rule_told(params->n_dynamic_plus1) ? 0 : 1,
+                     n_dyn);
+  hipLaunchKernelGGL(fo_spawn_rules_select_kernel, dim3(1), dim3(64), 0, s, v, pr, O, d_ocorn, d_oflags, d_obst_vis,
+                     sc->d_rule_rec, max_out, d_out, d_n_out);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+// fo_scene_spawn_rule_agents; slot0 / agent0 / at (fo_step_run): the rule agents' slots follow the cell sampler's in the
+// same arrays, and the kernel writes its slots' rows of the sweep's agent table
+int fo_scene_rule_agents_(fo_ctx *ctx, int max_points, const double *d_points, const int32_t *d_n_points, int routes,
+                          const fo_rule_agent_types_t *types, int n_path, const double *d_path, int T, double dt, double var0,
+                          double var_factor, int slot0, int agent0, double *d_pos0, double *d_yaw0, double *d_pos, double *d_yaw,
+                          double *d_v, double *d_cov, double *d_shape, double *d_raw_dims, int32_t *d_type, int32_t *d_len,
+                          void *stream, const fo_agent_table_t *at) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rule_agents: call fo_scene_set_map first");
+  Scene *sc = (Scene *)ctx->scene;
+  StaticMap *m = sc->map;
+  if (max_points < 1 || !d_points || !d_n_points || !types || n_path < 2 || !d_path || T < 1 || !d_pos0 || !d_yaw0 || !d_pos ||
+      !d_yaw || !d_v || !d_cov || !d_shape || !d_raw_dims || !d_type || !d_len || slot0 < 0 || agent0 < 0)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_spawn_rule_agents: bad arguments (max_points=%d n_path=%d T=%d)", max_points, n_path, T);
+  if (!m->d_poly_off) return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rule_agents: the map holds no lanelet polygons");
+  if (routes < 0 || (routes > 0 && !m->d_route_first))
+    return fo_fail(ctx, FO_E_STATE, "fo_scene_spawn_rule_agents: routes = %d needs fo_scene_set_routes first", routes);
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const RuleView v = rule_view_of(m);   // (no window of classes, no frame table: the kernel asks the lanelet polygons only)
+  RuleAgentTypes ty;
+  for (int i = 0; i < 3; ++i) {
+    ty.speed[i] = types->speed[i]; ty.raw_l[i] = types->raw_l[i]; ty.raw_w[i] = types->raw_w[i];
+    ty.infl_l[i] = types->infl_l[i]; ty.infl_w[i] = types->infl_w[i];
+  }
+  RouteView rv;
+  if (routes > 0) { rv.RT = m->R; rv.first = m->d_route_first; rv.count = m->d_route_count; rv.xy = m->d_route_xy; rv.s = m->d_route_s; }
+  const int R = routes > 0 ? routes : 1;
+  PredOut po{d_pos, d_yaw, d_v, d_cov, d_shape, d_raw_dims, d_type, d_len};
+  hipLaunchKernelGGL(fo_spawn_rule_predict_kernel, dim3(max_points * R), dim3(64), 0, (hipStream_t)stream, v, max_points, d_points,
+                     d_n_points, R, ty, n_path, d_path, m->d_center_off, m->d_center_xy, rv, T, dt, var0, var_factor, slot0, agent0,
+                     d_pos0, d_yaw0, po, at ? 1 : 0, at ? *at : fo_agent_table_t());
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+int fo_scene_spawn_rule_agents(fo_ctx *ctx, int max_points, const double *d_points, const int32_t *d_n_points, int routes,
+                               const fo_rule_agent_types_t *types, int n_path, const double *d_path, int T, double dt,
+                               double var0, double var_factor, double *d_pos0, double *d_yaw0, double *d_pos, double *d_yaw,
+                               double *d_v, double *d_cov, double *d_shape, double *d_raw_dims, int32_t *d_type,
+                               int32_t *d_len, void *stream) {
+  return fo_scene_rule_agents_(ctx, max_points, d_points, d_n_points, routes, types, n_path, d_path, T, dt, var0, var_factor, 0, 0,
+                               d_pos0, d_yaw0, d_pos, d_yaw, d_v, d_cov, d_shape, d_raw_dims, d_type, d_len, stream, nullptr);
 }
 
 // h_mirror as a device pointer if the kernels can fill it themselves (see FanArgs::hit_host), else null (fo_api.hip copies)

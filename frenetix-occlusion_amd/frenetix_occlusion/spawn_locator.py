@@ -25,6 +25,7 @@ from .utils.curvilinear import pathlength
 MIN_AHEAD = 3.0            # spawn_locator.py:234,381 "ahead by >= 3 m"
 S_THRESHOLD_TIME = 4.0     # spawn_locator.py:65-66,113: s_threshold = s_ego + max(4 v, 25)
 S_THRESHOLD_MIN = 25.0
+RULE_MAX_SAMPLES = 1024    # samples of a rule line the device holds (csrc/fo_rule_plan.hpp: RL_MAXSAMP)
 
 TYPE_NAME = {0: "Car", 1: "Truck", 3: "Bicycle", 4: "Pedestrian"}
 TYPE_CODE = {"car": 0, "truck": 1, "bicycle": 3, "pedestrian": 4}
@@ -38,6 +39,18 @@ class SpawnPoint:
     cl_pos: Optional[np.ndarray] = None
     source: str = "occluded frontier"
     orientation: Optional[float] = None
+
+
+def rule_point_capacity(max_dynamic: int, max_static: int) -> int:
+    """Spawn points the three rule families emit at most: the maxima of the YAML are compared with '>' BEFORE appending and a
+    dynamic obstacle can yield a Car and a Bicycle (Q11, spawn_locator.py:212,304-309,365), so (max_dynamic + 2) +
+    (max_static + 1) + 1 points (csrc/fo_rule_plan.hpp: rule_capacity with every family on)"""
+    return max_dynamic + max_static + 4
+
+
+def turn_line_outgrows_table(cell_size: float) -> bool:
+    """The turn rule samples its 40 m reference window every cell / 8 (+ the two ends): more samples than the device holds?"""
+    return 40.0 / (cell_size / 8.0) + 2.0 > RULE_MAX_SAMPLES
 
 
 def intention_from_curvature(k) -> int:
@@ -295,12 +308,10 @@ class SpawnLocator:
             raise ValueError("accelerator.spawn.frame must be 'polyline' or 'caller'")
         self.frame_fit_m = None            # largest distance between the caller's frame and its table at the segment midpoints
         self._frame_src, self._d_frame6 = None, None
-        # capacity of the rule families' output: the maxima of the YAML are compared with '>' BEFORE appending and a dynamic
-        # obstacle can yield a Car and a Bicycle (Q11, spawn_locator.py:212,304-309,365), so the three families emit up to
-        # (max_dynamic + 2) + (max_static + 1) + 1 points -- never less room than that, whatever the YAML says
+        # capacity of the rule families' output: never less room than they can emit, whatever the YAML says
         sl_cfg = (config.get("spawn_locator") or {}) if isinstance(config, dict) else {}
         self.max_rule_points = max(int(acc.get("max_rule_points", 8)),
-                                   int(sl_cfg.get("max_dynamic_spawn_points", 1)) + int(sl_cfg.get("max_static_spawn_points", 1)) + 4)
+                                   rule_point_capacity(int(sl_cfg.get("max_dynamic_spawn_points", 1)), int(sl_cfg.get("max_static_spawn_points", 1))))
         self.routes = int(acc.get("routes", 0)) if sensor_model.route_table is not None else 0
         if self.routes == 0 and sensor_model.route_table is not None and self.mode != "cells":
             self.routes = int(sensor_model.route_table.R)       # rule vehicles follow their lanelet's routes (agent.py:283-312)
@@ -452,7 +463,7 @@ class SpawnLocator:
         # the turn rule samples its 40 m window every cell / 8 and holds 1 024 samples (include/fo_hip.h: a longer line comes back
         # as a refused point count, which only whoever READS the step's list gets to see): say so once, up front
         cs = float(getattr(sm, "cell_size", 0.5))
-        if self._rule_cfg["behind_turn"] and 40.0 / (cs / 8.0) + 2.0 > 1024.0:
+        if self._rule_cfg["behind_turn"] and turn_line_outgrows_table(cs):
             import warnings
             warnings.warn(f"SpawnLocator: cells of {cs} m -- the turn rule of the spawn locator samples the 40 m reference window "
                           "every cell / 8 and holds 1 024 samples (cells >= 0.32 m); at a turn the step's spawn-point list will be "

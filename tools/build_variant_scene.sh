@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/build_variant_scene.sh <name> <extra hipcc flags for fo_scene.hip...> -> lib/variants/libfo_hip_<name>.so (tuning builds,
-# e.g. -DFO_RULE_TRACE=1: wall-clock stamps of the dynamic spawn rule's phases, read by tools/spawn_rules_bench.py)
+# e.g. -DFO_PRED_TRACE=<block>: wall-clock stamps of one workgroup of the phantom prediction kernel, read by tools/pred_trace.py)
 set -e
 NAME=$1; shift
 R=$(cd $(dirname $0)/.. && pwd); C=$R/frenetix-occlusion_amd/csrc; L=$R/frenetix-occlusion_amd/lib/variants; mkdir -p $L/$NAME
