@@ -270,6 +270,19 @@ def current_stream(device_index=None):
         return torch.cuda.current_stream(device_index).cuda_stream
 
 
+def ptr(t):
+    """address of a device tensor as a C argument; None (NULL) for no tensor and for one without elements"""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def on_device(a, dev, dtype="float64"):
+    """host array or device tensor -> contiguous tensor of ``dtype`` on ``dev``"""
+    import numpy as np
+    import torch
+    t = a if torch.is_tensor(a) else torch.as_tensor(np.ascontiguousarray(a, dtype=getattr(np, dtype)))
+    return t.to(dev, getattr(torch, dtype)).contiguous()
+
+
 def metric_mask(names):
     m = 0
     for n in names:

@@ -1,0 +1,241 @@
+"""Hidden traffic (an extension): the reach forecast for one speed and the clearance that serves every speed up to
+a cap.  ``hidden_reach`` and ``hidden_clearance`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods (``self``)."""
+import ctypes as C
+import math
+from dataclasses import dataclass
+from types import SimpleNamespace
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _native as N
+from .cell_window import CellWindow
+from .occlusion_memory import occlusion_memory_r2
+
+
+def hidden_reach_r2(v_max, dt, margin, cell_size, J):
+    """the reach table of the hidden-traffic forecast: ``R2[j] = occlusion_memory_r2(v_max, j dt, margin,
+    cell_size)`` for the J samples of a horizon -- what the occlusion memory uses for a step of j timesteps"""
+    return np.array([occlusion_memory_r2(v_max, j * float(dt), margin, cell_size) for j in range(int(J))], dtype=np.int32)
+
+
+def hidden_reach_road_units(r2):
+    """the reach table of the forecast's road metric: ``L[j] = isqrt(169 R2[j])`` -- the Euclidean reach in the
+    units of the road distance (12 per axis step, 17 per diagonal step, 13 per cell of Euclidean length), host int32 [J]"""
+    return np.array([math.isqrt(169 * int(v)) for v in r2], dtype=np.int32)
+
+
+HIDDEN_REACH_METRICS = ("euclid", "road")
+
+
+def unit_headings(theta):
+    """(cos, sin) of the sample headings as a float64 host array [..., 2]: the ONE place the forecast's footprints get their
+    rotation from (the device takes no sine or cosine; a checker is handed these numbers as data)"""
+    th = theta.detach().cpu().numpy() if torch.is_tensor(theta) else theta
+    th = np.asarray(th, dtype=np.float64)
+    return np.stack((np.cos(th), np.sin(th)), -1)
+
+
+@dataclass
+class HiddenReach:
+    """what :meth:`SensorModel.hidden_reach` returns (device tensors): ``arrival [ny, nx]`` uint8 over ``window`` -- the
+    first horizon sample at which a road user hidden now may be in the cell, 255 = not within the horizon or not road;
+    ``cells [M, T]`` int32 -- cells of the ego rectangle at sample k that hidden traffic may have reached by then;
+    ``first [M]`` int32 -- the first such sample, -1 = none; ``slack [M]`` int32 -- min over samples and footprint cells of
+    (arrival - k), ``SLACK_NONE`` where the trajectory meets no reachable cell (``slack <= 0`` iff ``first >= 0``).
+    ``r2`` (host int32 [J]) is the reach table, ``heading`` the (cos, sin) [M, T, 2] the footprints were turned by,
+    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step.  ``metric``: "euclid" (reach as
+    a disc around every hidden cell) or "road" (that, and no earlier than the distance along passable cells allows);
+    ``reach`` (host int32 [J]) is the table in road-distance units (:func:`hidden_reach_road_units`), ``road_dist [ny, nx]``
+    uint16 the road distance itself, 65535 = impassable or beyond ``reach[-1]`` (None for "euclid")."""
+    arrival: torch.Tensor
+    cells: torch.Tensor
+    first: torch.Tensor
+    slack: torch.Tensor
+    r2: np.ndarray
+    window: CellWindow
+    heading: Optional[torch.Tensor] = None
+    from_memory: bool = False
+    metric: str = "euclid"
+    reach: Optional[np.ndarray] = None
+    road_dist: Optional[torch.Tensor] = None
+
+    SLACK_NONE = 2 ** 31 - 1
+
+
+@dataclass
+class HiddenClearance:
+    """what :meth:`SensorModel.hidden_clearance` returns (device tensors; DESIGN.md §5.10 "Clearance and critical speed"):
+    ``key [ny, nx]`` int32 over ``window`` -- ``169 D2`` ("euclid") or ``max(169 D2, d^2)`` ("road") on road cells within the cap,
+    ``NONE`` = INT32_MAX elsewhere; ``qmin [M, T]`` int32 -- the minimum of ``key`` over the ego rectangle at sample k, ``NONE``
+    where the footprint holds no road cell within the cap and for ``k >= lengths[m]``; ``dist [ny, nx]`` uint16 the road
+    distance (65535 = impassable or beyond ``isqrt(169 r2_cap)``; None for "euclid"); ``heading`` the (cos, sin) [M, T, 2] the
+    footprints were turned by (hand it to a later call of the same candidates as ``heading=``); ``r2_cap`` the cap in squared
+    cells: every reach table whose last entry is ``<= r2_cap`` is served.  ``dt``, ``margin``, ``cell_size`` are what the
+    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set.
+
+    For any such table ``A(g) <= j`` iff ``key(g) <= 169 R2[j]``, so ``cells > 0``, ``first`` and ``slack`` of
+    :meth:`SensorModel.hidden_reach` follow from ``qmin`` alone (:meth:`reach`).  The COUNT ``cells[m, k]`` itself does not:
+    ``qmin`` keeps the nearest footprint cell, not how many there are."""
+    key: torch.Tensor
+    qmin: torch.Tensor
+    dist: Optional[torch.Tensor]
+    window: CellWindow
+    heading: Optional[torch.Tensor]
+    r2_cap: int
+    metric: str = "euclid"
+    dt: float = 0.1
+    margin: float = 0.0
+    cell_size: float = 0.5
+    from_memory: bool = False
+
+    NONE = 2 ** 31 - 1
+    SLACK_NONE = 2 ** 31 - 1
+
+    def reach(self, v_max):
+        """``(hit [M, T] bool, first [M] int32, slack [M] int32)`` for a hidden road user of up to ``v_max`` m/s: ``hit`` is
+        ``cells > 0`` of ``hidden_reach(v_max=v_max)`` with the same metric, margin and ``dt``, ``first`` and ``slack`` are its
+        ``first`` and ``slack``, exactly.  Torch ops on the tensors' device, nothing is read back.  ValueError when the table
+        of ``v_max`` ends beyond ``r2_cap``."""
+        M, T = (int(v) for v in self.qmin.shape)
+        v_max = float(v_max)
+        if not v_max >= 0.0:
+            raise ValueError("reach: v_max >= 0")
+        r2 = hidden_reach_r2(v_max, self.dt, self.margin, self.cell_size, T)
+        if T and int(r2[-1]) > int(self.r2_cap):
+            raise ValueError(f"reach: the table of v_max = {v_max} m/s ends at R2 = {int(r2[-1])}, beyond r2_cap = {int(self.r2_cap)} "
+                             "(ask hidden_clearance for a larger v_cap)")
+        dev = self.qmin.device
+        thr = torch.as_tensor(169 * r2.astype(np.int64), device=dev)            # non-decreasing, < 2^31
+        q = self.qmin.to(torch.int64)
+        k = torch.arange(T, device=dev, dtype=torch.int64)
+        hit = q <= thr[None, :]
+        first = torch.where(hit, k[None, :], T).amin(dim=1, keepdim=False) if T else torch.zeros(M, dtype=torch.int64, device=dev)
+        first = torch.where(first >= T, -1, first).to(torch.int32)
+        j = torch.searchsorted(thr, q.contiguous())                             # min { j : q <= 169 R2[j] }, T = none
+        slack = torch.where(j < T, j - k[None, :], self.SLACK_NONE)
+        slack = (slack.amin(dim=1) if T else torch.full((M,), self.SLACK_NONE, dtype=torch.int64, device=dev)).to(torch.int32)
+        return hit, first, slack
+
+    def critical_speed(self):
+        """``v_crit [M]`` float64 (m/s): the slowest hidden road user that could meet the trajectory at all, ``+inf`` where nothing
+        lies within the cap.  Per sample, with ``r = sqrt(qmin / 169) cs``: at ``k = 0`` the value is 0 if
+        ``qmin <= 169 floor(margin^2 / cs^2)`` and ``+inf`` otherwise, at ``k >= 1`` it is ``max(0, r - margin) / (k dt)``;
+        ``v_crit`` is the minimum over the samples.
+
+        "euclid": exact -- ``D2 <= floor(X)`` iff ``D2 <= X``, so ``reach(v_crit (1 + 1e-9))`` hits and
+        ``reach(v_crit (1 - 1e-9))`` does not (up to the rounding of this float64 formula, around 1e-15 relative).
+        "road": the floor under ``169 R2`` makes it a LOWER bound -- no ``v_max < v_crit`` produces a hit, the smallest ``v_max``
+        that does may be larger: the conservative side."""
+        M, T = (int(v) for v in self.qmin.shape)
+        dev = self.qmin.device
+        inf = float("inf")
+        if T == 0:
+            return torch.full((M,), inf, dtype=torch.float64, device=dev)
+        q = self.qmin.to(torch.int64)
+        none = q == self.NONE
+        r = torch.sqrt(q.to(torch.float64) / 169.0) * self.cell_size
+        k = torch.arange(T, device=dev, dtype=torch.float64)
+        kdt = k * self.dt
+        kdt[0] = 1.0                                                             # (column 0 is replaced below)
+        v = torch.clamp(r - self.margin, min=0.0) / kdt[None, :]
+        r2_0 = int(hidden_reach_r2(0.0, self.dt, self.margin, self.cell_size, 1)[0])
+        v[:, 0] = torch.where(q[:, 0] <= 169 * r2_0, 0.0, inf)
+        v = torch.where(none, inf, v)
+        return v.amin(dim=1)
+
+
+def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflate, lengths, metric, heading=None):
+    """What ``hidden_reach`` and ``hidden_clearance`` (``entry``; ``v_name``: its name for the speed ``v``) do before they differ: the
+    refusals in their one order (before the last one only ``window`` and ``cell_size`` of the model are read), the device inputs,
+    the reach table of ``v``, this step's hidden set (None: the reset definition) and the ``fields`` both argument structures share."""
+    if metric not in HIDDEN_REACH_METRICS:
+        raise ValueError(f"{entry}: metric {metric!r}, one of {HIDDEN_REACH_METRICS} is possible")
+    if self.window is None:
+        raise RuntimeError(f"{entry} needs the cell classes of a previous launch()")
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    v, dt, inflate = float(v), float(dt), float(inflate)
+    margin = math.sqrt(2.0) * self.cell_size if margin is None else float(margin)
+    if not (v >= 0.0 and margin >= 0.0 and dt > 0.0):
+        raise ValueError(f"{entry}: {v_name} >= 0, margin >= 0 and dt > 0")
+    hl, hw = 0.5 * length + inflate, 0.5 * width + inflate
+    ext = N.HIDDEN_REACH_MAX_HALF_EXTENT * self.cell_size
+    if not (0.0 <= hl <= ext and 0.0 <= hw <= ext and abs(wb) <= ext):
+        raise ValueError(f"{entry}: the inflated half extents and |wb_rear_axle| must lie in [0, {ext} m]")
+    M, T = (int(a) for a in x.shape)
+    if tuple(y.shape) != (M, T) or (heading is None and (theta is None or tuple(theta.shape) != (M, T))):
+        raise ValueError(f"{entry}: x, y and theta must be [M, T]")
+    if heading is not None and tuple(heading.shape) != (M, T, 2):
+        raise ValueError(f"{entry}: heading must be [M, T, 2]")
+    if not 1 <= T <= N.HIDDEN_REACH_MAX_J:
+        raise ValueError(f"{entry}: {T} samples per trajectory, 1 .. {N.HIDDEN_REACH_MAX_J} are possible")
+    r2 = hidden_reach_r2(v, dt, margin, self.cell_size, T)
+    if int(r2[-1]) >= (N.HIDDEN_REACH_MAX_HALO + 1) ** 2:
+        raise ValueError(f"{entry}: a reach of {math.isqrt(int(r2[-1]))} cells at the end of the horizon, at most "
+                         f"{N.HIDDEN_REACH_MAX_HALO} are possible (shorter horizon, lower {v_name} or larger cells)")
+    if lengths is not None and tuple(np.shape(lengths)) != (M,):
+        raise ValueError(f"{entry}: lengths must be [M]")
+    dev = self.device
+    tx, ty = N.on_device(x, dev), N.on_device(y, dev)
+    heading = N.on_device(unit_headings(theta) if heading is None else heading, dev)
+    tlen = None if lengths is None else N.on_device(lengths, dev, "int32")
+    w = self.window
+    hidden = self._om.hidden_on_device(w)
+    fields = dict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(heading), d_len_or_null=N.ptr(tlen), hl=hl, hw=hw, wb=wb,
+                  d_cls=self.cell_class.data_ptr(), d_hidden_or_null=N.ptr(hidden), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
+                  win_ny=w.ny)
+    return SimpleNamespace(M=M, T=T, dt=dt, margin=margin, r2=r2, x=tx, y=ty, heading=heading, lengths=tlen, hidden=hidden, fields=fields)
+
+
+def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, metric="euclid"):
+    """Hidden-traffic reach forecast (``fo_scene_hidden_reach``, with ``metric="road"`` ``fo_scene_hidden_reach_road``:
+    hidden traffic arrives along the road, not through what is not road); returns a :class:`HiddenReach`.  The kernels are queued
+    on the current stream and nobody waits for them; ``theta`` is turned into (cos, sin) on the HOST (:func:`unit_headings`:
+    the device takes no sine or cosine), so a ``theta`` that lives on the device is first copied back, which waits for the
+    stream -- hand ``theta`` over as a host array, as a planner's trajectory objects give it, to avoid that.
+
+    ``x, y, theta [M, T]``: candidate trajectories, sample k at ``k dt`` from now (M = 0: the arrival map alone).
+    ``vehicle``: (length, width, wb_rear_axle) of the ego rectangle, ``inflate`` (m) is added to both half extents.
+    A road user hidden now -- in the occlusion memory's hidden set when the memory ran this step, else anywhere on
+    road that is not visible -- moves at up to ``v_max`` (m/s); ``margin`` (m, None = sqrt(2) cell sizes) as for the
+    memory.  ``lengths [M]``: samples ``k >= lengths[m]`` of a ragged batch contribute nothing."""
+    q = _prepare(self, "hidden_reach", "v_max", x=x, y=y, theta=theta, vehicle=vehicle, v=v_max, dt=dt, margin=margin, inflate=inflate,
+                 lengths=lengths, metric=metric)
+    dev, w, r2 = self.device, self.window, q.r2
+    arrival = torch.empty((w.ny, w.nx), dtype=torch.uint8, device=dev)
+    cells = torch.empty((q.M, q.T), dtype=torch.int32, device=dev)
+    first = torch.empty(q.M, dtype=torch.int32, device=dev)
+    slack = torch.empty(q.M, dtype=torch.int32, device=dev)
+    args = N.HiddenReach(J=q.T, h_r2=r2.ctypes.data_as(C.POINTER(C.c_int32)), d_arrival=arrival.data_ptr(), d_cells=N.ptr(cells),
+                         d_first=N.ptr(first), d_slack=N.ptr(slack), **q.fields)
+    dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev) if metric == "road" else None
+    if dist is not None:
+        args = N.HiddenReachRoad(base=args, d_dist_or_null=dist.data_ptr())
+    self.ctx.call("fo_scene_hidden_reach" if dist is None else "fo_scene_hidden_reach_road", C.byref(args), N.current_stream(self._dev_index))
+    self._hr_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in future_visibility_ex)
+    return HiddenReach(arrival, cells, first, slack, r2, w, q.heading, q.hidden is not None, metric,
+                       hidden_reach_road_units(r2), dist)
+
+
+def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, inflate=0.0, lengths=None, metric="euclid",
+                     heading=None):
+    """Hidden-traffic clearance (``fo_scene_hidden_clearance``; DESIGN.md §5.10 "Clearance and critical speed"): ONE key
+    map and one minimum per pose that answer :meth:`hidden_reach` for every ``v_max <= v_cap``
+    (:meth:`HiddenClearance.reach`) and give the slowest hidden road user that could meet each trajectory
+    (:meth:`HiddenClearance.critical_speed`); returns a :class:`HiddenClearance`.  Arguments as for :meth:`hidden_reach`;
+    ``r2_cap`` is the last entry of the reach table of ``v_cap``.  ``heading``: the ``[M, T, 2]`` (cos, sin) tensor of an
+    earlier :class:`HiddenReach` / :class:`HiddenClearance` of the SAME candidates -- the host-side ``unit_headings`` pass
+    over ``theta`` is then skipped (``theta`` may be None).  The number of reached footprint cells (``cells`` of
+    ``hidden_reach``) is not derivable from the result, only whether it is positive."""
+    q = _prepare(self, "hidden_clearance", "v_cap", x=x, y=y, theta=theta, vehicle=vehicle, v=v_cap, dt=dt, margin=margin, inflate=inflate,
+                 lengths=lengths, metric=metric, heading=heading)
+    dev, w, r2_cap = self.device, self.window, int(q.r2[-1])
+    key = torch.empty((w.ny, w.nx), dtype=torch.int32, device=dev)
+    qmin = torch.empty((q.M, q.T), dtype=torch.int32, device=dev)
+    dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev) if metric == "road" else None
+    args = N.HiddenClearance(r2_cap=r2_cap, metric=N.HIDDEN_CLEARANCE_METRIC[metric], d_key=key.data_ptr(), d_qmin=N.ptr(qmin),
+                             d_dist_or_null=N.ptr(dist), **q.fields)
+    self.ctx.call("fo_scene_hidden_clearance", C.byref(args), N.current_stream(self._dev_index))
+    self._hc_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in hidden_reach)
+    return HiddenClearance(key, qmin, dist, w, q.heading, r2_cap, metric, q.dt, q.margin, self.cell_size, q.hidden is not None)

@@ -16,6 +16,46 @@ def _pyhost():
     return _native.pyhost()
 
 
+# One step's obstacles travel as ONE byte buffer of O rows (csrc/fo_pyhost.c obstacle_rows writes the same layout):
+# corners [O,4,2] f64 | centres [O,2] f64 | headings [O] f64 | dimensions [O,2] f64 | flags [O] u8 -- part k starts at byte O * k_AT
+ROW_BYTES = 105
+CENTRES_AT, HEADINGS_AT, DIMENSIONS_AT, FLAGS_AT = 64, 80, 88, 104
+DYNAMIC_CANDIDATE_MASK, DYNAMIC_CANDIDATE_BITS = 13, 5      # flag bits 0 present, 2 dynamic role set; bit 3 bicycle / pedestrian clear
+
+
+def _split(buf, f64):
+    O = len(buf) // ROW_BYTES
+    part = lambda a, b: buf[O * a:O * b].view(f64)
+    return (part(0, CENTRES_AT).reshape(O, 4, 2), part(CENTRES_AT, HEADINGS_AT).reshape(O, 2), part(HEADINGS_AT, DIMENSIONS_AT),
+            part(DIMENSIONS_AT, FLAGS_AT).reshape(O, 2), buf[O * FLAGS_AT:])
+
+
+def split_rows(host):
+    """(corners, centres, headings, dimensions, flags): the parts of a packed host buffer (numpy uint8 [O * ROW_BYTES]) as views"""
+    return _split(host, np.float64)
+
+
+def split_rows_device(d):
+    """:func:`split_rows` for a packed buffer that is a torch uint8 tensor"""
+    import torch
+    return _split(d, torch.float64)
+
+
+def n_dynamic_candidates(flags):
+    """obstacles whose flags allow the dynamic-obstacle rule (present, dynamic role, no bicycle / pedestrian): a count the
+    rule launch wants from the host (fo_spawn_rule_params_t::n_dynamic_plus1)"""
+    return int(((flags & DYNAMIC_CANDIDATE_MASK) == DYNAMIC_CANDIDATE_BITS).sum())
+
+
+def resolved_first(name):
+    """property ``name`` over ``_name``: the visibility a one-call planning step left pending is applied
+    (``resolve_visible_objects``, SensorModel.defer_visible_objects) before the attribute is read; assignable as before"""
+    def get(self):
+        self.resolve_visible_objects()
+        return getattr(self, "_" + name)
+    return property(get, lambda self, v: setattr(self, "_" + name, v))
+
+
 class FOObstacle:
     def __init__(self, obst):
         self.cr_obstacle = obst
@@ -33,29 +73,14 @@ class FOObstacle:
         self._current_visible = False
         self._last_visible_at_ts = None
 
-    # visibility of the current step: after a one-call planning step these are read from the step's mirror when somebody
-    # looks (SensorModel.defer_visible_objects)
-    @property
-    def current_visible(self):
+    # visibility of the current step: after a one-call planning step these are read from the step's mirror when somebody looks
+    current_visible = resolved_first("current_visible")
+    last_visible_at_ts = resolved_first("last_visible_at_ts")
+
+    def resolve_visible_objects(self):
         o = self._owner
         if o is not None and o._pending is not None:
             o._pending()
-        return self._current_visible
-
-    @current_visible.setter
-    def current_visible(self, v):
-        self._current_visible = v
-
-    @property
-    def last_visible_at_ts(self):
-        o = self._owner
-        if o is not None and o._pending is not None:
-            o._pending()
-        return self._last_visible_at_ts
-
-    @last_visible_at_ts.setter
-    def last_visible_at_ts(self, v):
-        self._last_visible_at_ts = v
 
     @property
     def length(self):
@@ -100,15 +125,11 @@ class FOObstacles:
             o._owner = self
         self._visible_obstacle_multipolygon = None  # list of [4,2] corner arrays of the visible obstacles
 
-    @property
-    def visible_obstacle_multipolygon(self):
+    visible_obstacle_multipolygon = resolved_first("visible_obstacle_multipolygon")
+
+    def resolve_visible_objects(self):
         if self._pending is not None:
             self._pending()
-        return self._visible_obstacle_multipolygon
-
-    @visible_obstacle_multipolygon.setter
-    def visible_obstacle_multipolygon(self, v):
-        self._visible_obstacle_multipolygon = v
 
     def __iter__(self):
         return iter(self.fo_obstacles)
@@ -154,12 +175,12 @@ class FOObstacles:
     def _rows(self, tb, timestep, H):
         """the rows of time step ``timestep`` in a fresh host buffer (layout of ``packed()``) -- what ``update`` writes"""
         O = len(self.fo_obstacles)
-        host = np.empty(O * 105, dtype=np.uint8)                       # fresh per step: last step's views stay what they were
-        corn = host[:O * 64].view(np.float64).reshape(O, 4, 2)
-        cen = host[O * 64:O * 80].view(np.float64).reshape(O, 2)
-        yaw = host[O * 80:O * 88].view(np.float64)
-        dims = host[O * 88:O * 104].view(np.float64).reshape(O, 2)
-        flags = host[O * 104:]
+        host = np.empty(O * ROW_BYTES, dtype=np.uint8)                 # fresh per step: last step's views stay what they were
+        corn = host[:O * CENTRES_AT].view(np.float64).reshape(O, 4, 2)
+        cen = host[O * CENTRES_AT:O * HEADINGS_AT].view(np.float64).reshape(O, 2)
+        yaw = host[O * HEADINGS_AT:O * DIMENSIONS_AT].view(np.float64)
+        dims = host[O * DIMENSIONS_AT:O * FLAGS_AT].view(np.float64).reshape(O, 2)
+        flags = host[O * FLAGS_AT:]
         if H is not None:
             # csrc/fo_pyhost.c obstacle_rows: the same operations in the same order, in C (the array expressions below cost
             # ~40 us of interpreter time whatever O is)
@@ -254,49 +275,30 @@ class FOObstacles:
     def update_multipolygon(self):
         self._visible_obstacle_multipolygon = [o.current_corner_points for o in self.fo_obstacles if o._current_visible]
 
-    def packed(self):
-        """the rows ``SensorModel.stage_obstacles`` hands to a one-call step, one host buffer in the layout of
-        ``SensorModel.upload_obstacles``: corners [O,4,2] | centres [O,2] | headings [O] | dimensions [O,2] | flags [O]"""
-        if self._packed is not None:
-            return self._packed[0]
-        corn, cen, flags, yaw, dims = self.arrays_full()
-        O = len(flags)
-        host = np.empty(O * 105, dtype=np.uint8)
-        host[:O * 64].view(np.float64)[:] = corn.reshape(-1)
-        host[O * 64:O * 80].view(np.float64)[:] = cen.reshape(-1)
-        host[O * 80:O * 88].view(np.float64)[:] = yaw
-        host[O * 88:O * 104].view(np.float64)[:] = dims.reshape(-1)
-        host[O * 104:] = flags
-        return host
-
-    def arrays(self):
-        """corner points [O,4,2], centres [O,2], flags uint8 [O] (bit0 present at this step, bit1 occludes)"""
-        if self._packed is not None:
-            _, corn, cen, flags, _, _ = self._packed
-            return corn, cen, flags & 3
-        O = len(self.fo_obstacles)
-        corn, cen, flags = np.zeros((O, 4, 2)), np.zeros((O, 2)), np.zeros(O, dtype=np.uint8)
+    def _rows_of_state(self):
+        """the tuple ``update`` leaves in ``_packed``, built from the obstacles' own state (they were moved one by one)"""
+        host = np.zeros(len(self.fo_obstacles) * ROW_BYTES, dtype=np.uint8)
+        corn, cen, yaw, dims, flags = split_rows(host)
         for i, o in enumerate(self.fo_obstacles):
             if o.current_pos is None:
                 continue
-            corn[i], cen[i] = o.current_corner_points, o.current_pos
-            flags[i] = 1 | (2 if o.occludes else 0)
-        return corn, cen, flags
+            corn[i], cen[i], yaw[i], dims[i] = o.current_corner_points, o.current_pos, o.current_orientation, (o.length, o.width)
+            flags[i] = (1 | (2 if o.occludes else 0) | (4 if o.obstacle_role == "dynamic" else 0)
+                        | (8 if str(o.obstacle_type).lower() in ("bicycle", "pedestrian") else 0))
+        return host, corn, cen, flags, yaw, dims
+
+    def packed(self):
+        """the rows ``SensorModel.stage_obstacles`` hands to a one-call step, one host buffer in the layout of
+        ``SensorModel.upload_obstacles``: corners [O,4,2] | centres [O,2] | headings [O] | dimensions [O,2] | flags [O]"""
+        return (self._packed or self._rows_of_state())[0]
+
+    def arrays(self):
+        """corner points [O,4,2], centres [O,2], flags uint8 [O] (bit0 present at this step, bit1 occludes)"""
+        _, corn, cen, flags, _, _ = self._packed or self._rows_of_state()
+        return corn, cen, flags & 3
 
     def arrays_full(self):
         """``arrays()`` plus what the spawn rule families read (fo_scene_spawn_rules): headings [O], dimensions [O,2]
         (length, width), and two more flag bits -- bit2 dynamic role, bit3 type bicycle or pedestrian
         (spawn_locator.py:209-210).  The visibility kernels test bits 0 and 1 only, so one flag array serves both."""
-        if self._packed is not None:
-            _, corn, cen, flags, yaw, dims = self._packed
-            return corn, cen, flags, yaw, dims
-        corn, cen, flags = self.arrays()
-        O = len(self.fo_obstacles)
-        yaw, dims = np.zeros(O), np.zeros((O, 2))
-        for i, o in enumerate(self.fo_obstacles):
-            if o.current_pos is None:
-                continue
-            yaw[i], dims[i] = o.current_orientation, (o.length, o.width)
-            t = str(o.obstacle_type).lower()
-            flags[i] |= (4 if o.obstacle_role == "dynamic" else 0) | (8 if t in ("bicycle", "pedestrian") else 0)
-        return corn, cen, flags, yaw, dims
+        return (self._packed or self._rows_of_state())[1:]
