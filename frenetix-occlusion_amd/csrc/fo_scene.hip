@@ -38,6 +38,7 @@
 //   fo_future_visibility.hpp fo_future_visibility_kernel  an extension outside the step: what a candidate trajectory comes to see
 //   fo_hidden_reach.hpp      fo_hr_*_kernel  hidden-traffic reach forecast, an extension outside the step
 //   fo_hidden_reach_road.hpp fo_hr_road_*_kernel  its road metric: distance bands along the road, arrival merge
+//   fo_hidden_reach_flow.hpp fo_hr_flow_band_kernel  the road metric bound to the lanes' driving direction: directed distance bands
 //   fo_hidden_clearance.hpp  fo_hc_*_kernel  hidden-traffic clearance: the key map behind every reach table, its minimum per pose
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
@@ -47,6 +48,7 @@
 #include "fo_scene_state.hpp"
 #include "fo_hidden_reach.hpp"
 #include "fo_hidden_reach_road.hpp"
+#include "fo_hidden_reach_flow.hpp"
 #include "fo_hidden_clearance.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
@@ -263,6 +265,22 @@ int fo_scene_set_centerlines(fo_ctx *ctx, int P, const int32_t *h_off, const dou
   FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_center_xy, sizeof(double) * 2 * (size_t)(NV > 0 ? NV : 1)));
   FO_HIP_TRY(ctx, hipMemcpy(m->d_center_off, h_off, sizeof(int32_t) * (P + 1), hipMemcpyHostToDevice));
   if (NV > 0) FO_HIP_TRY(ctx, hipMemcpy(m->d_center_xy, h_xy, sizeof(double) * 2 * (size_t)NV, hipMemcpyHostToDevice));
+  return FO_OK;
+}
+
+// the move bytes of the lane flow (fo_hidden_reach_flow.hpp): a table of the map, uploaded by its owner before sharing
+int fo_scene_set_lane_moves(fo_ctx *ctx, const uint8_t *h_moves) {
+  if (!ctx || !ctx->scene) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_lane_moves: call fo_scene_set_map first");
+  StaticMap *m = ((Scene *)ctx->scene)->map;
+  if (m->P < 1 || !m->d_raster) return fo_fail(ctx, FO_E_STATE, "fo_scene_set_lane_moves: call fo_scene_set_map first");
+  if (m->refs.load() > 1)
+    return fo_fail(ctx, FO_E_STATE, "fo_scene_set_lane_moves: the static map is shared (fo_scene_share_map); set the move table on the owner before sharing");
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  m->free_tables(MAP_LANE_MOVES);
+  if (!h_moves) return FO_OK;           // NULL drops the table
+  const size_t cells = (size_t)m->rnx * m->rny;
+  FO_HIP_TRY(ctx, hipMalloc((void **)&m->d_lane_moves, cells));
+  FO_HIP_TRY(ctx, hipMemcpy(m->d_lane_moves, h_moves, cells, hipMemcpyHostToDevice));
   return FO_OK;
 }
 
@@ -522,6 +540,13 @@ static int hr_check_footprint(fo_ctx *ctx, double hl, double hw, double wb, cons
   return FO_OK;
 }
 
+// the lane flow reads the map's move table
+static int hr_check_moves(fo_ctx *ctx, const char *fn) {
+  if (!((Scene *)ctx->scene)->map->d_lane_moves)
+    return fo_fail(ctx, FO_E_STATE, "%s: the map has no move table (call fo_scene_set_lane_moves first)", fn);
+  return FO_OK;
+}
+
 // the road metric's distance map: the caller's buffer, or -- the caller does not want the distances -- a workspace of the context
 static int hr_dist_buffer(fo_ctx *ctx, Scene *sc, bool road, size_t cells, uint16_t **d_dist) {
   if (!road || *d_dist) return FO_OK;
@@ -530,8 +555,9 @@ static int hr_dist_buffer(fo_ctx *ctx, Scene *sc, bool road, size_t cells, uint1
   return FO_OK;
 }
 
-// both metrics of the forecast: `road` adds the distance bands and the arrival merge between the map and the trajectories
-static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road, uint16_t *d_dist, const char *fn, void *stream) {
+// the metrics of the forecast: `road` adds the distance bands and the arrival merge between the map and the trajectories, `flow`
+// (with road) takes the bands over the map's move table in place of the undirected ones
+static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road, bool flow, uint16_t *d_dist, const char *fn, void *stream) {
   int rc;
   if ((rc = hr_check_scene(ctx, p, fn))) return rc;
   Scene *sc = (Scene *)ctx->scene;
@@ -556,6 +582,7 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
       return fo_fail(ctx, FO_E_ARG, "%s: d_cells [M][T], d_first [M] and d_slack [M] are required with M > 0", fn);
     if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
   }
+  if (flow && (rc = hr_check_moves(ctx, fn))) return rc;
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int nx = p->win_nx, ny = p->win_ny;
   if ((rc = hr_dist_buffer(ctx, sc, road, (size_t)ny * nx, &d_dist))) return rc;
@@ -571,7 +598,8 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
   if (road) {
     HrR2 reach;                         // L[j] = isqrt(169 R2[j]): the reach in distance units (12 / 17 per step, 13 per cell)
     for (int j = 0; j < HR_MAX_J; ++j) reach.v[j] = road_reach(r2.v[j]);
-    hr_launch_bands(a, d_dist, reach.v[p->J - 1], s);
+    if (flow) hr_launch_flow_bands(a, sc->map->d_lane_moves, d_dist, reach.v[p->J - 1], s);
+    else hr_launch_bands(a, d_dist, reach.v[p->J - 1], s);
     const HrRoadArrivalArgs aa{p->d_cls, d_dist, p->d_arrival, nx * ny, p->J};
     hipLaunchKernelGGL(fo_hr_road_arrival_kernel, dim3((nx * ny + HR_THREADS - 1) / HR_THREADS), dim3(HR_THREADS), 0, s, aa, reach);
   }
@@ -590,19 +618,25 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
 }
 
 int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
-  return hidden_reach_call(ctx, p, false, nullptr, "fo_scene_hidden_reach", stream);
+  return hidden_reach_call(ctx, p, false, false, nullptr, "fo_scene_hidden_reach", stream);
 }
 
 int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream) {
-  return hidden_reach_call(ctx, p ? &p->base : nullptr, true, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_road", stream);
+  return hidden_reach_call(ctx, p ? &p->base : nullptr, true, false, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_road", stream);
 }
 
-// the clearance: the distance transform and the distance bands of the reach, run to a cap in place of a table's end
-int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream) {
-  const char *fn = "fo_scene_hidden_clearance";
+int fo_scene_hidden_reach_flow(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream) {
+  return hidden_reach_call(ctx, p ? &p->base : nullptr, true, true, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_flow", stream);
+}
+
+// the clearance: the distance transform and the distance bands of the reach, run to a cap in place of a table's end; `flow`: the
+// road metric alone, its bands over the map's move table
+static int hidden_clearance_call(fo_ctx *ctx, const fo_hidden_clearance_t *p, bool flow, const char *fn, void *stream) {
   int rc;
   if ((rc = hr_check_scene(ctx, p, fn))) return rc;
   Scene *sc = (Scene *)ctx->scene;
+  if (flow && p->metric != FO_HIDDEN_CLEARANCE_ROAD)
+    return fo_fail(ctx, FO_E_ARG, "%s: metric = %d (the lane flow is a road metric: 1 road)", fn, p->metric);
   if (p->metric != FO_HIDDEN_CLEARANCE_EUCLID && p->metric != FO_HIDDEN_CLEARANCE_ROAD)
     return fo_fail(ctx, FO_E_ARG, "%s: metric = %d (0 euclid, 1 road)", fn, p->metric);
   if (!p->d_key) return fo_fail(ctx, FO_E_ARG, "%s: no buffer for the key map (d_key is required)", fn);
@@ -618,6 +652,7 @@ int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void 
     if (!p->d_qmin) return fo_fail(ctx, FO_E_ARG, "%s: d_qmin [M][T] is required with M > 0", fn);
     if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
   }
+  if (flow && (rc = hr_check_moves(ctx, fn))) return rc;
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int nx = p->win_nx, ny = p->win_ny;
   const bool road = p->metric == FO_HIDDEN_CLEARANCE_ROAD;
@@ -631,7 +666,8 @@ int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void 
   hipLaunchKernelGGL(fo_hr_cols_kernel<HrKeyOut>, dim3((nx + HR_TX - 1) / HR_TX, (ny + HR_TY - 1) / HR_TY), dim3(HR_THREADS),
                      (size_t)(HR_TY + 2 * h) * HR_TX, s, a, HrKeyOut{p->r2_cap, p->d_key});
   if (road) {
-    hr_launch_bands(a, d_dist, road_reach(p->r2_cap), s);       // to Lcap = isqrt(169 r2_cap)
+    if (flow) hr_launch_flow_bands(a, sc->map->d_lane_moves, d_dist, road_reach(p->r2_cap), s);
+    else hr_launch_bands(a, d_dist, road_reach(p->r2_cap), s);  // to Lcap = isqrt(169 r2_cap)
     const HcMergeArgs ma{d_dist, p->d_key, nx * ny};
     hipLaunchKernelGGL(fo_hc_road_merge_kernel, dim3((nx * ny + HR_THREADS - 1) / HR_THREADS), dim3(HR_THREADS), 0, s, ma);
   }
@@ -643,6 +679,14 @@ int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void 
   }
   FO_HIP_TRY(ctx, hipGetLastError());
   return FO_OK;
+}
+
+int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream) {
+  return hidden_clearance_call(ctx, p, false, "fo_scene_hidden_clearance", stream);
+}
+
+int fo_scene_hidden_clearance_flow(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream) {
+  return hidden_clearance_call(ctx, p, true, "fo_scene_hidden_clearance_flow", stream);
 }
 
 // fo_scene_spawn on the step's own structure (the members fo_step_t lists under fo_scene_spawn); at (fo_step_run): the

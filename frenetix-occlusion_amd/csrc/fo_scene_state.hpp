@@ -17,6 +17,7 @@ enum : unsigned {
   MAP_ROUTES = 8u,           // fo_scene_set_routes
   MAP_TOPOLOGY = 16u,        // fo_scene_set_topology
   MAP_CENTERLINES = 32u,     // fo_scene_set_centerlines
+  MAP_LANE_MOVES = 64u,      // fo_scene_set_lane_moves; a new road raster (fo_scene_set_map) invalidates it
   MAP_ALL = ~0u
 };
 
@@ -51,6 +52,8 @@ struct StaticMap {
   // lanelet centre lines (fo_scene_set_centerlines; optional): vertices center_xy[center_off[p] .. center_off[p+1])
   int32_t *d_center_off = nullptr;
   double *d_center_xy = nullptr;
+  // move bytes of the lane flow (fo_scene_set_lane_moves; optional): bit k = step k * 45 degrees may be taken out of the cell
+  uint8_t *d_lane_moves = nullptr;   // [rny][rnx] or null
 
   // frees the tables of the groups in `which` and nulls their pointers: THE list of the map's device tables
   void free_tables(unsigned which = MAP_ALL) {
@@ -62,7 +65,7 @@ struct StaticMap {
         {MAP_ROUTES, (void **)&d_route_xy},         {MAP_ROUTES, (void **)&d_route_s},         {MAP_TOPOLOGY, (void **)&d_left0},
         {MAP_TOPOLOGY, (void **)&d_pred0},          {MAP_TOPOLOGY, (void **)&d_adj_left},      {MAP_TOPOLOGY, (void **)&d_inter_off},
         {MAP_TOPOLOGY, (void **)&d_inter_lanelet},  {MAP_TOPOLOGY, (void **)&d_inter_kind},    {MAP_CENTERLINES, (void **)&d_center_off},
-        {MAP_CENTERLINES, (void **)&d_center_xy}};
+        {MAP_CENTERLINES, (void **)&d_center_xy},   {MAP_LANE_MOVES, (void **)&d_lane_moves}};
     for (const auto &t : tables)
       if ((t.group & which) && *t.p) { (void)hipFree(*t.p); *t.p = nullptr; }
   }

@@ -35,6 +35,7 @@ EXPORTS = [
     "fo_scene_set_centerlines", "fo_scene_spawn_rule_agents", "fo_sweep_autotune", "fo_scene_set_shadow_length",
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
+    "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
 ]
 
 
@@ -204,6 +205,9 @@ def load():
     lib.fo_scene_hidden_reach.argtypes = [vp, C.POINTER(HiddenReach), vp]
     lib.fo_scene_hidden_reach_road.argtypes = [vp, C.POINTER(HiddenReachRoad), vp]
     lib.fo_scene_hidden_clearance.argtypes = [vp, C.POINTER(HiddenClearance), vp]
+    lib.fo_scene_set_lane_moves.argtypes = [vp, vp]
+    lib.fo_scene_hidden_reach_flow.argtypes = [vp, C.POINTER(HiddenReachRoad), vp]
+    lib.fo_scene_hidden_clearance_flow.argtypes = [vp, C.POINTER(HiddenClearance), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -27,6 +27,7 @@ def hidden_reach_road_units(r2):
 
 
 HIDDEN_REACH_METRICS = ("euclid", "road")
+HIDDEN_REACH_FLOWS = ("any", "lanes")      # "lanes": the road metric bound to the lanes' driving direction (DESIGN.md §5.10 "Lane flow")
 
 
 def unit_headings(theta):
@@ -48,7 +49,9 @@ class HiddenReach:
     ``from_memory`` whether the sources were the occlusion memory's hidden set of this step.  ``metric``: "euclid" (reach as
     a disc around every hidden cell) or "road" (that, and no earlier than the distance along passable cells allows);
     ``reach`` (host int32 [J]) is the table in road-distance units (:func:`hidden_reach_road_units`), ``road_dist [ny, nx]``
-    uint16 the road distance itself, 65535 = impassable or beyond ``reach[-1]`` (None for "euclid")."""
+    uint16 the road distance itself, 65535 = impassable or beyond ``reach[-1]`` (None for "euclid").  ``flow``: "any" (a hidden
+    road user moves along the road in any direction) or "lanes" (a hidden vehicle obeys the driving direction of the lanes, DESIGN.md
+    §5.10 "Lane flow"; ``road_dist`` then holds the distance over allowed steps, ``d_flow``)."""
     arrival: torch.Tensor
     cells: torch.Tensor
     first: torch.Tensor
@@ -60,6 +63,7 @@ class HiddenReach:
     metric: str = "euclid"
     reach: Optional[np.ndarray] = None
     road_dist: Optional[torch.Tensor] = None
+    flow: str = "any"
 
     SLACK_NONE = 2 ** 31 - 1
 
@@ -73,7 +77,8 @@ class HiddenClearance:
     distance (65535 = impassable or beyond ``isqrt(169 r2_cap)``; None for "euclid"); ``heading`` the (cos, sin) [M, T, 2] the
     footprints were turned by (hand it to a later call of the same candidates as ``heading=``); ``r2_cap`` the cap in squared
     cells: every reach table whose last entry is ``<= r2_cap`` is served.  ``dt``, ``margin``, ``cell_size`` are what the
-    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set.
+    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set.  ``flow``:
+    "any", or "lanes" -- ``d`` is the distance over the steps the lanes' driving direction allows (``d_flow``, which ``dist`` then holds).
 
     For any such table ``A(g) <= j`` iff ``key(g) <= 169 R2[j]``, so ``cells > 0``, ``first`` and ``slack`` of
     :meth:`SensorModel.hidden_reach` follow from ``qmin`` alone (:meth:`reach`).  The COUNT ``cells[m, k]`` itself does not:
@@ -89,13 +94,14 @@ class HiddenClearance:
     margin: float = 0.0
     cell_size: float = 0.5
     from_memory: bool = False
+    flow: str = "any"
 
     NONE = 2 ** 31 - 1
     SLACK_NONE = 2 ** 31 - 1
 
     def reach(self, v_max):
         """``(hit [M, T] bool, first [M] int32, slack [M] int32)`` for a hidden road user of up to ``v_max`` m/s: ``hit`` is
-        ``cells > 0`` of ``hidden_reach(v_max=v_max)`` with the same metric, margin and ``dt``, ``first`` and ``slack`` are its
+        ``cells > 0`` of ``hidden_reach(v_max=v_max)`` with the same metric, flow, margin and ``dt``, ``first`` and ``slack`` are its
         ``first`` and ``slack``, exactly.  Torch ops on the tensors' device, nothing is read back.  ValueError when the table
         of ``v_max`` ends beyond ``r2_cap``."""
         M, T = (int(v) for v in self.qmin.shape)
@@ -146,12 +152,16 @@ class HiddenClearance:
         return v.amin(dim=1)
 
 
-def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflate, lengths, metric, heading=None):
+def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflate, lengths, metric, flow="any", heading=None):
     """What ``hidden_reach`` and ``hidden_clearance`` (``entry``; ``v_name``: its name for the speed ``v``) do before they differ: the
     refusals in their one order (before the last one only ``window`` and ``cell_size`` of the model are read), the device inputs,
     the reach table of ``v``, this step's hidden set (None: the reset definition) and the ``fields`` both argument structures share."""
     if metric not in HIDDEN_REACH_METRICS:
         raise ValueError(f"{entry}: metric {metric!r}, one of {HIDDEN_REACH_METRICS} is possible")
+    if flow not in HIDDEN_REACH_FLOWS:
+        raise ValueError(f"{entry}: flow {flow!r}, one of {HIDDEN_REACH_FLOWS} is possible")
+    if flow == "lanes" and metric != "road":
+        raise ValueError(f"{entry}: flow 'lanes' follows the lanes along the road: it needs metric 'road', not {metric!r}")
     if self.window is None:
         raise RuntimeError(f"{entry} needs the cell classes of a previous launch()")
     length, width, wb = (float(a) for a in tuple(vehicle)[:3])
@@ -176,6 +186,8 @@ def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflat
                          f"{N.HIDDEN_REACH_MAX_HALO} are possible (shorter horizon, lower {v_name} or larger cells)")
     if lengths is not None and tuple(np.shape(lengths)) != (M,):
         raise ValueError(f"{entry}: lengths must be [M]")
+    if flow == "lanes" and getattr(self, "lane_moves", None) is None:
+        raise RuntimeError(f"{entry}: flow 'lanes' needs the map's move table, and this model has none (it was built without lanelets)")
     dev = self.device
     tx, ty = N.on_device(x, dev), N.on_device(y, dev)
     heading = N.on_device(unit_headings(theta) if heading is None else heading, dev)
@@ -188,9 +200,11 @@ def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflat
     return SimpleNamespace(M=M, T=T, dt=dt, margin=margin, r2=r2, x=tx, y=ty, heading=heading, lengths=tlen, hidden=hidden, fields=fields)
 
 
-def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, metric="euclid"):
+def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, metric="euclid", flow="any"):
     """Hidden-traffic reach forecast (``fo_scene_hidden_reach``, with ``metric="road"`` ``fo_scene_hidden_reach_road``:
-    hidden traffic arrives along the road, not through what is not road); returns a :class:`HiddenReach`.  The kernels are queued
+    hidden traffic arrives along the road, not through what is not road; with ``flow="lanes"`` on top of it
+    ``fo_scene_hidden_reach_flow``: hidden VEHICLES follow the driving direction of the lanes -- pedestrians do not, they keep
+    ``flow="any"``); returns a :class:`HiddenReach`.  The kernels are queued
     on the current stream and nobody waits for them; ``theta`` is turned into (cos, sin) on the HOST (:func:`unit_headings`:
     the device takes no sine or cosine), so a ``theta`` that lives on the device is first copied back, which waits for the
     stream -- hand ``theta`` over as a host array, as a planner's trajectory objects give it, to avoid that.
@@ -201,7 +215,7 @@ def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=
     road that is not visible -- moves at up to ``v_max`` (m/s); ``margin`` (m, None = sqrt(2) cell sizes) as for the
     memory.  ``lengths [M]``: samples ``k >= lengths[m]`` of a ragged batch contribute nothing."""
     q = _prepare(self, "hidden_reach", "v_max", x=x, y=y, theta=theta, vehicle=vehicle, v=v_max, dt=dt, margin=margin, inflate=inflate,
-                 lengths=lengths, metric=metric)
+                 lengths=lengths, metric=metric, flow=flow)
     dev, w, r2 = self.device, self.window, q.r2
     arrival = torch.empty((w.ny, w.nx), dtype=torch.uint8, device=dev)
     cells = torch.empty((q.M, q.T), dtype=torch.int32, device=dev)
@@ -212,14 +226,15 @@ def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=
     dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev) if metric == "road" else None
     if dist is not None:
         args = N.HiddenReachRoad(base=args, d_dist_or_null=dist.data_ptr())
-    self.ctx.call("fo_scene_hidden_reach" if dist is None else "fo_scene_hidden_reach_road", C.byref(args), N.current_stream(self._dev_index))
+    entry = "fo_scene_hidden_reach" if dist is None else "fo_scene_hidden_reach_flow" if flow == "lanes" else "fo_scene_hidden_reach_road"
+    self.ctx.call(entry, C.byref(args), N.current_stream(self._dev_index))
     self._hr_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in future_visibility_ex)
     return HiddenReach(arrival, cells, first, slack, r2, w, q.heading, q.hidden is not None, metric,
-                       hidden_reach_road_units(r2), dist)
+                       hidden_reach_road_units(r2), dist, flow)
 
 
 def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, inflate=0.0, lengths=None, metric="euclid",
-                     heading=None):
+                     heading=None, flow="any"):
     """Hidden-traffic clearance (``fo_scene_hidden_clearance``; DESIGN.md §5.10 "Clearance and critical speed"): ONE key
     map and one minimum per pose that answer :meth:`hidden_reach` for every ``v_max <= v_cap``
     (:meth:`HiddenClearance.reach`) and give the slowest hidden road user that could meet each trajectory
@@ -227,15 +242,18 @@ def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, infl
     ``r2_cap`` is the last entry of the reach table of ``v_cap``.  ``heading``: the ``[M, T, 2]`` (cos, sin) tensor of an
     earlier :class:`HiddenReach` / :class:`HiddenClearance` of the SAME candidates -- the host-side ``unit_headings`` pass
     over ``theta`` is then skipped (``theta`` may be None).  The number of reached footprint cells (``cells`` of
-    ``hidden_reach``) is not derivable from the result, only whether it is positive."""
+    ``hidden_reach``) is not derivable from the result, only whether it is positive.  ``flow="lanes"`` (with ``metric="road"``):
+    ``fo_scene_hidden_clearance_flow``, the key map of the lane flow."""
     q = _prepare(self, "hidden_clearance", "v_cap", x=x, y=y, theta=theta, vehicle=vehicle, v=v_cap, dt=dt, margin=margin, inflate=inflate,
-                 lengths=lengths, metric=metric, heading=heading)
+                 lengths=lengths, metric=metric, flow=flow, heading=heading)
     dev, w, r2_cap = self.device, self.window, int(q.r2[-1])
     key = torch.empty((w.ny, w.nx), dtype=torch.int32, device=dev)
     qmin = torch.empty((q.M, q.T), dtype=torch.int32, device=dev)
     dist = torch.empty((w.ny, w.nx), dtype=torch.uint16, device=dev) if metric == "road" else None
     args = N.HiddenClearance(r2_cap=r2_cap, metric=N.HIDDEN_CLEARANCE_METRIC[metric], d_key=key.data_ptr(), d_qmin=N.ptr(qmin),
                              d_dist_or_null=N.ptr(dist), **q.fields)
-    self.ctx.call("fo_scene_hidden_clearance", C.byref(args), N.current_stream(self._dev_index))
+    self.ctx.call("fo_scene_hidden_clearance_flow" if flow == "lanes" else "fo_scene_hidden_clearance", C.byref(args),
+                  N.current_stream(self._dev_index))
     self._hc_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in hidden_reach)
-    return HiddenClearance(key, qmin, dist, w, q.heading, r2_cap, metric, q.dt, q.margin, self.cell_size, q.hidden is not None)
+    return HiddenClearance(key, qmin, dist, w, q.heading, r2_cap, metric, q.dt, q.margin, self.cell_size, q.hidden is not None,
+                           flow)

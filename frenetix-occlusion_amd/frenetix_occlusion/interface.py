@@ -321,7 +321,7 @@ class FOInterface:
         out.slice_timesteps = slice_ts
         return out
 
-    def hidden_reach(self, trajectories, v_max=None, margin=None, inflate=0.0, metric="euclid"):
+    def hidden_reach(self, trajectories, v_max=None, margin=None, inflate=0.0, metric="euclid", flow="any"):
         """EXTENSION, not part of the reference: where road users the ego cannot see may be during the planning horizon, and
         which candidate trajectories drive through such road (:meth:`SensorModel.hidden_reach`; returns its
         :class:`~frenetix_occlusion.sensor_model.HiddenReach`: ``arrival`` map, ``cells [M, T]``, ``first [M]``,
@@ -330,7 +330,9 @@ class FOInterface:
         ``accelerator.occlusion_memory``'s values, so that the forecast and the memory speak of the same road user; with the
         memory enabled the sources are its hidden set of this step, otherwise all road that is not visible.  ``metric``:
         "euclid" -- the reach is a disc around every hidden cell, also across what is not road -- or "road": no cell is reached
-        earlier than the distance along the road allows (hidden road behind a building block does not arrive through it)."""
+        earlier than the distance along the road allows (hidden road behind a building block does not arrive through it).
+        ``flow`` (with "road"): "any" -- along the road in any direction, the call for pedestrians -- or "lanes": hidden VEHICLES
+        follow the driving direction of the lanes (no arrival down the ego's own lane or against a one-way street)."""
         from .metrics.metric import trajectories_to_arrays
         from .sweep import _vehicle_tuple
         if self.timestep is None or self.sensor_model.window is None:
@@ -341,9 +343,9 @@ class FOInterface:
         return self.sensor_model.hidden_reach(arr["x"], arr["y"], arr["theta"], vehicle=vehicle,
                                               v_max=om["v_max"] if v_max is None else v_max,
                                               margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate,
-                                              metric=metric)
+                                              metric=metric, flow=flow)
 
-    def hidden_clearance(self, trajectories, v_cap=None, margin=None, inflate=0.0, metric="euclid"):
+    def hidden_clearance(self, trajectories, v_cap=None, margin=None, inflate=0.0, metric="euclid", flow="any"):
         """EXTENSION, not part of the reference: one device pass that answers :meth:`hidden_reach` for every hidden-user speed
         up to ``v_cap`` and grades each candidate by the slowest hidden road user that could meet it
         (:meth:`SensorModel.hidden_clearance`; returns its :class:`~frenetix_occlusion.sensor_model.HiddenClearance`: ``key``
@@ -360,7 +362,7 @@ class FOInterface:
         return self.sensor_model.hidden_clearance(arr["x"], arr["y"], arr["theta"], vehicle=vehicle,
                                                   v_cap=om["v_max"] if v_cap is None else v_cap,
                                                   margin=om["margin"] if margin is None else margin, dt=self.dt,
-                                                  inflate=inflate, metric=metric)
+                                                  inflate=inflate, metric=metric, flow=flow)
 
     def _update_time_step(self, timestep):
         self.timestep = timestep

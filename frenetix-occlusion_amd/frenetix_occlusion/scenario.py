@@ -270,10 +270,12 @@ def union_boundary_edges(polys, eps=1e-4, tol=1e-9):
     return np.concatenate(out, axis=0) if out else np.zeros((0, 4))
 
 
-def lane_yaw_raster(lanelets, x0, y0, cs, nx, ny):
-    """per raster cell: heading of the nearest centre-line segment of a lanelet containing the cell centre
-    (what lanelet_orientation_at_position [ext] gives spawn_locator.py:653-660); NaN off-lane."""
-    out = np.full((ny, nx), np.nan)
+def lanelet_cell_yaws(lanelets, x0, y0, cs, nx, ny):
+    """for every lanelet that contains a cell centre, in list order: ``(iy0, iy1, ix0, ix1, idx, yaw)`` -- the raster box of its
+    polygon, the flat indices (within the box) of the cells whose centre lies inside it, and for each of them the heading of the
+    nearest centre-line segment: the cell-in-lanelet rule and the segment rule every heading table of the map shares.  A list:
+    who builds several tables hands it to each of them as ``cells=``"""
+    out = []
     for ll in lanelets:
         poly = ll.polygon
         ix0 = max(int(math.floor((poly[:, 0].min() - x0) / cs)), 0)
@@ -295,12 +297,43 @@ def lane_yaw_raster(lanelets, x0, y0, cs, nx, ny):
         t = np.clip(np.sum((qi[:, None, :] - a[None]) * e[None], axis=2) / l2[None], 0.0, 1.0)
         proj = a[None] + t[..., None] * e[None]
         k = np.argmin(np.sum((qi[:, None, :] - proj) ** 2, axis=2), axis=1)
-        yaw = np.arctan2(e[k, 1], e[k, 0])
+        out.append((iy0, iy1, ix0, ix1, np.nonzero(inside)[0], np.arctan2(e[k, 1], e[k, 0])))
+    return out
+
+
+def lane_yaw_raster(lanelets, x0, y0, cs, nx, ny, cells=None):
+    """per raster cell: heading of the nearest centre-line segment of a lanelet containing the cell centre
+    (what lanelet_orientation_at_position [ext] gives spawn_locator.py:653-660); NaN off-lane."""
+    out = np.full((ny, nx), np.nan)
+    for iy0, iy1, ix0, ix1, idx, yaw in (lanelet_cell_yaws(lanelets, x0, y0, cs, nx, ny) if cells is None else cells):
         sub = out[iy0:iy1, ix0:ix1].ravel()
-        idx = np.nonzero(inside)[0]
         free = np.isnan(sub[idx])       # first lanelet in list order wins where lanelets overlap
         sub[idx[free]] = yaw[free]
         out[iy0:iy1, ix0:ix1] = sub.reshape(iy1 - iy0, ix1 - ix0)
+    return out
+
+
+def lane_move_raster(lanelets, x0, y0, cs, nx, ny, cone_deg=67.5, cells=None):
+    """per raster cell: the move byte of the lane flow (DESIGN.md §5.10 "Lane flow"), uint8 [ny, nx].  Bit k is set when a
+    lane-abiding vehicle in the cell may take the lattice step k (E, NE, N, NW, W, SW, S, SE: step k points at k * 45 degrees):
+    ``cos(k * 45 deg - yaw) >= cos(cone)`` for the heading ``yaw`` of the nearest centre-line segment (the rules of
+    :func:`lane_yaw_raster`) of ANY lanelet that contains the cell centre -- the union over all of them, so that every turn
+    through an intersection stays possible.  0xFF (every step) off-lane.  At 67.5 degrees a heading gets three directions,
+    four at the float borderline of odd multiples of 22.5 degrees."""
+    out = np.zeros((ny, nx), dtype=np.uint8)
+    on_lane = np.zeros((ny, nx), dtype=bool)
+    steps = np.deg2rad(45.0 * np.arange(8))
+    lim = math.cos(math.radians(float(cone_deg)))
+    weight = (1 << np.arange(8)).astype(np.uint8)
+    for iy0, iy1, ix0, ix1, idx, yaw in (lanelet_cell_yaws(lanelets, x0, y0, cs, nx, ny) if cells is None else cells):
+        bits = ((np.cos(steps[None, :] - yaw[:, None]) >= lim) * weight[None, :]).sum(axis=1).astype(np.uint8)
+        sub = out[iy0:iy1, ix0:ix1].ravel()
+        sub[idx] |= bits
+        out[iy0:iy1, ix0:ix1] = sub.reshape(iy1 - iy0, ix1 - ix0)
+        hit = on_lane[iy0:iy1, ix0:ix1].ravel()
+        hit[idx] = True
+        on_lane[iy0:iy1, ix0:ix1] = hit.reshape(iy1 - iy0, ix1 - ix0)
+    out[~on_lane] = 0xFF
     return out
 
 

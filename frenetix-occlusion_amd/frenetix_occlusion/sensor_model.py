@@ -22,7 +22,7 @@ from .fan_geometry import ROAD, VISIBLE, OCCLUDED, HoleIndex, footprint_polygon,
 from .cell_window import CellWindow, VisibleArea  # noqa: F401
 from .occlusion_memory import OCCLUSION_MEMORY_METRICS, OcclusionMemory, OcclusionMemoryPlan, occlusion_memory_r2  # noqa: F401
 from .future_visibility import FutureVisibility  # noqa: F401
-from .hidden_traffic import HIDDEN_REACH_METRICS, HiddenClearance, HiddenReach, hidden_reach_r2, hidden_reach_road_units, unit_headings  # noqa: F401
+from .hidden_traffic import HIDDEN_REACH_FLOWS, HIDDEN_REACH_METRICS, HiddenClearance, HiddenReach, hidden_reach_r2, hidden_reach_road_units, unit_headings  # noqa: F401
 
 
 class SensorModel:
@@ -104,12 +104,13 @@ class SensorModel:
         self.map_geometry, self.hole_index = other.map_geometry, other.hole_index
         self._skip_key, self._edge_skip = (), None
         self.raster_origin, self.raster_dims, self.lane_yaw = other.raster_origin, other.raster_dims, other.lane_yaw
+        self.lane_moves = other.lane_moves      # (on the device the table travels with the map)
         self.route_table, self.lanelet_raster = other.route_table, other.lanelet_raster
         self.ctx.call("fo_scene_share_map", other.ctx._h)
 
     # ---- one-off: replaces _convert_lanelet_network (sensor_model.py:195-199)
     def _set_map(self, net):
-        from .scenario import lane_yaw_raster, lanelets_of
+        from .scenario import lane_move_raster, lane_yaw_raster, lanelet_cell_yaws, lanelets_of
         if isinstance(net, MapGeometry):
             geo, lanelets = net, None
         else:
@@ -126,8 +127,12 @@ class SensorModel:
         nx = int(math.ceil((xy[:, 0].max() + margin - x0) / cs))
         ny = int(math.ceil((xy[:, 1].max() + margin - y0) / cs))
         self.raster_origin, self.raster_dims = (x0, y0), (nx, ny)
-        lane_yaw = lane_yaw_raster(lanelets, x0, y0, cs, nx, ny) if lanelets is not None else None
+        on_lane = lanelet_cell_yaws(lanelets, x0, y0, cs, nx, ny) if lanelets is not None else None     # one pass for both tables
+        lane_yaw = lane_yaw_raster(lanelets, x0, y0, cs, nx, ny, cells=on_lane) if lanelets is not None else None
         self.lane_yaw = lane_yaw
+        # move bytes of the lane flow (hidden_reach / hidden_clearance with flow="lanes"; DESIGN.md §5.10 "Lane flow")
+        self.lane_moves = (np.ascontiguousarray(lane_move_raster(lanelets, x0, y0, cs, nx, ny, cells=on_lane))
+                           if lanelets is not None else None)
         off = np.ascontiguousarray(geo.poly_off, dtype=np.int32)
         pxy = np.ascontiguousarray(geo.poly_xy, dtype=np.float64)
         edges = np.ascontiguousarray(geo.edges, dtype=np.float64)
@@ -140,6 +145,8 @@ class SensorModel:
         if len(edges):
             line = np.ascontiguousarray(geo.edge_line, dtype=np.int32)
             self.ctx.call("fo_scene_set_edge_lines", len(edges), line.ctypes.data)
+        if self.lane_moves is not None:
+            self.ctx.call("fo_scene_set_lane_moves", self.lane_moves.ctypes.data)
         if lanelets:
             self._set_topology(lanelets)
             # centre lines: a pedestrian spawned behind a turn heads for the centre of its lanelet (agent.py:459-467)

@@ -433,6 +433,42 @@ typedef struct {
 } fo_hidden_clearance_t;
 int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: the road metric bound to the DRIVING DIRECTION of the lanes (DESIGN.md §5.10 "Lane
+ * flow") -- a hidden vehicle that obeys the lanes does not come back down the ego's own lane, against a one-way street or out of
+ * the lane that leads away from a junction.  Opt-in and additive: pedestrians are not bound to lanes and keep the two entries
+ * above.  Integers only; the device computes no angle.
+ *  Directions k = 0 .. 7 are the lattice steps E (1,0), NE (1,1), N (0,1), NW (-1,1), W (-1,0), SW (-1,-1), S (0,-1), SE (1,-1):
+ *   step k points at k * 45 degrees.
+ *  Move byte out(q), one uint8 per cell of the world raster: bit k is set when a lane-abiding vehicle in q may take step k.
+ *   0xFF (every step) for a cell off the raster and, by the table's builder, for a cell whose centre lies in no lanelet: the
+ *   occlusion memory's hidden cells beside the road stay free.  A cell inside several lanelets carries the union of their sets.
+ *   The table is static map data, built on the host once per map.
+ *  A step q -> g = q + dir_k is allowed iff g is passable (the road metric's set, unchanged), bit k is set in out(q) AND bit k is
+ *   set in out(g): both ends decide -- a step only its origin allows would let oncoming traffic swerve into every cell of the
+ *   ego's lane.  Neighbour lanes of one direction share directions (lane changes stay possible), opposite lanes share none.
+ *  d_flow(g) = the cheapest path from a source over allowed steps, 12 per axis step and 17 per diagonal one, 0 on sources;
+ *   nothing is propagated beyond L[J-1]; 65535 = none.  Sources, window, hidden mask, the rule outside the window, L[j], A_geo,
+ *   d_arrival = max(A_geo, A_euclid), d_cells, d_first and d_slack are exactly those of fo_scene_hidden_reach_road with d_flow in
+ *   the place of d.  d_flow >= d (65535 the largest), hence A_flow >= A_road >= A_euclid; with a table of 0xFF everywhere
+ *   d_flow == d and every output equals that entry's bit for bit.
+ *  Not claimed: wrong-way drivers, U-turns and reversing vehicles are outside the model ("no driving against the lane").  The
+ *   occlusion memory is not given this metric: its hidden set is a superset of what a flow memory would keep, so it stays a
+ *   conservative source set.
+ *
+ * fo_scene_set_lane_moves: h_moves [rny][rnx] of the map's raster (fo_scene_map_info), one-off after fo_scene_set_map; the table
+ *  belongs to the map (a new fo_scene_set_map drops it) and is shared with it: upload it through the owner before
+ *  fo_scene_share_map, FO_E_STATE while the map has more than one reader.  NULL drops the table.
+ * fo_scene_hidden_reach_flow: the structure, outputs and refusals of fo_scene_hidden_reach_road (messages prefixed
+ *  "fo_scene_hidden_reach_flow:"), d_dist_or_null receives d_flow; FO_E_STATE, nothing launched, when the map has no move table.
+ *  Launches: the two of the Euclidean map, ceil(L[J-1] / 192) flow bands (at least one), the road entry's merge, one for the
+ *  trajectories with M > 0.
+ * fo_scene_hidden_clearance_flow: fo_scene_hidden_clearance with metric == FO_HIDDEN_CLEARANCE_ROAD (anything else: FO_E_ARG)
+ *  and key = max(169 D2, d_flow^2); the tie holds with fo_scene_hidden_reach_flow in the place of the road entry.  FO_E_STATE
+ *  without a move table. */
+int fo_scene_set_lane_moves(fo_ctx *ctx, const uint8_t *h_moves /* [rny][rnx] */);
+int fo_scene_hidden_reach_flow(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream);
+int fo_scene_hidden_clearance_flow(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

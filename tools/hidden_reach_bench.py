@@ -3,7 +3,9 @@ whole call, next to the visibility stage the forecast
 follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
-                                       [--clearance]
+                                       [--flow any|lanes] [--clearance]
+
+``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
 ``--clearance``: one ``hidden_clearance`` call at ``v_cap = --v-max`` plus ``.reach`` for three speeds (2, 7 m/s and the cap)
 against three ``hidden_reach`` calls at those speeds, and the clearance split by stage (key map alone, whole call with and
@@ -50,8 +52,11 @@ def main():
     ap.add_argument("--v-max", type=float, default=13.9)
     ap.add_argument("--calls", type=int, default=25)
     ap.add_argument("--metric", default="euclid", choices=("euclid", "road"), help="road: the reach follows the road (§5.10)")
+    ap.add_argument("--flow", default="any", choices=("any", "lanes"), help="lanes: hidden vehicles follow the lanes (needs --metric road)")
     ap.add_argument("--clearance", action="store_true", help="time hidden_clearance + .reach x 3 against three hidden_reach calls")
     a = ap.parse_args()
+    if a.flow == "lanes" and a.metric != "road":
+        ap.error("--flow lanes needs --metric road")
     if a.scene == "city_grid":
         sc = SC.synthetic_urban_grid()
     else:
@@ -77,23 +82,23 @@ def main():
         sm.launch(ego, yaw, timestep=step_no[0])
         step_no[0] += 1
 
-    res = {"scene": a.scene, "metric": a.metric, "M": M, "T": T, "memory": bool(a.memory), "window": [sm.window.nx, sm.window.ny],
+    res = {"scene": a.scene, "metric": a.metric, "flow": a.flow, "M": M, "T": T, "memory": bool(a.memory), "window": [sm.window.nx, sm.window.ny],
            "build": N.build_id()[:12], "device": torch.cuda.get_device_name(0)}
     res["visibility_stage_ms"] = _median_ms(stage, a.calls)
-    out = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric)
+    out = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric, flow=a.flow)
     res["halo_cells"] = int(math.isqrt(int(out.r2[-1])))
-    res["map_only_ms"] = _median_ms(lambda: sm.hidden_reach(e, e, e, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric), a.calls)
-    res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric), a.calls)
+    res["map_only_ms"] = _median_ms(lambda: sm.hidden_reach(e, e, e, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric, flow=a.flow), a.calls)
+    res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric, flow=a.flow), a.calls)
     res["future_visibility_720_first_seen_ms"] = _median_ms(
         lambda: sm.future_visibility_ex(tx, ty, None, t_stride=5, n_rays=720, first_seen=True), a.calls)
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
-        hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, **kw)
+        hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
         got = hc()
 
         def three_reach_calls():
             for v in speeds:
-                sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric)
+                sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric, flow=a.flow)
 
         def derive(c=got):
             for v in speeds:
@@ -106,12 +111,12 @@ def main():
         res["clearance_call_ms"] = _median_ms(hc, a.calls)
         res["clearance_call_reused_heading_ms"] = _median_ms(lambda: hc(heading=got.heading), a.calls)
         res["clearance_map_only_ms"] = _median_ms(
-            lambda: sm.hidden_clearance(e, e, e, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric), a.calls)
+            lambda: sm.hidden_clearance(e, e, e, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow), a.calls)
         res["three_reach_derivations_ms"] = _median_ms(derive, a.calls)
         res["critical_speed_ms"] = _median_ms(got.critical_speed, a.calls)
         # the two ways agree (exact integers), and what the critical speed says of the batch
         for v in speeds:
-            r = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric)
+            r = sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=v, dt=0.1, metric=a.metric, flow=a.flow)
             hit, f, sl = got.reach(v)
             assert torch.equal(hit, r.cells > 0) and torch.equal(f, r.first) and torch.equal(sl, r.slack), v
         vc = got.critical_speed()
