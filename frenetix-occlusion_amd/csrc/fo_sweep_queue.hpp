@@ -15,7 +15,13 @@ namespace {
 //   pass 2 (t loop)  harm + risk + running maxima + coalesced list stores, cp read back from cpbuf.
 // exp() for the logistic models is a 64-entry 2^(j/64) table + degree-5 polynomial (~15 VALU ops).
 // Supports T-1 <= TQ; longer horizons take the generic kernel.
-enum { HM_LR4S = 0, HM_DVMAX = 1, HM_GENERIC = 2 };   // pass-2 bodies by harm model (see dvmax_mode in the kernel)
+enum { HM_LR4S = 0, HM_DVMAX = 1, HM_GENERIC = 2 };   // per-agent bodies by harm model (see agent_body in the kernel)
+// What an agent's body is told about its harm model: hm_const<HM> -- a compile-time constant, one copy of the body per model
+// -- or hm_any, the model as a run-time value in a single copy (the horizon-split form).
+template <int HM> using hm_const = std::integral_constant<int, HM>;
+struct hm_any { int value; };
+template <class Tag> struct hm_fixed : std::true_type {};
+template <> struct hm_fixed<hm_any> : std::false_type {};
 constexpr int DVR = TC + 1;          // rows of the per-wave ring of relative speeds: samples t0-1 .. t1-1 are live at once
 constexpr int WROWS = TC + DVR;      // LDS rows (64 doubles each) per wave
 constexpr int QCAP = 128;
@@ -198,12 +204,25 @@ __device__ __forceinline__ cip_t fo_const(const int32_t *p) { return (cip_t)(uns
 // CORR: the agent set holds a covariance with correlation (status[1] of fo_prep_agents_kernel): in-gate samples then
 // add the correlation integral to their box probabilities (fo_corr_corners).  The kernel below carries both bodies and picks one at
 // its start, so that the usual diagonal case keeps the registers and the code it had.
+// Harm model: everything the body does per agent -- the DCE probe, both passes of every chunk, the pair outputs, the running
+// extrema -- is one generic lambda (agent_body) that takes the agent's harm model as a tag.  On the full grid it is
+// instantiated three times (hm_const<HM_LR4S | HM_DVMAX | HM_GENERIC>) and ONE wave-uniform three-way branch per agent picks
+// the copy: at three waves per SIMD every instruction and every taken branch of the sample loops is paid in full, and the
+// per-sample `is this agent LR4S` (three places in pass 1), the per-chunk choice of pass 2's body, the headings, the impact
+// classes and their re-rating are gone from the copies that do not need them (pass-1 loop of the headline instantiation: 485
+// -> 392 instructions, 136 -> 106 scalar, in the two non-LR4S copies).  The horizon-split form keeps ONE
+// copy with the model as a run-time value (hm_any): its workgroups live for one chunk per wave, where the flags cost nothing
+// that shows, and three copies there put 35-40 spilled VGPRs (96-112 B of scratch per lane) into the instantiations that
+// tests/test_kernel_shape_cpu.py holds to 48 B.
+// (Measured and dropped with it: a second copy of pass 1's sample loop without the two range tests, for chunks that lie wholly
+// inside the agent's prediction -- four instructions and two branches less per sample, but twice the pass-1 copies: 105
+// spilled VGPRs instead of 35 and scalar spills inside the loop, 0.533 / 0.542 ms against 0.497 / 0.500)
 template <bool PAIR, int LISTS, bool ALLM, bool SPLIT, bool CORR>
 __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const double2 *__restrict__ erf_tab,
                                                     const double *__restrict__ exp_tab, const double *__restrict__ zc_tab,
                                                     double *__restrict__ hk_all, double *__restrict__ cpbuf_all,
-                                                    unsigned short *__restrict__ queue_all, int *__restrict__ /* next_agent, see the kernel */,
-                                                    int *__restrict__ pool_i, double *__restrict__ pool_hd) {
+                                                    unsigned short *__restrict__ queue_all, int *__restrict__ pool_i,
+                                                    double *__restrict__ pool_hd) {
   constexpr int QCAPX = SPLIT ? TILE * TC : QCAP;           // queue entries per wave: a chunk's worth with the pool (pool_round)
   static_assert(!SPLIT || WROWS >= 10, "the horizon-split fold parks ten values per lane in the wave's rows");
   const int lane = threadIdx.x & 63;
@@ -364,12 +383,8 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
   // the samples this wave owns: everything, or time chunk `wave` of the agent the workgroup shares
   const int seg0 = SPLIT ? wave * TC : 0, seg1 = SPLIT ? min(seg0 + TC, a.T) : a.T;
   const int gfirst_ = max(seg0 - 1, 0);  // first harm / cp sample this wave evaluates for an agent
-  for (int kk = 0;; ++kk) {   // (written as `kk < apw_` in the loop header the product's device code changes)
-    int k;
-    {
-      if (kk >= apw_) break;
-      k = k0 + kk;
-    }
+  for (int kk = 0; kk < apw_; ++kk) {
+    const int k = k0 + kk;
     if (k >= A) break;
     const cdp_t G = fo_const(a.atab) + (size_t)k * a.Ta * NAF;
     const cdp_t C = fo_const(a.acst) + (size_t)k * NAC;
@@ -422,6 +437,14 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       continue;
     }
 
+    // Everything below runs once per agent, on the full grid in one of three copies chosen at the end of this loop body
+    // (wave-uniform): the harm model is a constant of the copy (HM; FIXED), so neither pass 1 nor pass 2 asks for it per sample
+    // or per chunk, and what only the LR4S model reads -- the headings, the impact classes and their re-rating on a class
+    // boundary -- is live in the LR4S copy alone.  (`lr4s` and `dvmax_mode` are plain constants rather than constexpr so that
+    // the horizon-split form can run the same text with the model as a run-time value.)
+    auto agent_body = [&](auto hm_tag) {
+    constexpr bool FIXED = hm_fixed<decltype(hm_tag)>::value;
+    const int HM = hm_tag.value;   // (a constant in the copies of the full grid)
     // Per-agent state that lives across the time chunks.
     // DCE (dce.py:69-99) = the minimum over t of the rounded rectangle distance and the EARLIEST t that attains it (the
     // reference's early stop at 0 only cuts samples after the first zero) -- a result that does not depend on the
@@ -510,11 +533,11 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     // fma(k, dv, c) is monotonic in dv and so is its rounding -- pass 1 keeps the running maximum of dv (as -dv in
     // nze_min, no new register) and pass 2 visits the gate rows only.  Wave-uniform.
     // (round 4: in EVERY output mode -- the per-wave ring holds the SQUARED relative speed, pass 1 takes no square root, and
-    // pass 2 runs one of three bodies chosen once per agent: HM_DVMAX for these agents, HM_LR4S, HM_GENERIC for the rest
+    // the agent runs in one of three bodies (agent_body's tag): HM_DVMAX for these agents, HM_LR4S, HM_GENERIC for the rest
     // -- agents without a harm model, speed coefficients of unusual sign.  With the lists the running maximum is kept by
     // pass 2, which walks every sample anyway; without them by pass 1, and pass 2 visits the gate rows only.  The maxima are
     // the same arithmetic in all three output modes: logistic at sqrt(max dv^2).)
-    const bool dvmax_mode = prot == 0 && C[10] <= 0.0 && C[11] <= 0.0 && !(FO_X & 8);
+    const bool dvmax_mode = HM == HM_DVMAX;
     // List stores: the three blocks (cp | harm pairs | risk pairs) from per-agent scalar bases plus two running 32-bit
     // lane offsets (element size 1x and 2x) -- no 64-bit address arithmetic per sample (fo_sweep_run sends batches whose
     // (T-1) M pair elements pass 4 GB to the generic kernel)
@@ -526,14 +549,14 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     unsigned lo1 = (unsigned)(gfirst_ * M + m) * LE, lo2 = (unsigned)(gfirst_ * M + m) * (2u * LE);
     // logistic arguments as one fma of dv: the speed coefficient times the mass split is folded per agent
     // (harm_model.py:96-97: ego_dv = m_obs/(m_ego+m_obs) dv, obs_dv = m_ego/(m_ego+m_obs) dv)
-    const bool lr4s = prot == 1;
+    const bool lr4s = HM == HM_LR4S;
     // The logistic slopes and offsets (fo_prep_agents_kernel) are wave-uniform, but the scalar registers are taken:
     // parked in LDS, pass 2 reads them back into vector registers that are free by then (held across pass 1 they would
     // cost eight VGPRs at its register peak).
     if (lane < 4) hk[lane] = a.acst[(size_t)k * NAC + 10 + lane];
     // LR4S impact classes (0 front, 1 side, 2 rear) of the ego's and the obstacle's occupants: two bits per sample,
     // slot t & 15 (a chunk and its predecessor's last sample are live at once: TC + 1 <= 16 slots)
-    unsigned cls_e = 0u, cls_o = 0u;
+    [[maybe_unused]] unsigned cls_e = 0u, cls_o = 0u;   // (the LR4S copy's)
 
     // The horizon is walked in chunks of TC iterations, two passes per chunk.
     //  pass 1, iteration t: everything that needs the poses -- DCE(t); the relative speed of sample t (harm_model.py:
@@ -551,7 +574,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
     // fetched it (its last iteration prefetches row t1): carried over pass 2, the 14 live registers cost more than the
     // wait of the loads behind that pass's list stores (float32 lists 0.562 against 0.552 ms).
     fo_d2 nxy, ncs, nvv;
-    double nth_ = 0.0;
+    [[maybe_unused]] double nth_ = 0.0;   // the ego's heading angle of the next sample: read by the LR4S copy only
     for (int t0 = seg0; t0 < seg1; t0 += TC) {
       const int t1 = min(t0 + TC, T);
       // A segment other than the first also needs the relative speed and the impact classes of the sample before it
@@ -595,12 +618,18 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       double px = gr0[0], py = gr0[1], npx = px, npy = py;
       // Only the mean of the next row is fetched a sample ahead (the first thing a sample needs); heading and velocity
       // are re-loaded IN PLACE right after their last use in a sample -- no second register set, no copies
-      double pc = gr0[2], ps = gr0[3], pyaw = gr0[4], pvx = gr0[8], pvy = gr0[9];
+      double pc = gr0[2], ps = gr0[3], pvx = gr0[8], pvy = gr0[9];
+      [[maybe_unused]] double pyaw = 0.0;   // the agent's heading angle only enters the LR4S model
+      if (!FIXED || lr4s) pyaw = gr0[4];
       // Scalar loads return out of order, so any use of an s_load result waits for lgkmcnt(0).  Pinning the per-agent
       // constants and the first rows here (an empty asm that names them as SGPR inputs) drains the counter before the
       // loop, which leaves the in-loop wait to cover only the row that was prefetched one iteration ago.
-      asm volatile("; scalar operands resident" ::"s"(hlB), "s"(hwB), "s"(hdev), "s"(Rsum), "s"(gate_far2), "s"(px),
-                   "s"(py), "s"(pc), "s"(ps), "s"(pvx), "s"(pvy), "s"(pyaw));
+      if (!FIXED || lr4s)
+        asm volatile("; scalar operands resident" ::"s"(hlB), "s"(hwB), "s"(hdev), "s"(Rsum), "s"(gate_far2), "s"(px),
+                     "s"(py), "s"(pc), "s"(ps), "s"(pvx), "s"(pvy), "s"(pyaw));
+      else
+        asm volatile("; scalar operands resident" ::"s"(hlB), "s"(hwB), "s"(hdev), "s"(Rsum), "s"(gate_far2), "s"(px),
+                     "s"(py), "s"(pc), "s"(ps), "s"(pvx), "s"(pvy));
       SW_STAMP(0);
       // rows t+1 as running 32-bit byte offsets from the (uniform) bases of this tile's and this agent's rows: one add
       // each per sample instead of a 64-bit multiply-add, and the loads take the base from scalar registers
@@ -610,7 +639,8 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
         // (Round 5, measured and dropped: the ego's velocity -- and heading -- of sample t asked for at the top of iteration t
         // instead of one iteration ahead with the pose -- three register pairs and three v_mov_b64 less per sample -- and no row
         // fetched ahead at all: 0.536-0.540 ms against 0.542, inside the noise, and 2 % slower together with the shorter erf step.)
-        const double ex = nxy.x, ey = nxy.y, ec = ncs.x, es = ncs.y, evx = nvv.x, evy = nvv.y, eth = nth_;
+        const double ex = nxy.x, ey = nxy.y, ec = ncs.x, es = ncs.y, evx = nvv.x, evy = nvv.y;
+        [[maybe_unused]] const double eth = nth_;
         {
           eoff += (unsigned)(NEF * TILE * sizeof(double));
           goff += (unsigned)(NAF * sizeof(double));
@@ -758,8 +788,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       if (SPLIT) pool_round(qn, k, hdev, gbase);
       else if (qn > 0) process(qn);
       wgate = __builtin_amdgcn_readfirstlane(wgate);  // uniform by construction; says so to the register allocator
-      const unsigned wband = wgate >> 16;
-      if (lr4s && wband) {
+      if (const unsigned wband = wgate >> 16; lr4s && wband) {
         // Impact angles on a class boundary to within rounding: the reference's own floating-point route (float64 atan2,
         // the subtraction, the comparison with 45/180 pi; harm_model.py:86-90, logistic_regression.py:28-42) decides
         // those samples -- here, outside the loop whose registers a float64 atan2 does not fit into.
@@ -960,9 +989,10 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
           for (; t < g1s; ++t) row_step(t, std::false_type{});
           }
         };
-        if (lr4s) pass2(std::integral_constant<int, HM_LR4S>{});
-        else if (dvmax_mode) pass2(std::integral_constant<int, HM_DVMAX>{});
-        else pass2(std::integral_constant<int, HM_GENERIC>{});
+        if constexpr (FIXED) pass2(hm_tag);
+        else if (lr4s) pass2(hm_const<HM_LR4S>{});
+        else if (dvmax_mode) pass2(hm_const<HM_DVMAX>{});
+        else pass2(hm_const<HM_GENERIC>{});
       }
       SW_STAMP(2);
     }
@@ -1005,7 +1035,7 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       }
       // more agents to come: the other waves' rows are theirs again once wave 0 has read them
       if (kk + 1 < apw_ && k + 1 < A) __syncthreads();
-      if (wave > 0) continue;
+      if (wave > 0) return;
     }
     SW_STAMP(3);
     // ------------------------------------------------------------------ per-pair scalars
@@ -1070,6 +1100,15 @@ __device__ __forceinline__ void fo_sweep_queue_body(const SweepArgs a, const dou
       w_max_cp = fo_vmax(w_max_cp, max_cp);
       w_max_hwc = fo_vmax(w_max_hwc, hwc);
     }
+    };
+    // the one place that asks for the agent's harm model (wave-uniform): LR4S; the two-coefficient models (pedestrian, LR1S:
+    // prot == 0) with the usual signs of the speed coefficients; everything else -- agents without a harm model, speed
+    // coefficients of unusual sign
+    const bool dvmax_ = prot == 0 && C[10] <= 0.0 && C[11] <= 0.0 && !(FO_X & 8);
+    if constexpr (SPLIT) agent_body(hm_any{prot == 1 ? HM_LR4S : dvmax_ ? HM_DVMAX : HM_GENERIC});
+    else if (prot == 1) agent_body(hm_const<HM_LR4S>{});
+    else if (dvmax_) agent_body(hm_const<HM_DVMAX>{});
+    else agent_body(hm_const<HM_GENERIC>{});
   }
 
   // ---------------- combine the waves of the workgroup (ascending agent order); scratch aliases the cp buffers
@@ -1133,8 +1172,6 @@ void fo_sweep_queue_kernel(const SweepArgs a) {
   __shared__ unsigned short queue_all[QWAVES * (SPLIT ? TILE * TC : QCAP)];   // per wave: in-gate samples (lane | row << 6)
   __shared__ int pool_i[3 * QWAVES];       // pool_round, per wave: queue length, agent, gate sample of buffer row 0
   __shared__ double pool_hd[QWAVES];       //             half the agent's inflated length
-  __shared__ int next_agent;   // unused; without it and its store the product's device code changes
-  if (threadIdx.x == 0) next_agent = 0;
   {
     // The two tables into LDS.  All of a thread's loads are issued before the first store (written as a loop the copy
     // compiles to five dependent round trips: load, wait, store, ...).  (A build WITHOUT the copy is no measure of its
@@ -1167,9 +1204,9 @@ void fo_sweep_queue_kernel(const SweepArgs a) {
   if (a.trace && threadIdx.x == 0) a.trace[4 * (size_t)blockIdx.x + 3] = wall_clock64();   // tables in LDS
 #endif
   if (__builtin_expect(!corr, 1))
-    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, false>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
+    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, false>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, pool_i, pool_hd);
   else
-    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, true>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, &next_agent, pool_i, pool_hd);
+    fo_sweep_queue_body<PAIR, LISTS, ALLM, SPLIT, true>(a, erf_tab, exp_tab, zc_tab, hk_all, cpbuf_all, queue_all, pool_i, pool_hd);
 #if FO_TRACE
   if (a.trace && threadIdx.x == 0) a.trace[4 * (size_t)blockIdx.x + 1] = wall_clock64();
 #endif
