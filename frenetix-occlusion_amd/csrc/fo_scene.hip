@@ -35,6 +35,8 @@
 //   fo_occlusion_memory.hpp  fo_occlusion_memory_kernel  occlusion memory, an extension: one launch between the settlement and
 //                                            the compaction when armed (fo_occlusion_memory_road_kernel, the road metric:
 //                                            fo_occlusion_memory_road.hpp)
+//   fo_occlusion_memory_flow.hpp  fo_occlusion_memory_flow_kernel  its vehicle layer: a second hidden set bound to the lanes'
+//                                            driving direction, one more launch behind the memory's when armed
 //   fo_future_visibility.hpp fo_future_visibility_kernel  an extension outside the step: what a candidate trajectory comes to see
 //   fo_hidden_reach.hpp      fo_hr_*_kernel  hidden-traffic reach forecast, an extension outside the step
 //   fo_hidden_reach_road.hpp fo_hr_road_*_kernel  its road metric: distance bands along the road, arrival merge
@@ -56,6 +58,7 @@
 #include "fo_scene_compact.hpp"
 #include "fo_spawn_predict.hpp"
 #include "fo_occlusion_memory.hpp"
+#include "fo_occlusion_memory_flow.hpp"
 #include "fo_spawn_rules.hpp"
 
 // (fo_reserve's instantiations are part of the library's dynamic symbols; this one has a single caller, which would inline it away)
@@ -352,6 +355,8 @@ static int scene_visibility(fo_ctx *ctx, const fo_step_t &p, void *stream, const
   sc->cand_flags_ready = false;
   const bool om_on = sc->om_armed;   // (fo_scene_set_occlusion_memory arms this call only)
   sc->om_armed = false;
+  const bool ov_on = om_on && sc->ov_armed;   // (the vehicle layer rides on the main memory of the same stage)
+  sc->ov_armed = false;
   const int O = p.O;
   if (p.n_rays < 4 || !p.d_dirs || !p.d_range || !p.d_hit_id || O < 0 || (O > 0 && (!p.d_ocorn || !p.d_ocen || !p.d_oflags)) ||
       p.win_nx < 1 || p.win_ny < 1 || !p.d_cls || !p.d_occ_idx || !p.d_n_occ || !(p.r > 0))
@@ -369,6 +374,11 @@ static int scene_visibility(fo_ctx *ctx, const fo_step_t &p, void *stream, const
   if (om_on && sc->om.cur_bytes < (int64_t)cells)
     return fo_fail(ctx, FO_E_ARG, "fo_scene_visibility: the occlusion memory's buffer holds %lld bytes, the window %d cells",
                    (long long)sc->om.cur_bytes, cells);
+  if (ov_on && sc->ov.cur_bytes < (int64_t)cells)
+    return fo_fail(ctx, FO_E_ARG, "fo_scene_visibility: the vehicle layer's buffer holds %lld bytes, the window %d cells",
+                   (long long)sc->ov.cur_bytes, cells);
+  if (ov_on && !m->d_lane_moves)
+    return fo_fail(ctx, FO_E_STATE, "fo_scene_visibility: the vehicle layer is armed and the map has lost its move table");
   if ((rc = ensure_cells(ctx, sc, (size_t)cells))) return rc;
   const FanArgs fan = fan_in ? *fan_in : FanArgs();
   fo_prep_args_t prep = prep_in ? *prep_in : fo_prep_args_t();
@@ -395,6 +405,7 @@ static int scene_visibility(fo_ctx *ctx, const fo_step_t &p, void *stream, const
     launch_settle(m, sc, p, nw, far, s);
   }
   if (om_on) launch_occlusion_memory(sc, p, s);
+  if (ov_on) launch_occlusion_memory_flow(sc, p, s);
   FO_HIP_TRY(ctx, hipGetLastError());
   if (!sf_in) return compact(ctx, sc, sc->d_flags, sc->d_blk, cells, p.d_occ_idx, p.d_n_occ, s);
   if ((rc = fo_reserve(ctx, &sc->d_flags2, &sc->cap_cells2, (size_t)cells))) return rc;
@@ -427,7 +438,7 @@ int fo_scene_visibility(fo_ctx *ctx, double ego_x, double ego_y, double head_x, 
 // fo_scene_set_occlusion_memory / _road: the same structure, checks and refusals; the later call decides the metric
 static int set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om, bool road, const char *fn) {
   if (!ctx) return FO_E_ARG;
-  if (ctx->scene) ((Scene *)ctx->scene)->om_armed = false;
+  if (ctx->scene) ((Scene *)ctx->scene)->om_armed = ((Scene *)ctx->scene)->ov_armed = false;   // (a main arming call drops the vehicle layer)
   if (!om) return FO_OK;   // off
   if (!ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
   Scene *sc = (Scene *)ctx->scene;
@@ -455,6 +466,37 @@ int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om) 
 
 int fo_scene_set_occlusion_memory_road(fo_ctx *ctx, const fo_occlusion_memory_t *om) {
   return set_occlusion_memory(ctx, om, true, "fo_scene_set_occlusion_memory_road");
+}
+
+// the vehicle layer: valid on top of an armed main memory only, and only with the map's move table
+int fo_scene_set_occlusion_memory_vehicles(fo_ctx *ctx, const fo_occlusion_memory_t *vm) {
+  const char *fn = "fo_scene_set_occlusion_memory_vehicles";
+  if (!ctx) return FO_E_ARG;
+  if (ctx->scene) ((Scene *)ctx->scene)->ov_armed = false;
+  if (!vm) return FO_OK;   // off
+  if (!ctx->scene) return fo_fail(ctx, FO_E_STATE, "%s: call fo_scene_set_map first", fn);
+  Scene *sc = (Scene *)ctx->scene;
+  if (!sc->om_armed)
+    return fo_fail(ctx, FO_E_STATE, "%s: arm the main memory of the stage first (fo_scene_set_occlusion_memory or its _road form)", fn);
+  if (!sc->map->d_lane_moves) return fo_fail(ctx, FO_E_STATE, "%s: the map has no move table (call fo_scene_set_lane_moves first)", fn);
+  constexpr int cap = FO_OCCLUSION_MEMORY_MAX_HALO;
+  if (vm->r2 < 0 || vm->r2 > cap * cap)
+    return fo_fail(ctx, FO_E_ARG, "%s: r2 = %d outside [0, %d] (a reach of at most %d cells)", fn, vm->r2, cap * cap, cap);
+  if ((vm->reset != 0) != (sc->om.reset != 0))
+    return fo_fail(ctx, FO_E_ARG, "%s: reset = %d, the main memory's is %d (both sets reset together)", fn, vm->reset, sc->om.reset);
+  if (vm->r2 > sc->om.r2)
+    return fo_fail(ctx, FO_E_ARG, "%s: r2 = %d above the main memory's %d (V would not stay inside H)", fn, vm->r2, sc->om.r2);
+  if (!vm->d_cur || vm->cur_bytes < 1 || vm->d_cur == sc->om.d_cur) return fo_fail(ctx, FO_E_ARG, "%s: no buffer of its own for this step", fn);
+  if (!vm->reset) {
+    if (!vm->d_prev || vm->d_prev == vm->d_cur || vm->prev_nx < 1 || vm->prev_ny < 1)
+      return fo_fail(ctx, FO_E_ARG, "%s: the previous step needs a window and a buffer of its own", fn);
+    if (vm->prev_bytes < (int64_t)vm->prev_nx * vm->prev_ny)
+      return fo_fail(ctx, FO_E_ARG, "%s: the previous buffer holds %lld bytes, its window %d x %d cells",
+                     fn, (long long)vm->prev_bytes, vm->prev_nx, vm->prev_ny);
+  }
+  sc->ov = *vm;
+  sc->ov_armed = true;
+  return FO_OK;
 }
 
 int fo_scene_future_visibility(fo_ctx *ctx, int M, int T, const double *d_x, const double *d_y, int t_stride, int n_rays,

@@ -16,6 +16,7 @@ constexpr int FV_THREADS = 256;            // threads per pose of the future vis
 constexpr int HRR_HALO = 16;               // ring staged around a tile of the road distance = steps a band can hold
 constexpr int HRR_BAND = 12 * HRR_HALO;    // B: distance units per band launch (12 per axis step)
 constexpr int OMR_SMALL_N = 16;            // largest halo of the road occlusion memory's small form
+constexpr int OMF_SMALL_N = 16;            // ... and of its vehicle layer's (a lane per staged column: 32 + 2 n <= 64)
 
 // ... or one: the boundary soup is a single group of chunk boxes (<= 64 chunks = 4 096 pieces: only the first wave of five would
 // have pieces to scan) and the obstacle sides fit a wave; forced: FO_SCENE_FIVE_WAVES is set
@@ -47,5 +48,7 @@ inline int road_steps(int L) { return L / 12; }
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)
 inline bool omr_small(int n) { return n <= OMR_SMALL_N; }
+// the vehicle layer's form (fo_occlusion_memory_flow_kernel) by the same halo
+inline bool omf_small(int n) { return n <= OMF_SMALL_N; }
 
 }  // namespace

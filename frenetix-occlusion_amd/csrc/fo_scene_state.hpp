@@ -105,6 +105,9 @@ struct Scene {
   bool om_armed = false;
   bool om_road = false;   // the armed call asked for the road metric (fo_scene_set_occlusion_memory_road)
   fo_occlusion_memory_t om{};
+  // its vehicle layer (fo_scene_set_occlusion_memory_vehicles): armed on top of an armed main memory, for the same stage only
+  bool ov_armed = false;
+  fo_occlusion_memory_t ov{};
   // hidden-traffic reach forecast (fo_scene_hidden_reach): row distances of the grown window, allocated by its first call
   uint8_t *d_hr_g = nullptr;
   size_t cap_hr_g = 0;

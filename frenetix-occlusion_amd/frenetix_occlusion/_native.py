@@ -36,6 +36,7 @@ EXPORTS = [
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
+    "fo_scene_set_occlusion_memory_vehicles",
 ]
 
 
@@ -220,6 +221,7 @@ def load():
     lib.fo_scene_set_shadow_length.argtypes = [vp, C.c_double]
     lib.fo_scene_set_occlusion_memory.argtypes = [vp, C.POINTER(OcclusionMemory)]
     lib.fo_scene_set_occlusion_memory_road.argtypes = [vp, C.POINTER(OcclusionMemory)]
+    lib.fo_scene_set_occlusion_memory_vehicles.argtypes = [vp, C.POINTER(OcclusionMemory)]
     lib.fo_scene_spawn_rule_agents.argtypes = ([vp, C.c_int, dp, ip, C.c_int, C.POINTER(RuleAgentTypes), C.c_int, dp, C.c_int]
                                                + [D] * 3 + [dp] * 8 + [ip, ip, vp])
     for name in EXPORTS:

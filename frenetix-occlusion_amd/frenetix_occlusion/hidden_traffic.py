@@ -46,7 +46,8 @@ class HiddenReach:
     ``first [M]`` int32 -- the first such sample, -1 = none; ``slack [M]`` int32 -- min over samples and footprint cells of
     (arrival - k), ``SLACK_NONE`` where the trajectory meets no reachable cell (``slack <= 0`` iff ``first >= 0``).
     ``r2`` (host int32 [J]) is the reach table, ``heading`` the (cos, sin) [M, T, 2] the footprints were turned by,
-    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step.  ``metric``: "euclid" (reach as
+    ``from_memory`` whether the sources were the occlusion memory's hidden set of this step, ``from_vehicle_memory`` whether
+    that set was the memory's vehicle layer V (``flow="lanes"`` with ``enable_occlusion_memory(vehicles="lanes")``).  ``metric``: "euclid" (reach as
     a disc around every hidden cell) or "road" (that, and no earlier than the distance along passable cells allows);
     ``reach`` (host int32 [J]) is the table in road-distance units (:func:`hidden_reach_road_units`), ``road_dist [ny, nx]``
     uint16 the road distance itself, 65535 = impassable or beyond ``reach[-1]`` (None for "euclid").  ``flow``: "any" (a hidden
@@ -60,6 +61,7 @@ class HiddenReach:
     window: CellWindow
     heading: Optional[torch.Tensor] = None
     from_memory: bool = False
+    from_vehicle_memory: bool = False      # ... and that set was its vehicle layer V, not H (flow="lanes" only)
     metric: str = "euclid"
     reach: Optional[np.ndarray] = None
     road_dist: Optional[torch.Tensor] = None
@@ -77,7 +79,8 @@ class HiddenClearance:
     distance (65535 = impassable or beyond ``isqrt(169 r2_cap)``; None for "euclid"); ``heading`` the (cos, sin) [M, T, 2] the
     footprints were turned by (hand it to a later call of the same candidates as ``heading=``); ``r2_cap`` the cap in squared
     cells: every reach table whose last entry is ``<= r2_cap`` is served.  ``dt``, ``margin``, ``cell_size`` are what the
-    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set.  ``flow``:
+    tables of :meth:`reach` are made of, ``from_memory`` whether the sources were the occlusion memory's hidden set
+    (``from_vehicle_memory``: its vehicle layer V).  ``flow``:
     "any", or "lanes" -- ``d`` is the distance over the steps the lanes' driving direction allows (``d_flow``, which ``dist`` then holds).
 
     For any such table ``A(g) <= j`` iff ``key(g) <= 169 R2[j]``, so ``cells > 0``, ``first`` and ``slack`` of
@@ -94,6 +97,7 @@ class HiddenClearance:
     margin: float = 0.0
     cell_size: float = 0.5
     from_memory: bool = False
+    from_vehicle_memory: bool = False      # ... and that set was its vehicle layer V, not H (flow="lanes" only)
     flow: str = "any"
 
     NONE = 2 ** 31 - 1
@@ -193,11 +197,15 @@ def _prepare(self, entry, v_name, *, x, y, theta, vehicle, v, dt, margin, inflat
     heading = N.on_device(unit_headings(theta) if heading is None else heading, dev)
     tlen = None if lengths is None else N.on_device(lengths, dev, "int32")
     w = self.window
-    hidden = self._om.hidden_on_device(w)
+    # lane-abiding vehicles start from the occlusion memory's vehicle layer when it ran in this step's stage, every other
+    # question from H, as before (flow="any" never reads V)
+    vehicles = self._om.hidden_vehicles_on_device(w) if flow == "lanes" else None
+    hidden = vehicles if vehicles is not None else self._om.hidden_on_device(w)
     fields = dict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(heading), d_len_or_null=N.ptr(tlen), hl=hl, hw=hw, wb=wb,
                   d_cls=self.cell_class.data_ptr(), d_hidden_or_null=N.ptr(hidden), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
                   win_ny=w.ny)
-    return SimpleNamespace(M=M, T=T, dt=dt, margin=margin, r2=r2, x=tx, y=ty, heading=heading, lengths=tlen, hidden=hidden, fields=fields)
+    return SimpleNamespace(M=M, T=T, dt=dt, margin=margin, r2=r2, x=tx, y=ty, heading=heading, lengths=tlen, hidden=hidden, fields=fields,
+                           from_vehicles=vehicles is not None)
 
 
 def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, metric="euclid", flow="any"):
@@ -229,7 +237,7 @@ def hidden_reach(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=
     entry = "fo_scene_hidden_reach" if dist is None else "fo_scene_hidden_reach_flow" if flow == "lanes" else "fo_scene_hidden_reach_road"
     self.ctx.call(entry, C.byref(args), N.current_stream(self._dev_index))
     self._hr_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in future_visibility_ex)
-    return HiddenReach(arrival, cells, first, slack, r2, w, q.heading, q.hidden is not None, metric,
+    return HiddenReach(arrival, cells, first, slack, r2, w, q.heading, q.hidden is not None, q.from_vehicles, metric,
                        hidden_reach_road_units(r2), dist, flow)
 
 
@@ -256,4 +264,4 @@ def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, infl
                   N.current_stream(self._dev_index))
     self._hc_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in hidden_reach)
     return HiddenClearance(key, qmin, dist, w, q.heading, r2_cap, metric, q.dt, q.margin, self.cell_size, q.hidden is not None,
-                           flow)
+                           q.from_vehicles, flow)

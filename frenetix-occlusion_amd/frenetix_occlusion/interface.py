@@ -55,6 +55,17 @@ def occlusion_memory_metric(acc):
     return metric
 
 
+def occlusion_memory_vehicles(acc):
+    """``accelerator.occlusion_memory_vehicles`` of a loaded configuration: ``"off"`` (the default) or ``"lanes"``; YAML reads a
+    bare ``off`` as False, which counts as ``"off"``"""
+    vehicles = (acc or {}).get("occlusion_memory_vehicles", "off")
+    if vehicles is None or vehicles is False:
+        vehicles = "off"
+    if vehicles not in ("off", "lanes"):
+        raise ValueError(f"accelerator.occlusion_memory_vehicles: 'off' or 'lanes', not {vehicles!r}")
+    return vehicles
+
+
 class FOInterface:
     def __init__(self, scenario, reference_path, vehicle_params, dt, config_path=None, cosy_cl=None, share_map_with=None):
         """Signature of the reference (interface.py:69) plus ``share_map_with``: another FOInterface of the same scenario
@@ -125,10 +136,12 @@ class FOInterface:
         # could have got there are no longer occluded (SensorModel.enable_occlusion_memory)
         self.occlusion_memory = occlusion_memory_config(acc)
         self.occlusion_memory_metric = occlusion_memory_metric(acc)
+        self.occlusion_memory_vehicles = occlusion_memory_vehicles(acc)
         if self.occlusion_memory["enabled"]:
             self.sensor_model.enable_occlusion_memory(v_max=self.occlusion_memory["v_max"],
                                                       margin=self.occlusion_memory["margin"], dt=self.dt,
-                                                      metric=self.occlusion_memory_metric)
+                                                      metric=self.occlusion_memory_metric,
+                                                      vehicles=self.occlusion_memory_vehicles)
 
     # ---------------------------------------------------------------------------------------- reference API
     def reset_occlusion_memory(self):

@@ -20,7 +20,7 @@ from .utils import fo_obstacle as R      # (the obstacle row layout)
 # the names this module has always exported (tests, tools, interface.py and the docs import them from here)
 from .fan_geometry import ROAD, VISIBLE, OCCLUDED, HoleIndex, footprint_polygon, footprint_ranges, half_fan_dirs, ray_dirs  # noqa: F401
 from .cell_window import CellWindow, VisibleArea  # noqa: F401
-from .occlusion_memory import OCCLUSION_MEMORY_METRICS, OcclusionMemory, OcclusionMemoryPlan, occlusion_memory_r2  # noqa: F401
+from .occlusion_memory import OCCLUSION_MEMORY_METRICS, OCCLUSION_MEMORY_VEHICLES, OcclusionMemory, OcclusionMemoryPlan, occlusion_memory_r2  # noqa: F401
 from .future_visibility import FutureVisibility  # noqa: F401
 from .hidden_traffic import HIDDEN_REACH_FLOWS, HIDDEN_REACH_METRICS, HiddenClearance, HiddenReach, hidden_reach_r2, hidden_reach_road_units, unit_headings  # noqa: F401
 
@@ -193,21 +193,32 @@ class SensorModel:
                       off.ctypes.data, lan.ctypes.data, kind.ctypes.data)
 
     # ---- occlusion memory (extension; state and bodies: occlusion_memory.OcclusionMemory)
-    def enable_occlusion_memory(self, enabled=True, v_max=13.9, margin=None, dt=0.1, metric="euclid"):
+    def enable_occlusion_memory(self, enabled=True, v_max=13.9, margin=None, dt=0.1, metric="euclid", vehicles="off"):
         """keep road cells seen empty out of the occluded area until a hidden road user moving at ``v_max`` (m/s) could
         have reached them; ``margin`` (m, None = sqrt(2) cell sizes) widens the reach, ``dt`` is the length of one
         timestep (s).  Every step with a timestep then advances the memory; the first step after this call is a reset.
         ``metric``: ``"euclid"`` (the disc, also across cells that are not road) or ``"road"`` (the disc and the distance
-        along passable cells, DESIGN.md §5.9 "Road metric": hidden traffic does not cross a building block)."""
+        along passable cells, DESIGN.md §5.9 "Road metric": hidden traffic does not cross a building block).
+        ``vehicles``: ``"off"``, or ``"lanes"`` -- a second hidden set V is kept next to H for vehicles that obey the driving
+        direction of the lanes (DESIGN.md §5.9 "Vehicle layer"; it needs the map's move table ``lane_moves``).  V masks nothing:
+        classes, occluded cells and phantoms stay those of ``vehicles="off"``; ``hidden_reach`` / ``hidden_clearance`` with
+        ``flow="lanes"`` start from V instead of H."""
         if metric not in OCCLUSION_MEMORY_METRICS:
             raise ValueError(f"occlusion memory: metric must be one of {OCCLUSION_MEMORY_METRICS}, not {metric!r}")
-        self._om.configure(OcclusionMemoryPlan(v_max, margin, self.cell_size, dt) if enabled else None, metric)
+        if vehicles not in OCCLUSION_MEMORY_VEHICLES:
+            raise ValueError(f"occlusion memory: vehicles must be one of {OCCLUSION_MEMORY_VEHICLES}, not {vehicles!r}")
+        if enabled and vehicles == "lanes" and getattr(self, "lane_moves", None) is None:
+            raise ValueError("occlusion memory: vehicles='lanes' needs the map's move table, and this model has none "
+                             "(it was built without lanelets)")
+        self._om.configure(OcclusionMemoryPlan(v_max, margin, self.cell_size, dt) if enabled else None, metric, vehicles)
 
     # read-only views of the memory's state: on / off, "euclid" | "road", why the last step was a reset (None: it was none), H
     occlusion_memory_enabled = property(lambda self: self._om.plan is not None)
     occlusion_memory_metric = property(lambda self: self._om.metric)
     occlusion_memory_reset_reason = property(lambda self: self._om.reset_reason)
     occlusion_memory_hidden = property(lambda self: self._om.hidden())
+    occlusion_memory_vehicles = property(lambda self: self._om.vehicles)                  # "off" | "lanes"
+    occlusion_memory_hidden_vehicles = property(lambda self: self._om.hidden_vehicles())  # V, None while the layer is off
 
     def reset_occlusion_memory(self):
         """forget what was seen: the next step's occluded cells are those of a step without memory"""

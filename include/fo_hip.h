@@ -266,6 +266,24 @@ int fo_scene_set_occlusion_memory(fo_ctx *ctx, const fo_occlusion_memory_t *om);
  * call's kernel).  Otherwise one launch of fo_occlusion_memory_road_kernel in place of the disc kernel. */
 int fo_scene_set_occlusion_memory_road(fo_ctx *ctx, const fo_occlusion_memory_t *om);
 
+/* EXTENSION: the vehicle layer of the occlusion memory (DESIGN.md §5.9 "Vehicle layer"): a second hidden set V kept next to H,
+ * for vehicles that obey the driving direction of the lanes.  It masks nothing: class bytes, occluded list and H of the stage
+ * are those of the stage without it.  The same structure; d_prev / d_cur are V of the previous / of this step, the window
+ * fields as above.  Valid only AFTER one of the two calls above has armed the main memory of the same stage; a later one of
+ * those calls drops it; it too arms the NEXT visibility stage only, NULL disarms, a failed stage disarms.  Integers only.
+ *  PV = V of the previous step inside its window, the road raster outside it, 0 off the raster; PassV(q) = PV(q) or road(q).
+ *  A step q -> g = q + dir_j (j * 45 degrees) is allowed iff PassV(g), bit j of out(q) AND bit j of out(g); out = the map's move
+ *   byte (fo_scene_set_lane_moves), 0xFF off the raster.  d_flow(g) = the cheapest path from a cell of PV over allowed steps, 12
+ *   per axis step, 17 per diagonal one, 0 on PV.
+ *  An occluded cell keeps V(g) = 1 iff PV(g + d) = 1 for some dx^2 + dy^2 <= r2 AND d_flow(g) <= isqrt(169 r2); visible cells
+ *   give 0, cells that are neither the road bit.  reset != 0: V = H of a reset step.  Cell by cell V <= H (the stage reads H of
+ *   this step and writes V = 0 wherever H = 0).
+ * One launch of fo_occlusion_memory_flow_kernel behind the main memory's.
+ * FO_E_STATE: no map, no armed main memory, no move table.  FO_E_ARG: no context, r2 outside [0, FO_OCCLUSION_MEMORY_MAX_HALO^2]
+ * or above the main memory's r2, reset different from the main memory's, buffers as above (d_cur must not be the main d_cur);
+ * the visibility stage returns FO_E_ARG when cur_bytes < win_nx * win_ny. */
+int fo_scene_set_occlusion_memory_vehicles(fo_ctx *ctx, const fo_occlusion_memory_t *vm);
+
 /* EXTENSION, not part of the reference: how much of the currently occluded area each candidate trajectory
  * will come to see.  d_x / d_y [M][T] as for fo_sweep_run; pose (m, k) = sample k * t_stride, K = ceil(T / t_stride).
  * From every pose a full fan of n_rays (<= 768: the 720-ray fan of the visibility stage fits) rays of length r along d_dirs [n_rays][2] (world-aligned, counter-
