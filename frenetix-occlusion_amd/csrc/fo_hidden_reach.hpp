@@ -172,13 +172,15 @@ struct HrTrajArgs {
   int32_t *cells, *first, *slack;       // [M][T], [M], [M]
 };
 
-// The footprint of pose i of the trajectory arrays of `a` (HrTrajArgs, or the clearance's arguments: the same field names):
-// every world-raster cell of the rectangle's bounding box (one cell of slack, clipped to [lox, hix] x [loy, hiy]) whose centre
-// passes the float64 point-in-rectangle test gets f(v), v = map[cell] inside the window, outside it 0 on raster road and
-// `none` elsewhere.  The ONE statement of the test on the device: the reach and the clearance kernel both scan with it.
+// The footprint of pose i of the trajectory arrays of `a` (HrTrajArgs, or the clearance's / the witness' arguments: the same field
+// names): every world-raster cell of the rectangle's bounding box (one cell of slack, clipped to [lox, hix] x [loy, hiy]) whose
+// centre passes the float64 point-in-rectangle test gets f(v, gx, gy), v = map[cell] inside the window, outside it 0 on raster
+// road and `none` elsewhere, (gx, gy) the cell's raster indices.  Of the box's rows a caller takes row0, row0 + row_step, ...:
+// the lanes that share a pose split its rows (fo_hidden_witness.hpp).  The ONE statement of the test on the device: the reach,
+// the clearance and the witness kernel all scan with it.
 template <class Args, class V, class F>
-__device__ __forceinline__ void fo_hr_scan_footprint(const Args &a, size_t i, const V *__restrict__ map, int none, int lox, int loy,
-                                                     int hix, int hiy, F &&f) {
+__device__ __forceinline__ void fo_hr_scan_footprint_rows(const Args &a, size_t i, const V *__restrict__ map, int none, int lox,
+                                                          int loy, int hix, int hiy, int row0, int row_step, F &&f) {
   const double c = a.heading[2 * i], s = a.heading[2 * i + 1];
   const double cx = a.x[i] + a.wb * c, cy = a.y[i] + a.wb * s;
   const double bx = fabs(c) * a.hl + fabs(s) * a.hw, by = fabs(s) * a.hl + fabs(c) * a.hw;
@@ -194,7 +196,7 @@ __device__ __forceinline__ void fo_hr_scan_footprint(const Args &a, size_t i, co
     gx0 = gx0 < lox ? lox : gx0; gx1 = gx1 > hix ? hix : gx1;
     gy0 = gy0 < loy ? loy : gy0; gy1 = gy1 > hiy ? hiy : gy1;
   }
-  for (int gy = gy0; gy <= gy1; ++gy) {
+  for (int gy = gy0 + row0; gy <= gy1; gy += row_step) {
     const double ey = (a.ry0 + ((double)gy + 0.5) * a.cs) - cy;
     const int wy = gy - a.iy0;
     const bool row_in = wy >= 0 && wy < a.ny, row_on = gy >= 0 && gy < a.rny;
@@ -206,9 +208,16 @@ __device__ __forceinline__ void fo_hr_scan_footprint(const Args &a, size_t i, co
       int v = none;
       if (row_in && wx >= 0 && wx < a.nx) v = map[wy * a.nx + wx];
       else if (row_on && gx >= 0 && gx < a.rnx) v = a.raster[(size_t)gy * a.rnx + gx] ? 0 : none;
-      f(v);
+      f(v, gx, gy);
     }
   }
+}
+
+// every row, the value alone: the scan of a lane that has a pose to itself
+template <class Args, class V, class F>
+__device__ __forceinline__ void fo_hr_scan_footprint(const Args &a, size_t i, const V *__restrict__ map, int none, int lox, int loy,
+                                                     int hix, int hiy, F &&f) {
+  fo_hr_scan_footprint_rows(a, i, map, none, lox, loy, hix, hiy, 0, 1, [&](int v, int, int) { f(v); });
 }
 
 __global__ __launch_bounds__(HR_THREADS) void fo_hr_traj_kernel(const HrTrajArgs a) {

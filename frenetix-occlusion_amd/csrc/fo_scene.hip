@@ -41,6 +41,7 @@
 //   fo_hidden_reach.hpp      fo_hr_*_kernel  hidden-traffic reach forecast, an extension outside the step
 //   fo_hidden_reach_road.hpp fo_hr_road_*_kernel  its road metric: distance bands along the road, arrival merge
 //   fo_hidden_reach_flow.hpp fo_hr_flow_band_kernel  the road metric bound to the lanes' driving direction: directed distance bands
+//   fo_hidden_witness.hpp    fo_hr_witness_kernel  the route behind each candidate's finding: conflict cell, walk back along d
 //   fo_hidden_clearance.hpp  fo_hc_*_kernel  hidden-traffic clearance: the key map behind every reach table, its minimum per pose
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
@@ -51,6 +52,7 @@
 #include "fo_hidden_reach.hpp"
 #include "fo_hidden_reach_road.hpp"
 #include "fo_hidden_reach_flow.hpp"
+#include "fo_hidden_witness.hpp"
 #include "fo_hidden_clearance.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
@@ -559,9 +561,21 @@ static int hr_check_scene(fo_ctx *ctx, const void *p, const char *fn) {
   return FO_OK;
 }
 
+static int hr_check_extent(fo_ctx *ctx, int nx, int ny, const char *fn) {
+  if (nx < 1 || ny < 1 || nx > 32768 || ny > 32768) return fo_fail(ctx, FO_E_ARG, "%s: window %d x %d outside [1, 32768]^2", fn, nx, ny);
+  return FO_OK;
+}
+
 static int hr_check_window(fo_ctx *ctx, const uint8_t *d_cls, int nx, int ny, const char *fn) {
   if (!d_cls) return fo_fail(ctx, FO_E_ARG, "%s: no cell classes (d_cls of the visibility stage)", fn);
-  if (nx < 1 || ny < 1 || nx > 32768 || ny > 32768) return fo_fail(ctx, FO_E_ARG, "%s: window %d x %d outside [1, 32768]^2", fn, nx, ny);
+  return hr_check_extent(ctx, nx, ny, fn);
+}
+
+// the reach table of a forecast: there at all, then (after the checks a caller puts between) its values
+static int hr_check_table(fo_ctx *ctx, int J, const int32_t *h_r2, const char *fn) {
+  if (J < 1 || J > HR_MAX_J)
+    return fo_fail(ctx, FO_E_ARG, "%s: J = %d outside [1, %d] (arrival steps are bytes, 255 = never)", fn, J, HR_MAX_J);
+  if (!h_r2) return fo_fail(ctx, FO_E_ARG, "%s: no reach table h_r2 [J]", fn);
   return FO_OK;
 }
 
@@ -572,6 +586,14 @@ static int hr_check_halo(fo_ctx *ctx, int r2, const char *what, const char *spee
     return fo_fail(ctx, FO_E_ARG, "%s: %s = %d is a reach of more than FO_HIDDEN_REACH_MAX_HALO = %d cells "
                    "(shorten the horizon or lower %s; the reach is never cut short)", fn, what, r2, cap, speed);
   return FO_OK;
+}
+
+static int hr_check_table_values(fo_ctx *ctx, int J, const int32_t *h_r2, const char *fn) {
+  if (h_r2[0] < 0) return fo_fail(ctx, FO_E_ARG, "%s: h_r2[0] = %d is negative", fn, h_r2[0]);
+  for (int j = 1; j < J; ++j)
+    if (h_r2[j] < h_r2[j - 1])
+      return fo_fail(ctx, FO_E_ARG, "%s: h_r2 decreases at entry %d (%d after %d)", fn, j, h_r2[j], h_r2[j - 1]);
+  return hr_check_halo(ctx, h_r2[J - 1], "h_r2[J-1]", "v_max", fn);
 }
 
 static int hr_check_footprint(fo_ctx *ctx, double hl, double hw, double wb, const char *fn) {
@@ -603,16 +625,10 @@ static int hidden_reach_call(fo_ctx *ctx, const fo_hidden_reach_t *p, bool road,
   int rc;
   if ((rc = hr_check_scene(ctx, p, fn))) return rc;
   Scene *sc = (Scene *)ctx->scene;
-  if (p->J < 1 || p->J > HR_MAX_J)
-    return fo_fail(ctx, FO_E_ARG, "%s: J = %d outside [1, %d] (arrival steps are bytes, 255 = never)", fn, p->J, HR_MAX_J);
-  if (!p->h_r2) return fo_fail(ctx, FO_E_ARG, "%s: no reach table h_r2 [J]", fn);
+  if ((rc = hr_check_table(ctx, p->J, p->h_r2, fn))) return rc;
   if (!p->d_arrival) return fo_fail(ctx, FO_E_ARG, "%s: no buffer for the arrival map (d_arrival is required)", fn);
   if ((rc = hr_check_window(ctx, p->d_cls, p->win_nx, p->win_ny, fn))) return rc;
-  if (p->h_r2[0] < 0) return fo_fail(ctx, FO_E_ARG, "%s: h_r2[0] = %d is negative", fn, p->h_r2[0]);
-  for (int j = 1; j < p->J; ++j)
-    if (p->h_r2[j] < p->h_r2[j - 1])
-      return fo_fail(ctx, FO_E_ARG, "%s: h_r2 decreases at entry %d (%d after %d)", fn, j, p->h_r2[j], p->h_r2[j - 1]);
-  if ((rc = hr_check_halo(ctx, p->h_r2[p->J - 1], "h_r2[J-1]", "v_max", fn))) return rc;
+  if ((rc = hr_check_table_values(ctx, p->J, p->h_r2, fn))) return rc;
   const int h = reach_cells(p->h_r2[p->J - 1]);
   if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
   if (p->M > 0) {
@@ -669,6 +685,47 @@ int fo_scene_hidden_reach_road(fo_ctx *ctx, const fo_hidden_reach_road_t *p, voi
 
 int fo_scene_hidden_reach_flow(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream) {
   return hidden_reach_call(ctx, p ? &p->base : nullptr, true, true, p ? p->d_dist_or_null : nullptr, "fo_scene_hidden_reach_flow", stream);
+}
+
+// the witness of every trajectory's finding: one launch over the maps of a road / flow forecast (fo_hidden_witness.hpp)
+int fo_scene_hidden_witness(fo_ctx *ctx, const fo_hidden_witness_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_witness";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  const fo_hidden_reach_t &b = p->base;
+  if (p->flow != 0 && p->flow != 1) return fo_fail(ctx, FO_E_ARG, "%s: flow = %d (0 road, 1 lanes)", fn, p->flow);
+  if ((rc = hr_check_table(ctx, b.J, b.h_r2, fn))) return rc;
+  if (!b.d_arrival || !p->d_dist)
+    return fo_fail(ctx, FO_E_ARG, "%s: the maps of the forecast are required (base.d_arrival and d_dist [win_ny][win_nx])", fn);
+  if ((rc = hr_check_extent(ctx, b.win_nx, b.win_ny, fn))) return rc;
+  if ((rc = hr_check_table_values(ctx, b.J, b.h_r2, fn))) return rc;
+  if (b.M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, b.M);
+  const int min_cap = witness_min_cap(b.h_r2[b.J - 1]);
+  if (p->path_cap < 0 || p->path_cap % 4 != 0 || p->path_cap < min_cap)
+    return fo_fail(ctx, FO_E_ARG, "%s: path_cap = %d, a multiple of 4 that is >= isqrt(169 h_r2[J-1]) / 12 = %d is needed "
+                   "(FO_HIDDEN_WITNESS_MAX_STEPS = %d always serves)", fn, p->path_cap, min_cap, FO_HIDDEN_WITNESS_MAX_STEPS);
+  if (b.M > 0) {
+    if (b.T < 1 || b.T > b.J)
+      return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, J = %d] (every sample needs its reach)", fn, b.T, b.J);
+    if (!b.d_x || !b.d_y || !b.d_heading || !b.d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T], d_heading [M][T][2] and d_first [M] of the forecast are required with M > 0", fn);
+    if (!p->d_cell || !p->d_src || !p->d_steps || !p->d_wdist || (!p->d_dirs && p->path_cap > 0))
+      return fo_fail(ctx, FO_E_ARG, "%s: d_cell, d_src [M][2], d_steps, d_wdist [M] and d_dirs [M][path_cap] are required with M > 0", fn);
+    if (((uintptr_t)p->d_dirs & 3) != 0)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_dirs must be aligned to 4 bytes (its rows are stored as dwords)", fn);
+    if ((rc = hr_check_footprint(ctx, b.hl, b.hw, b.wb, fn))) return rc;
+  }
+  if (p->flow && (rc = hr_check_moves(ctx, fn))) return rc;
+  if (b.M == 0) return FO_OK;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HrWitnessArgs a{b.M, b.T, b.d_x, b.d_y, b.d_heading, b.hl, b.hw, b.wb, sc->map->x0, sc->map->y0, sc->map->cs,
+                        sc->map->d_raster, sc->map->rnx, sc->map->rny, b.win_ix0, b.win_iy0, b.win_nx, b.win_ny, b.d_arrival,
+                        p->d_dist, p->flow ? sc->map->d_lane_moves : nullptr, b.d_first, p->path_cap, p->d_cell, p->d_src,
+                        p->d_steps, p->d_wdist, p->d_dirs};
+  hipLaunchKernelGGL(fo_hr_witness_kernel, dim3((unsigned)witness_blocks(b.M)), dim3(HR_THREADS), 0, (hipStream_t)stream, a);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
 }
 
 // the clearance: the distance transform and the distance bands of the reach, run to a cap in place of a table's end; `flow`: the

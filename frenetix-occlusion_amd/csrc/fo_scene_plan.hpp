@@ -15,6 +15,8 @@ constexpr int COMPACT_ONE_LAUNCH = 2048;   // block counts the one-launch compac
 constexpr int FV_THREADS = 256;            // threads per pose of the future visibility
 constexpr int HRR_HALO = 16;               // ring staged around a tile of the road distance = steps a band can hold
 constexpr int HRR_BAND = 12 * HRR_HALO;    // B: distance units per band launch (12 per axis step)
+constexpr int HW_LANES = 8;                // lanes per trajectory of the witness kernel: one per lattice direction
+constexpr int HW_PER_BLOCK = 32;           // ... and trajectories per workgroup of 256 threads
 constexpr int OMR_SMALL_N = 16;            // largest halo of the road occlusion memory's small form
 constexpr int OMF_SMALL_N = 16;            // ... and of its vehicle layer's (a lane per staged column: 32 + 2 n <= 64)
 
@@ -44,6 +46,9 @@ inline int64_t isqrt(int64_t v) {
 inline int reach_cells(int r2) { return (int)isqrt(r2); }
 inline int road_reach(int r2) { return (int)isqrt((int64_t)169 * r2); }
 inline int road_steps(int L) { return L / 12; }
+// workgroups of the witness kernel over M trajectories, and the shortest row that holds every walk within L
+inline int witness_blocks(int M) { return (int)(((int64_t)M + HW_PER_BLOCK - 1) / HW_PER_BLOCK); }
+inline int witness_min_cap(int r2) { return road_steps(road_reach(r2)); }
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -141,6 +141,41 @@ class FOAgentManager:
             self._pred_cache = None
         return agent
 
+    def add_route_agent(self, route, velocity, agent_type="Car", horizon=3.0):
+        """EXTENSION, not part of the reference: a phantom that drives along ``route`` ([n, 2] world points, e.g. a hidden-traffic
+        witness' route, ``HiddenWitness.routes``) at ``velocity`` (m/s), starting at ``route[0]`` and heading along its first
+        segment.  Collinear vertices are merged and the last segment is prolonged straight on by ``velocity * horizon``, so that
+        the prediction never runs off the route's end (``_route_prediction`` drops the samples beyond it) and keeps all its
+        samples; a one-point route stands still.  The agent joins this step's manual agents, as after :meth:`add_agent`."""
+        key = agent_type.lower()
+        if key not in ("bicycle", "car", "truck", "pedestrian"):
+            raise NotImplementedError(f'OAPManager: Agent type "{agent_type}" is not implemented!')
+        conf = self.config[key]
+        route = np.asarray(route, dtype=np.float64).reshape(-1, 2)
+        if len(route) == 0:
+            raise ValueError("add_route_agent: an empty route")
+        v = float(velocity)
+        seg = route[1:] - route[:-1]
+        seg_len = np.hypot(seg[:, 0], seg[:, 1])
+        route, seg = np.concatenate((route[:1], route[1:][seg_len > 0.0])), seg[seg_len > 0.0]      # (repeated points)
+        if len(seg) == 0:                                        # nowhere to go: a standing road user
+            agent = PhantomAgent(self._create_id(), agent_type, route[0], 0.0, 0.0, float(conf["length"]), float(conf["width"]))
+            agent.predictions = [self._cv_prediction(agent, horizon)]
+        else:
+            u = seg / np.hypot(seg[:, 0], seg[:, 1])[:, None]
+            turn = np.abs(u[1:, 0] * u[:-1, 1] - u[1:, 1] * u[:-1, 0]) > 1e-12
+            back = np.sum(u[1:] * u[:-1], axis=1) < 0.0
+            keep = np.concatenate(([True], turn | back, [True]))  # a vertex stays where the direction changes
+            poly = route[keep]
+            # (+ 1 m: a standing road user still needs a last segment of positive length)
+            poly = np.concatenate((poly, poly[-1:] + u[-1:] * (abs(v) * float(horizon) + 1.0)))
+            agent = PhantomAgent(self._create_id(), agent_type, route[0], float(np.arctan2(u[0, 1], u[0, 0])), v,
+                                 float(conf["length"]), float(conf["width"]))
+            agent.predictions = [self._route_prediction(agent, horizon, poly) or self._cv_prediction(agent, horizon)]
+        self._manual.append(agent)
+        self._pred_cache = None
+        return agent
+
     def _routes_at(self, pos, R=3):
         """candidate route polylines of the lanelet containing pos (route_planner.py:31-90), cached per scenario"""
         from .scenario import enumerate_routes, lanelets_of, points_in_polygon, route_polyline

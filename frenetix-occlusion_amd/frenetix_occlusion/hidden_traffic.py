@@ -265,3 +265,128 @@ def hidden_clearance(self, x, y, theta, *, vehicle, v_cap, dt, margin=None, infl
     self._hc_inputs = (q.x, q.y, q.heading, q.lengths)      # (stay referenced until the next call, as in hidden_reach)
     return HiddenClearance(key, qmin, dist, w, q.heading, r2_cap, metric, q.dt, q.margin, self.cell_size, q.hidden is not None,
                            q.from_vehicles, flow)
+
+
+# step k of the lattice points at k * 45 degrees: E, NE, N, NW, W, SW, S, SE (DESIGN.md §5.10 "Lane flow")
+WITNESS_DIRS = np.array([(1, 0), (1, 1), (0, 1), (-1, 1), (-1, 0), (-1, -1), (0, -1), (1, -1)], dtype=np.int64)
+
+
+def witness_path_cap(r2):
+    """the shortest row of ``dirs`` that holds every walk of a forecast with the reach table ``r2``: ``isqrt(169 R2[J-1]) // 12``
+    steps, rounded up to a multiple of 4 (at most ``_native.HIDDEN_WITNESS_MAX_STEPS`` at the halo cap)"""
+    return (math.isqrt(169 * int(r2[-1])) // 12 + 3) // 4 * 4
+
+
+@dataclass
+class HiddenWitness:
+    """what :meth:`SensorModel.hidden_witness` returns (DESIGN.md §5.10 "Witnesses"): ``reach`` is the :class:`HiddenReach` of the
+    road / lane-flow forecast the witnesses belong to (``k* = reach.first``), and per candidate trajectory m (device tensors)
+    ``cell [M, 2]`` int32 -- world-raster indices (gx, gy) of the conflict cell g*, the footprint cell of sample k* that hidden
+    traffic reaches along the shortest road distance; ``source [M, 2]`` int32 -- the hidden cell that traffic starts from;
+    ``steps [M]`` int32 -- lattice steps between them, -1 = the trajectory meets no hidden traffic (``cell`` and ``source`` then
+    hold INT32_MIN), -2 = the maps are not a forecast's (never after :meth:`SensorModel.hidden_witness`); ``dist [M]`` int32 --
+    the road distance ``d(g*)`` (12 per axis step, 17 per diagonal one), -1 = none; ``dirs [M, path_cap]`` uint8 -- the steps in
+    walk order (from g* back to the source), 255 beyond ``steps``.  ``origin`` (x0, y0) and ``cell_size`` place the raster in the
+    world, ``dt`` and ``v_max`` are the forecast's.
+
+    The witness is the road user that is FIRST by road distance, not the most harmful one.  :meth:`routes`, :meth:`speed` and
+    :meth:`select` read the tensors back once (the first call waits for the stream)."""
+    reach: HiddenReach
+    cell: torch.Tensor
+    source: torch.Tensor
+    steps: torch.Tensor
+    dist: torch.Tensor
+    dirs: torch.Tensor
+    origin: tuple
+    cell_size: float
+    dt: float
+    v_max: float
+    path_cap: int
+
+    def _host(self):
+        h = self.__dict__.get("_host_copy")
+        if h is None:
+            h = SimpleNamespace(**{n: getattr(self, n).detach().cpu().numpy() for n in ("cell", "source", "steps", "dist", "dirs")},
+                                first=self.reach.first.detach().cpu().numpy())
+            self.__dict__["_host_copy"] = h
+        return h
+
+    def routes(self, indices):
+        """per trajectory index a float64 ``[steps + 1, 2]`` polyline of cell centres (world coordinates) in TRAVEL order: the
+        source first, the conflict cell last; ``None`` where ``steps < 0``"""
+        h, out = self._host(), []
+        for m in indices:
+            n = int(h.steps[m])
+            if n < 0:
+                out.append(None)
+                continue
+            moves = WITNESS_DIRS[h.dirs[m, :n][::-1].astype(np.int64)]           # travel order: dir_{k_{n-1}}, .., dir_{k_0}
+            cells = h.source[m].astype(np.int64)[None] + np.concatenate((np.zeros((1, 2), dtype=np.int64), np.cumsum(moves, axis=0)))
+            out.append(np.asarray(self.origin, dtype=np.float64)[None] + (cells.astype(np.float64) + 0.5) * self.cell_size)
+        return out
+
+    def length(self, m):
+        """length (m) of the route of trajectory m: ``cell_size`` per axis step, ``cell_size sqrt(2)`` per diagonal one"""
+        h = self._host()
+        n = max(int(h.steps[m]), 0)
+        diag = int((h.dirs[m, :n] & 1).sum())
+        return self.cell_size * ((n - diag) + diag * math.sqrt(2.0))
+
+    def speed(self, m):
+        """the speed (m/s) at which the witness of trajectory m is at the conflict cell exactly at sample k*: the route length
+        divided by ``k* dt``; 0.0 when ``k* = 0`` (it is there now) and without a witness.
+
+        Bound: ``speed <= 13/12 (v_max + margin / (k* dt))``.  A lattice path of road distance d has a length between ``d / 13``
+        and ``d / 12`` cells (an axis step: 12 units for 1 cell; a diagonal one: 17 units for sqrt(2) cells, 17 / sqrt(2) > 12,
+        and 12 dx + 5 dy <= 13 sqrt(dx^2 + dy^2)), and ``d(g*) <= L[k*] = isqrt(169 R2[k*]) <= 13 (v_max k* dt + margin) / cs``,
+        so the length is at most ``13/12 (v_max k* dt + margin)``.  The speed can therefore exceed ``v_max``: the forecast's
+        reach carries the margin, and the lattice measures an octagon, not a circle."""
+        h = self._host()
+        k = int(h.first[m])
+        if k <= 0 or int(h.steps[m]) < 0:
+            return 0.0
+        return self.length(m) / (k * self.dt)
+
+    def select(self, max_agents=8, merge_cells=4):
+        """trajectory indices whose witnesses are worth an agent each: one per block of ``merge_cells`` x ``merge_cells`` source
+        cells (``source // merge_cells``), within a block the smallest ``(k*, dist, m)``, the blocks ordered by that key, at most
+        ``max_agents``"""
+        h = self._host()
+        merge = max(int(merge_cells), 1)
+        best = {}
+        for m in np.nonzero(h.steps >= 0)[0]:
+            key = (int(h.first[m]), int(h.dist[m]), int(m))
+            block = (int(h.source[m, 0]) // merge, int(h.source[m, 1]) // merge)
+            if block not in best or key < best[block]:
+                best[block] = key
+        return [key[2] for key in sorted(best.values())[:max(int(max_agents), 0)]]
+
+
+def hidden_witness(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflate=0.0, lengths=None, flow="any"):
+    """Hidden-traffic witnesses (``fo_scene_hidden_witness``; DESIGN.md §5.10 "Witnesses"): runs
+    ``hidden_reach(..., metric="road", flow=flow)`` and, on the very same device inputs, one more launch that gives per
+    candidate the cell where hidden traffic first meets it, the hidden cell that traffic starts from and the cheapest route
+    between them; returns a :class:`HiddenWitness`.  Arguments as for :meth:`hidden_reach`; the Euclidean metric has no route
+    and is not offered.  Nothing is read back and nobody waits for the kernels."""
+    reach = hidden_reach(self, x, y, theta, vehicle=vehicle, v_max=v_max, dt=dt, margin=margin, inflate=inflate, lengths=lengths,
+                         metric="road", flow=flow)
+    tx, ty, heading, tlen = self._hr_inputs
+    M, T = (int(a) for a in tx.shape)
+    dev, w = self.device, reach.window
+    cap = witness_path_cap(reach.r2)
+    cell = torch.empty((M, 2), dtype=torch.int32, device=dev)
+    source = torch.empty((M, 2), dtype=torch.int32, device=dev)
+    steps = torch.empty(M, dtype=torch.int32, device=dev)
+    dist = torch.empty(M, dtype=torch.int32, device=dev)
+    dirs = torch.empty((M, cap), dtype=torch.uint8, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    base = N.HiddenReach(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(heading), d_len_or_null=N.ptr(tlen),
+                         hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, J=T,
+                         h_r2=reach.r2.ctypes.data_as(C.POINTER(C.c_int32)), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
+                         d_arrival=reach.arrival.data_ptr(), d_first=N.ptr(reach.first))
+    args = N.HiddenWitness(base=base, d_dist=reach.road_dist.data_ptr(), flow=int(flow == "lanes"), path_cap=cap, d_cell=N.ptr(cell),
+                           d_src=N.ptr(source), d_steps=N.ptr(steps), d_wdist=N.ptr(dist), d_dirs=N.ptr(dirs))
+    self.ctx.call("fo_scene_hidden_witness", C.byref(args), N.current_stream(self._dev_index))
+    return HiddenWitness(reach, cell, source, steps, dist, dirs, tuple(float(v) for v in self.raster_origin), self.cell_size,
+                         float(dt), float(v_max), cap)

@@ -377,6 +377,40 @@ class FOInterface:
                                                   margin=om["margin"] if margin is None else margin, dt=self.dt,
                                                   inflate=inflate, metric=metric, flow=flow)
 
+    def hidden_witness(self, trajectories, v_max=None, margin=None, inflate=0.0, flow="any"):
+        """EXTENSION, not part of the reference: :meth:`hidden_reach` with ``metric="road"`` and, per candidate, the route behind
+        its finding -- the cell where hidden traffic first meets it, the hidden cell that traffic starts from and the cheapest
+        route between them (:meth:`SensorModel.hidden_witness`; returns its :class:`~frenetix_occlusion.sensor_model.HiddenWitness`,
+        whose ``reach`` is the forecast itself).  Arguments and defaults as for :meth:`hidden_reach`; ``flow="lanes"`` for hidden
+        vehicles, ``flow="any"`` for pedestrians.  :meth:`add_witness_agents` turns selected witnesses into phantom agents."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_witness needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vehicle = _vehicle_tuple(self.vehicle_params)[:3]      # length, width, wb_rear_axle
+        return self.sensor_model.hidden_witness(arr["x"], arr["y"], arr["theta"], vehicle=vehicle,
+                                                v_max=om["v_max"] if v_max is None else v_max,
+                                                margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate,
+                                                flow=flow)
+
+    def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
+        """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
+        metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of
+        source cells, earliest first); each becomes a phantom of ``agent_type`` that drives its route at ``witness.speed(m)`` --
+        it is at the conflict cell exactly at the sample the forecast named -- over the candidates' horizon
+        (:meth:`FOAgentManager.add_route_agent`).  The next ``trajectory_safety_assessment_batch`` evaluates them after the device
+        batch's slots, as it does manual agents; the next ``evaluate_scenario`` drops them with the step.  Returns the agents, in
+        the order of ``select``.  The witness is the road user that is first by road distance, not the most harmful one, and
+        its speed may exceed ``v_max`` by the bound :meth:`HiddenWitness.speed` states."""
+        T = int(witness.reach.cells.shape[1])
+        picked = witness.select(max_agents=max_agents, merge_cells=merge_cells)
+        agents = [self.agent_manager.add_route_agent(route, witness.speed(m), agent_type=agent_type, horizon=(T - 0.5) * witness.dt)
+                  for m, route in zip(picked, witness.routes(picked))]     # (T - 0.5: int(horizon / dt) + 1 == T whatever dt rounds to)
+        self.metrics.invalidate()
+        return agents
+
     def _update_time_step(self, timestep):
         self.timestep = timestep
         self.sensor_model.timestep = timestep

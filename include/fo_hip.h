@@ -487,6 +487,52 @@ int fo_scene_set_lane_moves(fo_ctx *ctx, const uint8_t *h_moves /* [rny][rnx] */
 int fo_scene_hidden_reach_flow(fo_ctx *ctx, const fo_hidden_reach_road_t *p, void *stream);
 int fo_scene_hidden_clearance_flow(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic WITNESSES (DESIGN.md §5.10 "Witnesses") -- per candidate trajectory the
+ * cell where hidden traffic first meets it, the hidden cell that traffic starts from and the cheapest route between them: what a
+ * caller needs to put that road user in front of the metric sweep as a phantom agent.  Opt-in and additive: one launch, nothing
+ * is read back, no other output changes.  Integers only, apart from the footprint test.
+ *  Inputs: the outputs of ONE fo_scene_hidden_reach_road (flow = 0) or fo_scene_hidden_reach_flow (flow = 1) call of this step --
+ *   A = base.d_arrival, d = d_dist (that call's d_dist_or_null), base.d_first [M] -- with the same trajectories, headings, hl, hw,
+ *   wb, J, h_r2 and window.  base.d_cls, d_hidden_or_null, d_len_or_null, d_cells and d_slack are not read.
+ *  Extension to every world-raster cell g: inside the window A(g), d(g) are the maps'; outside it a cell on the raster and road
+ *   has A = 0, d = 0 (every unobserved road cell is a source), every other cell A = 255, d = 65535.  out(g) is the move table's
+ *   byte on the raster (flow = 1) and 0xFF off it and with flow = 0.  Directions k = 0 .. 7, dir_k and the weights w_k = 12 / 17
+ *   are those of the lane flow above.
+ *  1. Conflict cell.  k* = first[m]; k* = -1 (or no sample of the batch): no witness -- steps = -1, wdist = -1, cell = src =
+ *   (INT32_MIN, INT32_MIN), the row of dirs all 255.  Otherwise g* is, among the footprint cells of sample k* (the footprint and
+ *   the clipping of fo_scene_hidden_reach, cells outside the window included) with A(g) <= k*, the one with the smallest
+ *   (d(g), gy, gx), compared lexicographically.  (No such cell -- a first that is not these maps': steps = -2, the rest as without
+ *   a witness.)
+ *  2. Walk.  c_0 = g*, prev = none.  While d(c_i) > 0: K_i = { k : p = c_i - dir_k, d(p) != 65535, d(p) + w_k == d(c_i), bit k
+ *   set in out(p) and in out(c_i) }; k_i = prev if prev is in K_i, else min K_i; prev = k_i; c_{i+1} = c_i - dir_{k_i};
+ *   dirs[i] = k_i.  steps = n at the first c_n with d = 0, src = c_n.  On maps made by the two entries K_i is never empty (d is a
+ *   shortest-path distance) and n <= isqrt(169 h_r2[J-1]) / 12.  If K_i is empty or i reaches path_cap the maps are not this
+ *   definition's: steps = -2, src = c_i, the rest of the row 255 -- the walk is bounded whatever d holds, and reads only cells
+ *   of the maps and of the raster.
+ *  3. Outputs, every byte written by every call: d_cell [M][2] int32 the world-raster indices (gx, gy) of g*; d_src [M][2] those
+ *   of the source; d_steps [M]; d_wdist [M] = d(g*); d_dirs [M][path_cap] uint8 in walk order (from g* back), 255 beyond steps.
+ *   The hidden road user travels src -> g* by dir_{k_{n-1}}, .., dir_{k_0}; the step weights sum to wdist; every step is an
+ *   allowed step of the metric that made d, and src is a source.
+ *  Not claimed: the witness is the road user that is first by road distance, not the most harmful one.
+ * path_cap: a multiple of 4 (a row is stored as dwords; d_dirs aligned to 4 bytes) with path_cap >= isqrt(169 h_r2[J-1]) / 12,
+ *  at most FO_HIDDEN_WITNESS_MAX_STEPS at the halo cap.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_witness:"): flow not 0 or
+ * 1; J outside [1, 254]; no h_r2, base.d_arrival or d_dist; a window outside [1, 32768]^2; h_r2 refused as by
+ * fo_scene_hidden_reach; M < 0; path_cap negative, too small or no multiple of 4; with M > 0: T outside [1, J], no d_x / d_y /
+ * d_heading / d_first, no output buffer, or extents refused as by fo_scene_hidden_reach.  FO_E_STATE: flow = 1 without a move table. */
+#define FO_HIDDEN_WITNESS_MAX_STEPS 276
+typedef struct {
+  fo_hidden_reach_t base;                   /* M, T, d_x, d_y, d_heading, hl, hw, wb, J, h_r2, window: those of the call that made
+                                               the maps; d_arrival and d_first are INPUTS here */
+  const uint16_t *d_dist;                   /* [win_ny][win_nx] the d_dist_or_null of that call (required) */
+  int32_t flow;                             /* 0: road, 1: lanes */
+  int32_t path_cap;
+  int32_t *d_cell, *d_src;                  /* [M][2] */
+  int32_t *d_steps, *d_wdist;               /* [M] */
+  uint8_t *d_dirs;                          /* [M][path_cap] */
+} fo_hidden_witness_t;
+int fo_scene_hidden_witness(fo_ctx *ctx, const fo_hidden_witness_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

@@ -3,13 +3,16 @@ whole call, next to the visibility stage the forecast
 follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
-                                       [--flow any|lanes] [--clearance]
+                                       [--flow any|lanes] [--clearance] [--witness]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
 ``--clearance``: one ``hidden_clearance`` call at ``v_cap = --v-max`` plus ``.reach`` for three speeds (2, 7 m/s and the cap)
 against three ``hidden_reach`` calls at those speeds, and the clearance split by stage (key map alone, whole call with and
 without heading reuse, the three derivations).
+
+``--witness`` (with ``--metric road``): ``hidden_witness`` -- the forecast plus the route behind every candidate's finding (§5.10
+"Witnesses") -- joins the timed loop, next to the forecast alone; also the number of distinct sources and the longest walk.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -54,9 +57,12 @@ def main():
     ap.add_argument("--metric", default="euclid", choices=("euclid", "road"), help="road: the reach follows the road (§5.10)")
     ap.add_argument("--flow", default="any", choices=("any", "lanes"), help="lanes: hidden vehicles follow the lanes (needs --metric road)")
     ap.add_argument("--clearance", action="store_true", help="time hidden_clearance + .reach x 3 against three hidden_reach calls")
+    ap.add_argument("--witness", action="store_true", help="time hidden_witness next to hidden_reach (needs --metric road)")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
+    if a.witness and a.metric != "road":
+        ap.error("--witness needs --metric road")
     if a.scene == "city_grid":
         sc = SC.synthetic_urban_grid()
     else:
@@ -91,6 +97,17 @@ def main():
     res["call_ms"] = _median_ms(lambda: sm.hidden_reach(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, metric=a.metric, flow=a.flow), a.calls)
     res["future_visibility_720_first_seen_ms"] = _median_ms(
         lambda: sm.future_visibility_ex(tx, ty, None, t_stride=5, n_rays=720, first_seen=True), a.calls)
+    if a.witness:
+        hw = lambda: sm.hidden_witness(tx, ty, tth, vehicle=veh, v_max=a.v_max, dt=0.1, flow=a.flow)
+        w = hw()
+        res["witness_call_ms"] = _median_ms(hw, a.calls)
+        steps, src = w.steps.cpu().numpy(), w.source.cpu().numpy()
+        res["path_cap"] = int(w.path_cap)
+        res["witnesses"] = int((steps >= 0).sum())
+        res["distinct_sources"] = int(len(np.unique(src[steps >= 0], axis=0)))
+        res["longest_walk"] = int(steps.max(initial=-1))
+        res["walk_steps_total"] = int(steps[steps > 0].sum())
+        res["agents_selected"] = len(w.select())
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
