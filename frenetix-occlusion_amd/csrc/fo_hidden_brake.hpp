@@ -1,0 +1,130 @@
+// fo_hidden_brake.hpp -- hidden-traffic brake clearance (fo_scene_hidden_brake; DESIGN.md §5.10 "Brake clearance"): from which
+// sample on "follow the candidate until here, then brake" no longer keeps the moving ego out of road hidden traffic may have
+// reached.  An EXTENSION, not part of the reference.  Included by fo_scene.hip after fo_hidden_reach.hpp (same translation unit,
+// same flags: -ffp-contract=off, which the pose arithmetic and the footprint test need); it scans with fo_hr_scan_pose_rows.
+//
+// Inputs are the arrival map A and d_first of one forecast call (any of the three entries) and, next to its trajectories, the
+// speed v and the travelled chord length arc per sample, handed over as data.  The definition stands in include/fo_hip.h.
+//   fo_hr_brake_kernel   a lane per brake start (m, b), lanes along b; G = the power of two >= min(T, 64) lanes per trajectory,
+//                        256 / G trajectories per workgroup, whose rows x, y, cos, sin, arc, v are staged in LDS once (48 T
+//                        bytes each).  The lane walks its manoeuvre's samples i = b + 1 .. in order: the running length s is a
+//                        serial float64 sum by definition, and the segment index j only ever moves forward (the first index
+//                        with arc[j] >= sc is non-decreasing in sc, whatever arc holds).  The walk ends at the first hit, and
+//                        once the ego stands (i >= stop) the pose no longer changes: ONE scan that keeps the smallest arrival
+//                        step of the footprint answers every remaining sample.  commit is a shuffle minimum over the G lanes.
+// The arrival map is read through the caches (the access pattern of fo_hr_traj_kernel).  Every LDS index is clamped to [0, Lm)
+// before it is used and the scan tests every cell against the window and the raster first: no content of v, arc, A or first can
+// make a lane read out of range.  No atomics, no scratch, plain vector stores; every byte of every output is written.
+#pragma once
+#include "fo_hidden_reach.hpp"
+
+namespace {
+
+static_assert(HB_THREADS == HR_THREADS && HB_THREADS % 64 == 0, "the lanes of a trajectory are consecutive lanes of one wave");
+
+struct HrBrakeArgs {
+  int M, T, G;                          // G lanes per trajectory (power of two, <= 64)
+  const double *x, *y, *heading;        // [M][T], [M][T], [M][T][2]
+  const int32_t *len;                   // [M] or null
+  double hl, hw, wb;
+  double rx0, ry0, cs;
+  const uint8_t *raster;
+  int rnx, rny;
+  int ix0, iy0, nx, ny;                 // the window
+  const uint8_t *arrival;               // [ny][nx]
+  const int32_t *first;                 // [M]
+  const double *v, *arc;                // [M][T]
+  double a_brake, dt;
+  int32_t *brake_first, *stop;          // [M][T]
+  int32_t *commit;                      // [M]
+};
+
+// vn(i) of a manoeuvre that brakes from sample b at speed vb: be.py's profile, the speed held over a step
+__device__ __forceinline__ double hb_speed(double vb, double a_brake, double dt, int i, int b) {
+  return fmax(vb - a_brake * ((double)(i - b) * dt), 0.0);
+}
+
+// dynamic LDS: brake_lds_bytes(T)
+__global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeArgs a) {
+  extern __shared__ double hb_rows[];   // per trajectory of the workgroup: x, y, cos, sin, arc, v, T entries each
+  const uint8_t *__restrict__ A = a.arrival;
+  const int G = a.G, T = a.T, per_block = HB_THREADS / G;
+  const int sub = threadIdx.x / G, kl = threadIdx.x & (G - 1);
+  const long long m0 = (long long)blockIdx.x * per_block, m = m0 + sub;
+  const bool live = m < a.M;
+  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
+    const int su = t / T, k = t - su * T;
+    if (m0 + su < a.M) {
+      const size_t i = (size_t)(m0 + su) * T + k;
+      double *row = hb_rows + (size_t)su * 6 * T + k;
+      row[0] = a.x[i];
+      row[T] = a.y[i];
+      row[2 * T] = a.heading[2 * i];
+      row[3 * T] = a.heading[2 * i + 1];
+      row[4 * T] = a.arc[i];
+      row[5 * T] = a.v[i];
+    }
+  }
+  __syncthreads();
+  const double *X = hb_rows + (size_t)sub * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
+  int Lm = 0, fm = -1;
+  if (live) {
+    Lm = T;
+    if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < T ? l : T); }
+    fm = a.first[m];
+  }
+  // cells beyond the raster and the window have no arrival step: the scan never leaves their union
+  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
+  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  int commit = 0x7fffffff;
+  for (int b = kl; b < T; b += G) {
+    int bf = -1, st = -1;
+    if (b < Lm) {                       // (Lm = 0 on lanes without a trajectory)
+      const double vb = V[b], arc_end = ARC[Lm - 1];
+      st = Lm;
+      for (int i = b; i < Lm; ++i)
+        if (hb_speed(vb, a.a_brake, a.dt, i, b) == 0.0) { st = i; break; }
+      double s = ARC[b];
+      int j = 0;
+      for (int i = b + 1; i < Lm; ++i) {
+        s = s + hb_speed(vb, a.a_brake, a.dt, i - 1, b) * a.dt;
+        const double sc = fmin(s, arc_end);
+        while (j < Lm && !(ARC[j] >= sc)) ++j;
+        int idx = j < 1 ? 1 : j;
+        idx = idx < Lm - 1 ? idx : Lm - 1;                       // (Lm >= 2 here: b + 1 < Lm)
+        const double xlo = ARC[idx - 1], xhi = ARC[idx];
+        double xn = X[idx - 1], yn = Y[idx - 1];
+        int hd = idx - 1;
+        if (xhi != xlo) {
+          const double w = sc - xlo, inv = xhi - xlo;
+          xn = (X[idx] - X[idx - 1]) / inv * w + X[idx - 1];
+          yn = (Y[idx] - Y[idx - 1]) / inv * w + Y[idx - 1];
+          if (!(w + w <= inv)) hd = idx;
+        }
+        // the ego stands from sample st on (vn = 0 adds nothing to s): this pose is the manoeuvre's last one
+        const bool stands = i >= st;
+        int amin = 255;
+        fo_hr_scan_pose_rows(a, xn, yn, C[hd], S[hd], A, 255, lox, loy, hix, hiy, 0, 1,
+                             [&](int av, int, int) { amin = amin < av ? amin : av; });
+        if (stands) {                   // hit(i') for i' >= i iff amin <= i'
+          const int at = amin > i ? amin : i;
+          if (at < Lm) bf = at;
+          break;
+        }
+        if (amin <= i) { bf = i; break; }
+      }
+      if ((fm >= 0 && fm <= b) || (bf >= 0 && bf < st)) commit = commit < b ? commit : b;
+    }
+    if (live) {
+      a.brake_first[(size_t)m * T + b] = bf;
+      a.stop[(size_t)m * T + b] = st;
+    }
+  }
+  for (int o = G >> 1; o > 0; o >>= 1) {            // lanes of a trajectory are G consecutive lanes of one wave
+    const int c = __shfl_xor(commit, o);
+    commit = commit < c ? commit : c;
+  }
+  if (live && kl == 0) a.commit[m] = commit == 0x7fffffff ? -1 : commit;
+}
+
+}  // namespace

@@ -177,12 +177,13 @@ struct HrTrajArgs {
 // centre passes the float64 point-in-rectangle test gets f(v, gx, gy), v = map[cell] inside the window, outside it 0 on raster
 // road and `none` elsewhere, (gx, gy) the cell's raster indices.  Of the box's rows a caller takes row0, row0 + row_step, ...:
 // the lanes that share a pose split its rows (fo_hidden_witness.hpp).  The ONE statement of the test on the device: the reach,
-// the clearance and the witness kernel all scan with it.
+// the clearance, the witness and the brake kernel all scan with it.
+// fo_hr_scan_pose_rows takes the pose's values (px, py, c, s) themselves: the brake kernel's poses are interpolated, no sample of
+// the arrays (fo_hidden_brake.hpp); the forms below hand it the values of sample i.
 template <class Args, class V, class F>
-__device__ __forceinline__ void fo_hr_scan_footprint_rows(const Args &a, size_t i, const V *__restrict__ map, int none, int lox,
-                                                          int loy, int hix, int hiy, int row0, int row_step, F &&f) {
-  const double c = a.heading[2 * i], s = a.heading[2 * i + 1];
-  const double cx = a.x[i] + a.wb * c, cy = a.y[i] + a.wb * s;
+__device__ __forceinline__ void fo_hr_scan_pose_rows(const Args &a, double px, double py, double c, double s, const V *__restrict__ map,
+                                                     int none, int lox, int loy, int hix, int hiy, int row0, int row_step, F &&f) {
+  const double cx = px + a.wb * c, cy = py + a.wb * s;
   const double bx = fabs(c) * a.hl + fabs(s) * a.hw, by = fabs(s) * a.hl + fabs(c) * a.hw;
   const double fx0 = (cx - bx - a.rx0) / a.cs - 0.5, fx1 = (cx + bx - a.rx0) / a.cs - 0.5;
   const double fy0 = (cy - by - a.ry0) / a.cs - 0.5, fy1 = (cy + by - a.ry0) / a.cs - 0.5;
@@ -211,6 +212,16 @@ __device__ __forceinline__ void fo_hr_scan_footprint_rows(const Args &a, size_t 
       f(v, gx, gy);
     }
   }
+}
+
+// the footprint of pose i of the trajectory arrays of `a`.  The heading is loaded first, in statements of its own: written so,
+// fo_hr_traj_kernel keeps the load order and the waits it had before the pose form existed (compared in the gfx950 assembly);
+// with the four loads as call arguments it waits for all of them before its first multiply.
+template <class Args, class V, class F>
+__device__ __forceinline__ void fo_hr_scan_footprint_rows(const Args &a, size_t i, const V *__restrict__ map, int none, int lox,
+                                                          int loy, int hix, int hiy, int row0, int row_step, F &&f) {
+  const double c = a.heading[2 * i], s = a.heading[2 * i + 1];
+  fo_hr_scan_pose_rows(a, a.x[i], a.y[i], c, s, map, none, lox, loy, hix, hiy, row0, row_step, f);
 }
 
 // every row, the value alone: the scan of a lane that has a pose to itself

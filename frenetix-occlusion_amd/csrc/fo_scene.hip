@@ -42,6 +42,7 @@
 //   fo_hidden_reach_road.hpp fo_hr_road_*_kernel  its road metric: distance bands along the road, arrival merge
 //   fo_hidden_reach_flow.hpp fo_hr_flow_band_kernel  the road metric bound to the lanes' driving direction: directed distance bands
 //   fo_hidden_witness.hpp    fo_hr_witness_kernel  the route behind each candidate's finding: conflict cell, walk back along d
+//   fo_hidden_brake.hpp      fo_hr_brake_kernel  brake clearance: follow a candidate until sample b, then brake -- a lane per (m, b)
 //   fo_hidden_clearance.hpp  fo_hc_*_kernel  hidden-traffic clearance: the key map behind every reach table, its minimum per pose
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
@@ -53,6 +54,7 @@
 #include "fo_hidden_reach_road.hpp"
 #include "fo_hidden_reach_flow.hpp"
 #include "fo_hidden_witness.hpp"
+#include "fo_hidden_brake.hpp"
 #include "fo_hidden_clearance.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
@@ -724,6 +726,43 @@ int fo_scene_hidden_witness(fo_ctx *ctx, const fo_hidden_witness_t *p, void *str
                         p->d_dist, p->flow ? sc->map->d_lane_moves : nullptr, b.d_first, p->path_cap, p->d_cell, p->d_src,
                         p->d_steps, p->d_wdist, p->d_dirs};
   hipLaunchKernelGGL(fo_hr_witness_kernel, dim3((unsigned)witness_blocks(b.M)), dim3(HR_THREADS), 0, (hipStream_t)stream, a);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+// the brake clearance of every (trajectory, brake start): one launch over the arrival map of any forecast (fo_hidden_brake.hpp)
+int fo_scene_hidden_brake(fo_ctx *ctx, const fo_hidden_brake_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_brake";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  const fo_hidden_reach_t &b = p->base;
+  if ((rc = hr_check_table(ctx, b.J, b.h_r2, fn))) return rc;
+  if (!b.d_arrival)
+    return fo_fail(ctx, FO_E_ARG, "%s: the map of the forecast is required (base.d_arrival [win_ny][win_nx])", fn);
+  if ((rc = hr_check_extent(ctx, b.win_nx, b.win_ny, fn))) return rc;
+  if ((rc = hr_check_table_values(ctx, b.J, b.h_r2, fn))) return rc;
+  if (b.M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, b.M);
+  if (!(p->a_brake >= 0.0) || !std::isfinite(p->a_brake))      // (NaN fails every comparison)
+    return fo_fail(ctx, FO_E_ARG, "%s: a_brake = %g, a finite deceleration >= 0 is needed", fn, p->a_brake);
+  if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return fo_fail(ctx, FO_E_ARG, "%s: dt = %g, a finite step > 0 is needed", fn, p->dt);
+  if (b.M > 0) {
+    if (b.T < 1 || b.T > b.J)
+      return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, J = %d] (every sample needs its reach)", fn, b.T, b.J);
+    if (!b.d_x || !b.d_y || !b.d_heading || !b.d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T], d_heading [M][T][2] and d_first [M] of the forecast are required with M > 0", fn);
+    if (!p->d_v || !p->d_arc) return fo_fail(ctx, FO_E_ARG, "%s: d_v and d_arc [M][T] are required with M > 0", fn);
+    if (!p->d_brake_first || !p->d_stop || !p->d_commit)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_brake_first, d_stop [M][T] and d_commit [M] are required with M > 0", fn);
+    if ((rc = hr_check_footprint(ctx, b.hl, b.hw, b.wb, fn))) return rc;
+  }
+  if (b.M == 0) return FO_OK;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HrBrakeArgs a{b.M, b.T, brake_group(b.T), b.d_x, b.d_y, b.d_heading, b.d_len_or_null, b.hl, b.hw, b.wb, sc->map->x0,
+                      sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, b.win_ix0, b.win_iy0, b.win_nx,
+                      b.win_ny, b.d_arrival, b.d_first, p->d_v, p->d_arc, p->a_brake, p->dt, p->d_brake_first, p->d_stop, p->d_commit};
+  hipLaunchKernelGGL(fo_hr_brake_kernel, dim3((unsigned)brake_blocks(b.M, b.T)), dim3(HB_THREADS), brake_lds_bytes(b.T),
+                     (hipStream_t)stream, a);
   FO_HIP_TRY(ctx, hipGetLastError());
   return FO_OK;
 }

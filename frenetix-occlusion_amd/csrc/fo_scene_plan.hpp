@@ -4,6 +4,7 @@
 // alone (tests/test_scene_plan_cpu.py, next to the Python restatement tests/scene_forms.expected_form).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 namespace {
@@ -17,6 +18,7 @@ constexpr int HRR_HALO = 16;               // ring staged around a tile of the r
 constexpr int HRR_BAND = 12 * HRR_HALO;    // B: distance units per band launch (12 per axis step)
 constexpr int HW_LANES = 8;                // lanes per trajectory of the witness kernel: one per lattice direction
 constexpr int HW_PER_BLOCK = 32;           // ... and trajectories per workgroup of 256 threads
+constexpr int HB_THREADS = 256;            // threads per workgroup of the brake kernel
 constexpr int OMR_SMALL_N = 16;            // largest halo of the road occlusion memory's small form
 constexpr int OMF_SMALL_N = 16;            // ... and of its vehicle layer's (a lane per staged column: 32 + 2 n <= 64)
 
@@ -49,6 +51,12 @@ inline int road_steps(int L) { return L / 12; }
 // workgroups of the witness kernel over M trajectories, and the shortest row that holds every walk within L
 inline int witness_blocks(int M) { return (int)(((int64_t)M + HW_PER_BLOCK - 1) / HW_PER_BLOCK); }
 inline int witness_min_cap(int r2) { return road_steps(road_reach(r2)); }
+// the brake kernel: a lane per brake start b, G = the power of two >= min(T, 64) lanes per trajectory (b = lane, lane + G, ..),
+// HB_THREADS / G trajectories per workgroup, whose six rows of T float64 (x, y, cos, sin, arc, v) are staged in LDS
+inline int brake_group(int T) { int G = 1; while (G < T && G < 64) G <<= 1; return G; }
+inline int brake_per_block(int T) { return HB_THREADS / brake_group(T); }
+inline int brake_blocks(int M, int T) { const int p = brake_per_block(T); return (int)(((int64_t)M + p - 1) / p); }
+inline size_t brake_lds_bytes(int T) { return (size_t)brake_per_block(T) * 6 * (size_t)T * sizeof(double); }
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -36,7 +36,7 @@ EXPORTS = [
     "fo_scene_set_occlusion_memory", "fo_scene_future_visibility_ex", "fo_scene_hidden_reach",
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
-    "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness",
+    "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
 ]
 
 
@@ -108,6 +108,11 @@ class HiddenWitness(C.Structure):       # fo_hidden_witness_t
     _fields_ = [("base", HiddenReach), ("d_dist", C.c_void_p), ("flow", C.c_int32), ("path_cap", C.c_int32),
                 ("d_cell", C.c_void_p), ("d_src", C.c_void_p), ("d_steps", C.c_void_p), ("d_wdist", C.c_void_p),
                 ("d_dirs", C.c_void_p)]
+
+
+class HiddenBrake(C.Structure):         # fo_hidden_brake_t
+    _fields_ = [("base", HiddenReach), ("d_v", C.c_void_p), ("d_arc", C.c_void_p), ("a_brake", C.c_double), ("dt", C.c_double),
+                ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p)]
 
 
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
@@ -219,6 +224,7 @@ def load():
     lib.fo_scene_hidden_reach_flow.argtypes = [vp, C.POINTER(HiddenReachRoad), vp]
     lib.fo_scene_hidden_clearance_flow.argtypes = [vp, C.POINTER(HiddenClearance), vp]
     lib.fo_scene_hidden_witness.argtypes = [vp, C.POINTER(HiddenWitness), vp]
+    lib.fo_scene_hidden_brake.argtypes = [vp, C.POINTER(HiddenBrake), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -390,3 +390,97 @@ def hidden_witness(self, x, y, theta, *, vehicle, v_max, dt, margin=None, inflat
     self.ctx.call("fo_scene_hidden_witness", C.byref(args), N.current_stream(self._dev_index))
     return HiddenWitness(reach, cell, source, steps, dist, dirs, tuple(float(v) for v in self.raster_origin), self.cell_size,
                          float(dt), float(v_max), cap)
+
+
+def travelled_arc(x, y):
+    """the travelled chord length of trajectories ``x, y [M, T]`` -- be.py's ``insert(cumsum(sqrt(diff(x)^2 + diff(y)^2)), 0, 0)``
+    per row, float64 ``[M, T]``.  Host arrays: that numpy formula.  Device tensors: the same with torch on the tensors' device,
+    nothing is copied back.  The brake clearance takes the result as DATA (as it takes the headings): whichever form made it, the
+    very numbers are kept in the :class:`HiddenBrake` and are what a checker is handed."""
+    if torch.is_tensor(x) or torch.is_tensor(y):
+        tx = x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x, dtype=np.float64), device=y.device)
+        ty = y if torch.is_tensor(y) else torch.as_tensor(np.asarray(y, dtype=np.float64), device=tx.device)
+        tx, ty = tx.to(torch.float64), ty.to(torch.float64)
+        seg = torch.sqrt(torch.diff(tx, dim=-1) ** 2 + torch.diff(ty, dim=-1) ** 2)
+        return torch.cat((torch.zeros_like(tx[..., :1]), torch.cumsum(seg, dim=-1)), dim=-1)
+    x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    seg = np.sqrt(np.diff(x, axis=-1) ** 2 + np.diff(y, axis=-1) ** 2)
+    return np.insert(np.cumsum(seg, axis=-1), 0, 0.0, axis=-1)
+
+
+@dataclass
+class HiddenBrake:
+    """what :meth:`SensorModel.hidden_brake` returns (DESIGN.md §5.10 "Brake clearance"): ``reach`` is the :class:`HiddenReach` of
+    the forecast the manoeuvres were held against, and (device tensors, int32) ``brake_first [M, T]`` -- for "follow candidate m
+    until sample b, then brake at ``a_brake``" the first sample ``i > b`` at which the braking ego's footprint holds a cell hidden
+    traffic may have reached by then, -1 = none within the horizon (and for ``b >= lengths[m]``); ``stop [M, T]`` -- the first
+    sample at which that manoeuvre stands, ``Lm`` = not within the horizon, -1 for ``b >= lengths[m]``; ``commit [M]`` -- the
+    smallest b from which the candidate is no longer fail-safe: ``reach.first <= b`` (it is in reached road itself) or
+    ``brake_first < stop`` (the braking ego meets reached road while it still moves), -1 = fail-safe from every sample of the
+    horizon.  A LARGER ``commit`` is the safer candidate, -1 the safest.  ``arc [M, T]`` float64 is the travelled chord length the
+    device was handed (:func:`travelled_arc`), ``a_brake`` (m/s^2) and ``dt`` the manoeuvre's, ``lengths [M]`` int32 the ragged
+    batch's lengths on the device (None: every trajectory has T samples).
+
+    Not claimed: the manoeuvre keeps to the candidate's own path and ends where it ends; one that still moves at the last sample
+    is decided within the horizon only (:meth:`decided_until`); the heading is the nearer sample's; the hidden road user is the
+    forecast's."""
+    reach: HiddenReach
+    brake_first: torch.Tensor
+    stop: torch.Tensor
+    commit: torch.Tensor
+    arc: torch.Tensor
+    a_brake: float
+    dt: float
+    lengths: Optional[torch.Tensor] = None
+
+    def decided_until(self):
+        """``[M]`` int32: the smallest brake start b with ``stop[m, b] == Lm`` -- from there on the horizon no longer sees the
+        braking ego stand, so ``commit`` speaks only of the samples it has -- and ``Lm`` where every manoeuvre stands in time.
+        Torch ops on the tensors' device, nothing is read back."""
+        M, T = (int(v) for v in self.stop.shape)
+        dev = self.stop.device
+        Lm = torch.full((M,), T, dtype=torch.int64, device=dev)
+        if self.lengths is not None:
+            Lm = torch.clamp(self.lengths.to(torch.int64), 0, T)
+        if T == 0:
+            return Lm.to(torch.int32)
+        b = torch.arange(T, device=dev, dtype=torch.int64)[None, :]
+        open_end = (self.stop.to(torch.int64) == Lm[:, None]) & (b < Lm[:, None])
+        return torch.where(open_end, b, Lm[:, None]).amin(dim=1).to(torch.int32)
+
+
+def hidden_brake(self, x, y, theta, v, *, vehicle, v_max, dt, a_brake, margin=None, inflate=0.0, lengths=None, metric="euclid",
+                 flow="any"):
+    """Hidden-traffic brake clearance (``fo_scene_hidden_brake``; DESIGN.md §5.10 "Brake clearance"): runs
+    ``hidden_reach(...)`` with these arguments and, on the very same device inputs, one more launch that holds the manoeuvre
+    "follow the candidate until sample b, then brake at ``a_brake``" of every (candidate, b) against the forecast's arrival map;
+    returns a :class:`HiddenBrake`.  ``v [M, T]``: the candidates' speed at each sample (m/s); the travelled chord length is
+    :func:`travelled_arc` of ``x, y``.  The other arguments as for :meth:`hidden_reach`.  Nothing is read back and nobody waits
+    for the kernels."""
+    reach = hidden_reach(self, x, y, theta, vehicle=vehicle, v_max=v_max, dt=dt, margin=margin, inflate=inflate, lengths=lengths,
+                         metric=metric, flow=flow)
+    tx, ty, heading, tlen = self._hr_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T):
+        raise ValueError("hidden_brake: v must be [M, T]")
+    a_brake = float(a_brake)
+    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
+        raise ValueError("hidden_brake: a_brake >= 0 and finite")
+    dev, w = self.device, reach.window
+    tv = N.on_device(v, dev)
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    arc = N.on_device(arc, dev)
+    brake_first = torch.empty((M, T), dtype=torch.int32, device=dev)
+    stop = torch.empty((M, T), dtype=torch.int32, device=dev)
+    commit = torch.empty(M, dtype=torch.int32, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    base = N.HiddenReach(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(heading), d_len_or_null=N.ptr(tlen),
+                         hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, J=T,
+                         h_r2=reach.r2.ctypes.data_as(C.POINTER(C.c_int32)), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
+                         d_arrival=reach.arrival.data_ptr(), d_first=N.ptr(reach.first))
+    args = N.HiddenBrake(base=base, d_v=N.ptr(tv), d_arc=N.ptr(arc), a_brake=a_brake, dt=float(dt), d_brake_first=N.ptr(brake_first),
+                         d_stop=N.ptr(stop), d_commit=N.ptr(commit))
+    self.ctx.call("fo_scene_hidden_brake", C.byref(args), N.current_stream(self._dev_index))
+    self._hb_inputs = (tv, arc)                             # (stay referenced until the next call, as in hidden_reach)
+    return HiddenBrake(reach, brake_first, stop, commit, arc, a_brake, float(dt), tlen)

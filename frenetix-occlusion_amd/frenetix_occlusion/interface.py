@@ -395,6 +395,25 @@ class FOInterface:
                                                 margin=om["margin"] if margin is None else margin, dt=self.dt, inflate=inflate,
                                                 flow=flow)
 
+    def hidden_brake(self, trajectories, a_brake=None, v_max=None, margin=None, inflate=0.0, metric="euclid", flow="any"):
+        """EXTENSION, not part of the reference: :meth:`hidden_reach` and, per candidate, the fail-safe question -- if the ego
+        follows it until sample b and then brakes at ``a_brake``, does it come to rest before it enters road hidden traffic could
+        have reached by then?  (:meth:`SensorModel.hidden_brake`; returns its :class:`~frenetix_occlusion.sensor_model.HiddenBrake`:
+        ``commit [M]`` the first b from which it does not, -1 = never within the horizon; ``brake_first``, ``stop [M, T]``;
+        ``reach`` the forecast itself.)  ``a_brake`` defaults to ``vehicle_params.a_max``; the speeds are the trajectories' own
+        ``v``.  The other arguments and defaults as for :meth:`hidden_reach`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        return self.sensor_model.hidden_brake(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3],
+                                              v_max=om["v_max"] if v_max is None else v_max,
+                                              margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                              a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate, metric=metric, flow=flow)
+
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
         metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of

@@ -533,6 +533,58 @@ typedef struct {
 } fo_hidden_witness_t;
 int fo_scene_hidden_witness(fo_ctx *ctx, const fo_hidden_witness_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic BRAKE CLEARANCE (DESIGN.md §5.10 "Brake clearance") -- if the ego follows
+ * candidate m until sample b and then brakes, does it come to rest before it enters road that hidden traffic could have reached
+ * by then?  commit[m] is the first b from which it does not: the fail-safe criterion that ranks the candidates where first >= 0
+ * holds for the whole fan.  The manoeuvre is the reference's (metrics/be.py:84-146, _calc_deceleration_trajectory): the path is
+ * kept, the speed ramps down, the poses are re-sampled by linear interpolation over the travelled chord length.  Opt-in and
+ * additive: one launch, nothing is read back, no other output changes.  Integers everywhere except the pose arithmetic and the
+ * footprint test; all float64 in the stated operation order, no contraction.
+ *  Inputs: those of ONE forecast call of this step (fo_scene_hidden_reach, _road or _flow) -- trajectories, headings, d_len_or_null,
+ *   hl, hw, wb, the window, J = T, h_r2 -- with its outputs A = base.d_arrival and first = base.d_first; d_v [M][T] the speed at
+ *   each sample (m/s), d_arc [M][T] the travelled chord length, handed over as data like the headings (nothing depends on it
+ *   being monotone); a_brake >= 0 (m/s^2), dt > 0.  base.d_cls, d_hidden_or_null, d_cells and d_slack are not read.
+ *   Lm = T clipped by len[m], as in fo_scene_hidden_reach.
+ *  For trajectory m and brake start b in 0 .. T-1:
+ *  1. b >= Lm: brake_first[m][b] = -1 and stop[m][b] = -1.
+ *  2. Speed profile, the speed held over a step: vn(i) = fmax(v[m][b] - a_brake * ((double)(i - b) * dt), 0.0) for i >= b.
+ *   stop[m][b] = the smallest i in [b, Lm) with vn(i) == 0.0, or Lm if there is none.
+ *  3. Poses.  Samples i <= b are the candidate's own (the forecast covers them).  For i = b+1 .. Lm-1, in this order:
+ *   s = arc[b] once, then s = s + vn(i-1) * dt;  sc = fmin(s, arc[Lm-1]) (clamped to the end of the path, where the reference
+ *   raises);  j = the first index in [0, Lm) with arc[j] >= sc, Lm if there is none;  idx = min(max(j, 1), Lm-1), xlo = arc[idx-1],
+ *   xhi = arc[idx].  If xhi != xlo: w = sc - xlo, inv = xhi - xlo, xn = (x[idx] - x[idx-1]) / inv * w + x[idx-1], yn likewise;
+ *   otherwise xn = x[idx-1], yn = y[idx-1].  Heading: the (c, s) of sample idx-1 if xhi == xlo or w + w <= inv, else that of
+ *   sample idx (no new trigonometry).  These are be.py's interp1d semantics (searchsorted-left segment, clipped), anchored at
+ *   arc[b] rather than at 0.
+ *  4. Hit.  The footprint of (xn, yn, c, s) is that of fo_scene_hidden_reach, with its clipping and its rule outside the window
+ *   (A = 0 on raster road, 255 elsewhere).  hit(i) iff some footprint cell has A <= i.  brake_first[m][b] = min { i : hit(i) }, -1 =
+ *   none.
+ *  5. commit[m] = the smallest b in [0, Lm) with 0 <= first[m] <= b (the candidate itself is already in reached road) or
+ *   0 <= brake_first[m][b] < stop[m][b] (the braking ego meets reached road while it still moves), -1 = none.  A conflict at or
+ *   after stop is a standing ego and does not count.
+ *  Outputs, every byte written by every call: d_brake_first [M][T], d_stop [M][T], d_commit [M], int32.
+ *  Safety of the data: the first-index rule is non-decreasing in sc and sc is non-decreasing in i, so a forward-only index is
+ *   exact for any content of arc; idx is clamped before any read; NaN in v or arc goes wherever fmax / fmin / the comparisons
+ *   send it and never reads out of range.
+ *  Not claimed: the manoeuvre follows the candidate's own path only as far as that path goes (clamped at its end); manoeuvres
+ *   still moving at the last sample (stop == Lm) are decided only within the horizon; the heading is that of the nearer sample,
+ *   off by at most half a step's turn (the caller's inflation is the margin for it); the hidden road user is the forecast's
+ *   (v_max, margin, metric and flow are baked into A).
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_brake:"): J outside
+ * [1, 254]; no h_r2 or base.d_arrival; a window outside [1, 32768]^2; h_r2 refused as by fo_scene_hidden_reach; M < 0; a_brake
+ * negative or not finite; dt not positive and finite; with M > 0: T outside [1, J], no d_x / d_y / d_heading / d_first, no d_v or
+ * d_arc, no output buffer, or extents refused as by fo_scene_hidden_reach. */
+typedef struct {
+  fo_hidden_reach_t base;                   /* M, T, d_x, d_y, d_heading, d_len_or_null, hl, hw, wb, J, h_r2, window: those of the call
+                                               that made the map; d_arrival and d_first are INPUTS here */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  double a_brake, dt;
+  int32_t *d_brake_first, *d_stop;          /* [M][T] */
+  int32_t *d_commit;                        /* [M] */
+} fo_hidden_brake_t;
+int fo_scene_hidden_brake(fo_ctx *ctx, const fo_hidden_brake_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

@@ -3,7 +3,7 @@ whole call, next to the visibility stage the forecast
 follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
-                                       [--flow any|lanes] [--clearance] [--witness]
+                                       [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -13,6 +13,10 @@ without heading reuse, the three derivations).
 
 ``--witness`` (with ``--metric road``): ``hidden_witness`` -- the forecast plus the route behind every candidate's finding (§5.10
 "Witnesses") -- joins the timed loop, next to the forecast alone; also the number of distinct sources and the longest walk.
+
+``--brake [A]``: ``hidden_brake`` -- the forecast plus the brake clearance of every (candidate, brake start) at A m/s^2 (§5.10
+"Brake clearance"; default: the vehicle's ``a_max``) -- joins the timed loop; also the manoeuvre poses the kernel scanned (from its
+outputs: up to the first hit, one scan for a standing ego), the longest manoeuvre and the candidates by ``commit`` class.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -58,6 +62,8 @@ def main():
     ap.add_argument("--flow", default="any", choices=("any", "lanes"), help="lanes: hidden vehicles follow the lanes (needs --metric road)")
     ap.add_argument("--clearance", action="store_true", help="time hidden_clearance + .reach x 3 against three hidden_reach calls")
     ap.add_argument("--witness", action="store_true", help="time hidden_witness next to hidden_reach (needs --metric road)")
+    ap.add_argument("--brake", nargs="?", type=float, const=SY.VEHICLE_BMW320I[4], default=None, metavar="A",
+                    help="time hidden_brake at A m/s^2 (default: the vehicle's a_max) next to hidden_reach")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -108,6 +114,24 @@ def main():
         res["longest_walk"] = int(steps.max(initial=-1))
         res["walk_steps_total"] = int(steps[steps > 0].sum())
         res["agents_selected"] = len(w.select())
+    if a.brake is not None:
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbk = lambda: sm.hidden_brake(tx, ty, tth, tv, vehicle=veh, v_max=a.v_max, dt=0.1, a_brake=a.brake, metric=a.metric, flow=a.flow)
+        b_out = hbk()
+        res["brake_call_ms"] = _median_ms(hbk, a.calls)
+        bf, st, commit = (t.cpu().numpy().astype(np.int64) for t in (b_out.brake_first, b_out.stop, b_out.commit))
+        b = np.arange(T)[None, :]
+        i0 = np.maximum(st, b + 1)                  # the sample at which the standing pose is first taken
+        moving = np.minimum(i0, T) - (b + 1)        # poses before it
+        scans = np.where((bf >= 0) & (bf < i0), bf - b, moving + (i0 < T))
+        res["a_brake"] = float(a.brake)
+        res["manoeuvres"] = int(M * T)
+        res["manoeuvre_poses_scanned"] = int(scans.sum())
+        res["manoeuvre_poses_defined"] = int(M * T * (T - 1) // 2)
+        res["longest_manoeuvre_scanned"] = int(scans.max(initial=0))
+        res["commit_classes"] = {"never": int((commit < 0).sum()), "now": int((commit == 0).sum()), "later": int((commit > 0).sum())}
+        res["commit_median_of_later"] = float(np.median(commit[commit > 0])) if (commit > 0).any() else None
+        res["decided_until_min"] = int(b_out.decided_until().min()) if M else None
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
