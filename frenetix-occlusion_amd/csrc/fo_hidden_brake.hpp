@@ -44,6 +44,34 @@ __device__ __forceinline__ double hb_speed(double vb, double a_brake, double dt,
   return fmax(vb - a_brake * ((double)(i - b) * dt), 0.0);
 }
 
+// The pose step of a manoeuvre, the ONE statement of step 3's arithmetic on the device (fo_hr_brake_kernel and
+// fo_hr_brake_classes_kernel, fo_hidden_brake_classes.hpp, both walk with it): the running length s gains vn(i - 1) dt, the segment
+// index j moves forward to the first sample with arc >= the clamped length, the position is interpolated between the segment's
+// ends and the heading is the nearer end's.  X .. ARC: the trajectory's rows (LDS), Lm >= 2 its length (i = b + 1 < Lm), last =
+// Lm - 1 and arc_end = ARC[last] from the caller; every index is clamped to [0, Lm) before it is used.  (`last` is the caller's
+// value on purpose: with Lm - 1 formed in here as well, fo_hr_brake_kernel's address of ARC[Lm - 1] was selected differently and the
+// kernel, an instruction longer, took 1.4 % more time; written so, its gfx950 assembly is what it was before the step was shared.)
+struct HbPose { double x, y, c, s; };
+__device__ __forceinline__ HbPose hb_pose_step(const double *X, const double *Y, const double *C, const double *S, const double *ARC,
+                                               int Lm, int last, double arc_end, double vb, double a_brake, double dt, int i, int b, double &s,
+                                               int &j) {
+  s = s + hb_speed(vb, a_brake, dt, i - 1, b) * dt;
+  const double sc = fmin(s, arc_end);
+  while (j < Lm && !(ARC[j] >= sc)) ++j;
+  int idx = j < 1 ? 1 : j;
+  idx = idx < last ? idx : last;
+  const double xlo = ARC[idx - 1], xhi = ARC[idx];
+  double xn = X[idx - 1], yn = Y[idx - 1];
+  int hd = idx - 1;
+  if (xhi != xlo) {
+    const double w = sc - xlo, inv = xhi - xlo;
+    xn = (X[idx] - X[idx - 1]) / inv * w + X[idx - 1];
+    yn = (Y[idx] - Y[idx - 1]) / inv * w + Y[idx - 1];
+    if (!(w + w <= inv)) hd = idx;
+  }
+  return HbPose{xn, yn, C[hd], S[hd]};
+}
+
 // dynamic LDS: brake_lds_bytes(T)
 __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeArgs a) {
   extern __shared__ double hb_rows[];   // per trajectory of the workgroup: x, y, cos, sin, arc, v, T entries each
@@ -80,31 +108,19 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeAr
   for (int b = kl; b < T; b += G) {
     int bf = -1, st = -1;
     if (b < Lm) {                       // (Lm = 0 on lanes without a trajectory)
-      const double vb = V[b], arc_end = ARC[Lm - 1];
+      const int last = Lm - 1;
+      const double vb = V[b], arc_end = ARC[last];
       st = Lm;
       for (int i = b; i < Lm; ++i)
         if (hb_speed(vb, a.a_brake, a.dt, i, b) == 0.0) { st = i; break; }
       double s = ARC[b];
       int j = 0;
       for (int i = b + 1; i < Lm; ++i) {
-        s = s + hb_speed(vb, a.a_brake, a.dt, i - 1, b) * a.dt;
-        const double sc = fmin(s, arc_end);
-        while (j < Lm && !(ARC[j] >= sc)) ++j;
-        int idx = j < 1 ? 1 : j;
-        idx = idx < Lm - 1 ? idx : Lm - 1;                       // (Lm >= 2 here: b + 1 < Lm)
-        const double xlo = ARC[idx - 1], xhi = ARC[idx];
-        double xn = X[idx - 1], yn = Y[idx - 1];
-        int hd = idx - 1;
-        if (xhi != xlo) {
-          const double w = sc - xlo, inv = xhi - xlo;
-          xn = (X[idx] - X[idx - 1]) / inv * w + X[idx - 1];
-          yn = (Y[idx] - Y[idx - 1]) / inv * w + Y[idx - 1];
-          if (!(w + w <= inv)) hd = idx;
-        }
+        const HbPose p = hb_pose_step(X, Y, C, S, ARC, Lm, last, arc_end, vb, a.a_brake, a.dt, i, b, s, j);
         // the ego stands from sample st on (vn = 0 adds nothing to s): this pose is the manoeuvre's last one
         const bool stands = i >= st;
         int amin = 255;
-        fo_hr_scan_pose_rows(a, xn, yn, C[hd], S[hd], A, 255, lox, loy, hix, hiy, 0, 1,
+        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, A, 255, lox, loy, hix, hiy, 0, 1,
                              [&](int av, int, int) { amin = amin < av ? amin : av; });
         if (stands) {                   // hit(i') for i' >= i iff amin <= i'
           const int at = amin > i ? amin : i;

@@ -44,6 +44,7 @@
 //   fo_hidden_witness.hpp    fo_hr_witness_kernel  the route behind each candidate's finding: conflict cell, walk back along d
 //   fo_hidden_brake.hpp      fo_hr_brake_kernel  brake clearance: follow a candidate until sample b, then brake -- a lane per (m, b)
 //   fo_hidden_clearance.hpp  fo_hc_*_kernel  hidden-traffic clearance: the key map behind every reach table, its minimum per pose
+//   fo_hidden_brake_classes.hpp  fo_hr_brake_classes_kernel  brake clearance for several hidden-user speeds: one walk over the key map
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -56,6 +57,7 @@
 #include "fo_hidden_witness.hpp"
 #include "fo_hidden_brake.hpp"
 #include "fo_hidden_clearance.hpp"
+#include "fo_hidden_brake_classes.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
 #include "fo_future_visibility.hpp"
@@ -825,6 +827,68 @@ int fo_scene_hidden_clearance(fo_ctx *ctx, const fo_hidden_clearance_t *p, void 
 
 int fo_scene_hidden_clearance_flow(fo_ctx *ctx, const fo_hidden_clearance_t *p, void *stream) {
   return hidden_clearance_call(ctx, p, true, "fo_scene_hidden_clearance_flow", stream);
+}
+
+// the brake clearance of every (class, trajectory, brake start): one launch over the key map of a clearance call
+// (fo_hidden_brake_classes.hpp); the threshold table travels as a kernel argument
+int fo_scene_hidden_brake_classes(fo_ctx *ctx, const fo_hidden_brake_classes_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_brake_classes";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  if (p->C < 1 || p->C > FO_HIDDEN_BRAKE_MAX_CLASSES)
+    return fo_fail(ctx, FO_E_ARG, "%s: C = %d outside [1, FO_HIDDEN_BRAKE_MAX_CLASSES = %d]", fn, p->C, FO_HIDDEN_BRAKE_MAX_CLASSES);
+  if (!p->h_thr) return fo_fail(ctx, FO_E_ARG, "%s: no threshold table h_thr [C][T]", fn);
+  if ((rc = hr_check_extent(ctx, p->win_nx, p->win_ny, fn))) return rc;
+  if (p->r2_cap < 0) return fo_fail(ctx, FO_E_ARG, "%s: r2_cap = %d is negative", fn, p->r2_cap);
+  if ((rc = hr_check_halo(ctx, p->r2_cap, "r2_cap", "v_cap", fn))) return rc;
+  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
+  if (!(p->a_brake >= 0.0) || !std::isfinite(p->a_brake))      // (NaN fails every comparison)
+    return fo_fail(ctx, FO_E_ARG, "%s: a_brake = %g, a finite deceleration >= 0 is needed", fn, p->a_brake);
+  if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return fo_fail(ctx, FO_E_ARG, "%s: dt = %g, a finite step > 0 is needed", fn, p->dt);
+  if (p->M == 0) return FO_OK;
+  const int T = p->T, C = p->C;
+  if (T < 1 || T > HR_MAX_J) return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, %d]", fn, T, HR_MAX_J);
+  if (C * T > FO_HIDDEN_BRAKE_MAX_TABLE)
+    return fo_fail(ctx, FO_E_ARG, "%s: C * T = %d * %d = %d entries, the table is a kernel argument of at most "
+                   "FO_HIDDEN_BRAKE_MAX_TABLE = %d", fn, C, T, C * T, FO_HIDDEN_BRAKE_MAX_TABLE);
+  const int64_t cap = (int64_t)169 * p->r2_cap;
+  for (int c = 0; c < C; ++c) {
+    const int32_t *row = p->h_thr + (size_t)c * T;
+    if (row[0] < 0) return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d][0] = %d is negative", fn, c, row[0]);
+    for (int j = 1; j < T; ++j)
+      if (row[j] < row[j - 1])
+        return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d] decreases at entry %d (%d after %d)", fn, c, j, row[j], row[j - 1]);
+    if (row[T - 1] > cap)
+      return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d][T-1] = %d lies beyond 169 r2_cap = %lld (the key map ends at the cap)", fn, c,
+                     row[T - 1], (long long)cap);
+  }
+  if (!p->d_x || !p->d_y || !p->d_heading)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0", fn);
+  if (!p->d_key || !p->d_qmin)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_key [win_ny][win_nx] and d_qmin [M][T] of the clearance are required with M > 0", fn);
+  if (!p->d_v || !p->d_arc) return fo_fail(ctx, FO_E_ARG, "%s: d_v and d_arc [M][T] are required with M > 0", fn);
+  if (!p->d_brake_first || !p->d_stop || !p->d_commit || !p->d_first)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_brake_first [C][M][T], d_stop [M][T], d_commit and d_first [C][M] are required with M > 0", fn);
+  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HrBrakeClassesArgs a{p->M, T, brake_group(T), C, p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw, p->wb,
+                             sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0,
+                             p->win_iy0, p->win_nx, p->win_ny, p->d_key, p->d_qmin, p->d_v, p->d_arc, p->a_brake, p->dt,
+                             p->d_brake_first, p->d_stop, p->d_commit, p->d_first};
+  HbThr thr;
+  for (int t = 0; t < FO_HIDDEN_BRAKE_MAX_TABLE; ++t) thr.v[t] = t < C * T ? p->h_thr[t] : 0;
+  const dim3 grid((unsigned)brake_classes_blocks(p->M, T)), block(HB_THREADS);
+  const size_t lds = brake_classes_lds_bytes(T, C);
+  hipStream_t s = (hipStream_t)stream;
+  switch (brake_classes_width(C)) {
+    case 1: hipLaunchKernelGGL(fo_hr_brake_classes_kernel<1>, grid, block, lds, s, a, thr); break;
+    case 2: hipLaunchKernelGGL(fo_hr_brake_classes_kernel<2>, grid, block, lds, s, a, thr); break;
+    case 4: hipLaunchKernelGGL(fo_hr_brake_classes_kernel<4>, grid, block, lds, s, a, thr); break;
+    default: hipLaunchKernelGGL(fo_hr_brake_classes_kernel<8>, grid, block, lds, s, a, thr); break;
+  }
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
 }
 
 // fo_scene_spawn on the step's own structure (the members fo_step_t lists under fo_scene_spawn); at (fo_step_run): the

@@ -57,6 +57,14 @@ inline int brake_group(int T) { int G = 1; while (G < T && G < 64) G <<= 1; retu
 inline int brake_per_block(int T) { return HB_THREADS / brake_group(T); }
 inline int brake_blocks(int M, int T) { const int p = brake_per_block(T); return (int)(((int64_t)M + p - 1) / p); }
 inline size_t brake_lds_bytes(int T) { return (size_t)brake_per_block(T) * 6 * (size_t)T * sizeof(double); }
+// the brake kernel by classes: the same lanes and grid; per trajectory its qmin row (T int32) joins the six rows in LDS, and the
+// workgroup keeps the threshold table thr [C][T] int32 behind them (at T = 254, C * T = 896 at most: 56 416 bytes).  The per-class
+// state lives in registers, indexed at compile time: the kernel's class count is the power of two >= C
+inline int brake_classes_width(int C) { return C <= 1 ? 1 : C <= 2 ? 2 : C <= 4 ? 4 : 8; }
+inline int brake_classes_blocks(int M, int T) { return brake_blocks(M, T); }
+inline size_t brake_classes_lds_bytes(int T, int C) {
+  return (size_t)brake_per_block(T) * (size_t)T * (6 * sizeof(double) + sizeof(int32_t)) + (size_t)C * (size_t)T * sizeof(int32_t);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -37,6 +37,7 @@ EXPORTS = [
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
+    "fo_scene_hidden_brake_classes",
 ]
 
 
@@ -113,6 +114,19 @@ class HiddenWitness(C.Structure):       # fo_hidden_witness_t
 class HiddenBrake(C.Structure):         # fo_hidden_brake_t
     _fields_ = [("base", HiddenReach), ("d_v", C.c_void_p), ("d_arc", C.c_void_p), ("a_brake", C.c_double), ("dt", C.c_double),
                 ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p)]
+
+
+HIDDEN_BRAKE_MAX_CLASSES = 8    # FO_HIDDEN_BRAKE_MAX_CLASSES: classes of hidden road users one fo_scene_hidden_brake_classes call serves
+HIDDEN_BRAKE_MAX_TABLE = 896    # FO_HIDDEN_BRAKE_MAX_TABLE: entries C * T of its threshold table (a kernel argument)
+
+
+class HiddenBrakeClasses(C.Structure):  # fo_hidden_brake_classes_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("r2_cap", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p), ("d_qmin", C.c_void_p), ("d_v", C.c_void_p),
+                ("d_arc", C.c_void_p), ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
+                ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
 
 
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
@@ -225,6 +239,7 @@ def load():
     lib.fo_scene_hidden_clearance_flow.argtypes = [vp, C.POINTER(HiddenClearance), vp]
     lib.fo_scene_hidden_witness.argtypes = [vp, C.POINTER(HiddenWitness), vp]
     lib.fo_scene_hidden_brake.argtypes = [vp, C.POINTER(HiddenBrake), vp]
+    lib.fo_scene_hidden_brake_classes.argtypes = [vp, C.POINTER(HiddenBrakeClasses), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -408,6 +408,21 @@ def travelled_arc(x, y):
     return np.insert(np.cumsum(seg, axis=-1), 0, 0.0, axis=-1)
 
 
+def _decided_until(stop, lengths):
+    """``decided_until`` of :class:`HiddenBrake` and :class:`HiddenBrakeClasses`: ``stop [M, T]`` does not depend on the hidden road
+    user"""
+    M, T = (int(v) for v in stop.shape)
+    dev = stop.device
+    Lm = torch.full((M,), T, dtype=torch.int64, device=dev)
+    if lengths is not None:
+        Lm = torch.clamp(lengths.to(torch.int64), 0, T)
+    if T == 0:
+        return Lm.to(torch.int32)
+    b = torch.arange(T, device=dev, dtype=torch.int64)[None, :]
+    open_end = (stop.to(torch.int64) == Lm[:, None]) & (b < Lm[:, None])
+    return torch.where(open_end, b, Lm[:, None]).amin(dim=1).to(torch.int32)
+
+
 @dataclass
 class HiddenBrake:
     """what :meth:`SensorModel.hidden_brake` returns (DESIGN.md §5.10 "Brake clearance"): ``reach`` is the :class:`HiddenReach` of
@@ -437,16 +452,7 @@ class HiddenBrake:
         """``[M]`` int32: the smallest brake start b with ``stop[m, b] == Lm`` -- from there on the horizon no longer sees the
         braking ego stand, so ``commit`` speaks only of the samples it has -- and ``Lm`` where every manoeuvre stands in time.
         Torch ops on the tensors' device, nothing is read back."""
-        M, T = (int(v) for v in self.stop.shape)
-        dev = self.stop.device
-        Lm = torch.full((M,), T, dtype=torch.int64, device=dev)
-        if self.lengths is not None:
-            Lm = torch.clamp(self.lengths.to(torch.int64), 0, T)
-        if T == 0:
-            return Lm.to(torch.int32)
-        b = torch.arange(T, device=dev, dtype=torch.int64)[None, :]
-        open_end = (self.stop.to(torch.int64) == Lm[:, None]) & (b < Lm[:, None])
-        return torch.where(open_end, b, Lm[:, None]).amin(dim=1).to(torch.int32)
+        return _decided_until(self.stop, self.lengths)
 
 
 def hidden_brake(self, x, y, theta, v, *, vehicle, v_max, dt, a_brake, margin=None, inflate=0.0, lengths=None, metric="euclid",
@@ -484,3 +490,94 @@ def hidden_brake(self, x, y, theta, v, *, vehicle, v_max, dt, a_brake, margin=No
     self.ctx.call("fo_scene_hidden_brake", C.byref(args), N.current_stream(self._dev_index))
     self._hb_inputs = (tv, arc)                             # (stay referenced until the next call, as in hidden_reach)
     return HiddenBrake(reach, brake_first, stop, commit, arc, a_brake, float(dt), tlen)
+
+
+def hidden_brake_thresholds(speeds, dt, margin, cell_size, T):
+    """the threshold table of :meth:`SensorModel.hidden_brake_classes` (DESIGN.md §5.10 "Brake clearance by classes"): host int32
+    ``[C, T]``, row c = ``169 * hidden_reach_r2(speeds[c], dt, margin, cell_size, T)`` -- a cell's key is at most ``thr[c, j]`` iff a
+    road user of up to ``speeds[c]`` m/s may be in it at sample j"""
+    rows = [169 * hidden_reach_r2(float(v), dt, margin, cell_size, T).astype(np.int64) for v in speeds]
+    return np.ascontiguousarray(np.stack(rows).astype(np.int32)) if rows else np.zeros((0, int(T)), dtype=np.int32)
+
+
+@dataclass
+class HiddenBrakeClasses:
+    """what :meth:`SensorModel.hidden_brake_classes` returns (DESIGN.md §5.10 "Brake clearance by classes"): ``clearance`` is the
+    :class:`HiddenClearance` the manoeuvres were held against (``v_cap = max(speeds)``), ``speeds`` the C hidden-user speeds (m/s) in
+    the order given, ``thr`` (host int32 ``[C, T]``) their threshold table (:func:`hidden_brake_thresholds`), and (device tensors,
+    int32) ``brake_first [C, M, T]``, ``stop [M, T]``, ``commit [C, M]``, ``first [C, M]``: row c of each is, bit for bit,
+    ``brake_first`` / ``stop`` / ``commit`` of ``hidden_brake(v_max=speeds[c])`` and ``first`` of its forecast, with the same metric,
+    flow, margin and hidden set (see :class:`HiddenBrake` for their meaning).  ``arc``, ``a_brake``, ``dt``, ``lengths`` as there."""
+    clearance: HiddenClearance
+    speeds: tuple
+    thr: np.ndarray
+    brake_first: torch.Tensor
+    stop: torch.Tensor
+    commit: torch.Tensor
+    first: torch.Tensor
+    arc: torch.Tensor
+    a_brake: float
+    dt: float
+    lengths: Optional[torch.Tensor] = None
+
+    def decided_until(self):
+        """``[M]`` int32, as :meth:`HiddenBrake.decided_until`: ``stop`` is the same for every class"""
+        return _decided_until(self.stop, self.lengths)
+
+    def critical_speed(self):
+        """``[M]`` float64 (m/s): the smallest ``speeds[c]`` with ``commit[c, m] >= 0`` -- the slowest of the given hidden road users
+        against which candidate m is not fail-safe over the whole horizon --, ``+inf`` if there is none.  Torch ops on the
+        tensors' device, nothing is read back."""
+        dev = self.commit.device
+        sp = torch.as_tensor(np.asarray(self.speeds, dtype=np.float64).reshape(-1, 1), device=dev)
+        inf = torch.full((), float("inf"), dtype=torch.float64, device=dev)
+        return torch.where(self.commit >= 0, sp, inf).amin(dim=0)
+
+
+def hidden_brake_classes(self, x, y, theta, v, *, vehicle, speeds, dt, a_brake, margin=None, inflate=0.0, lengths=None,
+                         metric="euclid", flow="any", heading=None):
+    """Hidden-traffic brake clearance for several hidden-user speeds in one pass (``fo_scene_hidden_brake_classes``; DESIGN.md
+    §5.10 "Brake clearance by classes"): runs ``hidden_clearance(..., v_cap=max(speeds), heading=heading)`` and, on the very same
+    device inputs, ONE more launch that walks the manoeuvre "follow the candidate until sample b, then brake at ``a_brake``" of
+    every (candidate, b) over the key map and decides it for every speed of ``speeds`` (1 .. 8 values, m/s, any order) at once;
+    returns a :class:`HiddenBrakeClasses`.  Row c of its outputs is what ``hidden_brake(v_max=speeds[c])`` gives, bit for bit.
+    ``len(speeds) * T`` may not exceed ``_native.HIDDEN_BRAKE_MAX_TABLE``: the thresholds travel as a kernel argument.  The other
+    arguments as for :meth:`hidden_brake` and :meth:`hidden_clearance`.  Nothing is read back and nobody waits for the kernels."""
+    try:
+        speeds = tuple(float(s) for s in speeds)
+    except TypeError:
+        speeds = ()
+    if not 1 <= len(speeds) <= N.HIDDEN_BRAKE_MAX_CLASSES or not all(math.isfinite(s) and s >= 0.0 for s in speeds):
+        raise ValueError(f"hidden_brake_classes: speeds must hold 1 .. {N.HIDDEN_BRAKE_MAX_CLASSES} finite values >= 0")
+    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
+    if len(speeds) * T > N.HIDDEN_BRAKE_MAX_TABLE:
+        raise ValueError(f"hidden_brake_classes: {len(speeds)} speeds x {T} samples = {len(speeds) * T} thresholds, at most "
+                         f"{N.HIDDEN_BRAKE_MAX_TABLE} are possible (they travel as a kernel argument)")
+    clearance = hidden_clearance(self, x, y, theta, vehicle=vehicle, v_cap=max(speeds), dt=dt, margin=margin, inflate=inflate,
+                                 lengths=lengths, metric=metric, heading=heading, flow=flow)
+    tx, ty, thead, tlen = self._hc_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T):
+        raise ValueError("hidden_brake_classes: v must be [M, T]")
+    a_brake = float(a_brake)
+    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
+        raise ValueError("hidden_brake_classes: a_brake >= 0 and finite")
+    dev, w, C_ = self.device, clearance.window, len(speeds)
+    thr = hidden_brake_thresholds(speeds, clearance.dt, clearance.margin, clearance.cell_size, T)
+    tv = N.on_device(v, dev)
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    arc = N.on_device(arc, dev)
+    brake_first = torch.empty((C_, M, T), dtype=torch.int32, device=dev)
+    stop = torch.empty((M, T), dtype=torch.int32, device=dev)
+    commit = torch.empty((C_, M), dtype=torch.int32, device=dev)
+    first = torch.empty((C_, M), dtype=torch.int32, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    args = N.HiddenBrakeClasses(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
+                                hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
+                                win_ny=w.ny, r2_cap=int(clearance.r2_cap), C=C_, d_key=clearance.key.data_ptr(), d_qmin=N.ptr(clearance.qmin),
+                                d_v=N.ptr(tv), d_arc=N.ptr(arc), a_brake=a_brake, dt=float(dt), h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)),
+                                d_brake_first=N.ptr(brake_first), d_stop=N.ptr(stop), d_commit=N.ptr(commit), d_first=N.ptr(first))
+    self.ctx.call("fo_scene_hidden_brake_classes", C.byref(args), N.current_stream(self._dev_index))
+    self._hbc_inputs = (tv, arc)                            # (stay referenced until the next call, as in hidden_brake)
+    return HiddenBrakeClasses(clearance, speeds, thr, brake_first, stop, commit, first, arc, a_brake, float(dt), tlen)

@@ -414,6 +414,25 @@ class FOInterface:
                                               margin=om["margin"] if margin is None else margin, dt=self.dt,
                                               a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate, metric=metric, flow=flow)
 
+    def hidden_brake_classes(self, trajectories, speeds, a_brake=None, margin=None, inflate=0.0, metric="euclid", flow="any"):
+        """EXTENSION, not part of the reference: the fail-safe question of :meth:`hidden_brake` for several hidden road users at
+        once -- ``speeds`` (m/s, 1 .. 8 values: a pedestrian, a cyclist, a car) -- from one clearance and one walk over its key map
+        (:meth:`SensorModel.hidden_brake_classes`; returns its :class:`~frenetix_occlusion.sensor_model.HiddenBrakeClasses`:
+        ``commit [C, M]``, ``first [C, M]``, ``brake_first [C, M, T]``, ``stop [M, T]``, row c as ``hidden_brake(v_max=speeds[c])``
+        gives them; ``.critical_speed()`` the slowest of them a candidate is not fail-safe against).  Defaults as for
+        :meth:`hidden_brake`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_classes needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        return self.sensor_model.hidden_brake_classes(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], speeds=speeds,
+                                                      margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                      a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate, metric=metric,
+                                                      flow=flow)
+
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
         metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of

@@ -585,6 +585,62 @@ typedef struct {
 } fo_hidden_brake_t;
 int fo_scene_hidden_brake(fo_ctx *ctx, const fo_hidden_brake_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic BRAKE CLEARANCE BY CLASSES (DESIGN.md §5.10 "Brake clearance by classes")
+ * -- the brake clearance above for up to FO_HIDDEN_BRAKE_MAX_CLASSES hidden road users of different speeds (a pedestrian, a
+ * cyclist, a car) from ONE walk over the clearance's key map, in place of one forecast and one walk per speed.  Opt-in and
+ * additive: one launch, nothing is read back, no other output changes.
+ *  Inputs: those of ONE fo_scene_hidden_clearance or fo_scene_hidden_clearance_flow call of this step -- trajectories, headings,
+ *   d_len_or_null, hl, hw, wb, the window and r2_cap -- with its outputs key = d_key [win_ny][win_nx] and qmin = d_qmin [M][T];
+ *   d_v, d_arc [M][T], a_brake >= 0 and dt > 0 as in fo_scene_hidden_brake; C classes, 1 <= C <= FO_HIDDEN_BRAKE_MAX_CLASSES; the
+ *   host table h_thr [C][T] int32, row c = 169 * R2_c[j] for the reach table R2_c of class c: every row non-decreasing with
+ *   0 <= thr[c][j] and thr[c][T-1] <= 169 * r2_cap.  The table travels as a kernel argument (no transfer, no device buffer), hence
+ *   C * T <= FO_HIDDEN_BRAKE_MAX_TABLE (3 584 bytes: with the other arguments under the 4 KB of a kernel's arguments) and
+ *   T <= 254.  Lm = T clipped by len[m].
+ *  For trajectory m, brake start b in 0 .. T-1 and class c:
+ *  1. Steps 1 - 3 of fo_scene_hidden_brake word for word: stop[m][b], the speed profile vn, the re-sampled poses (xn, yn) and the
+ *   heading rule.  None of them depends on the class.
+ *  2. q(i) = the minimum of key over the footprint cells of the braking pose i, with the scan, the clipping and the rule outside
+ *   the window of fo_scene_hidden_clearance (key 0 on raster road, FO_HIDDEN_CLEARANCE_NONE elsewhere); NONE for an empty footprint.
+ *  3. hit_c(i) iff q(i) <= thr[c][i].
+ *  4. brake_first[c][m][b] = min { i in (b, Lm) : hit_c(i) }, -1 = none (and for b >= Lm, where stop[m][b] = -1).
+ *  5. first[c][m] = min { k < Lm : qmin[m][k] <= thr[c][k] }, -1 = none.
+ *  6. commit[c][m] = the smallest b in [0, Lm) with 0 <= first[c][m] <= b or 0 <= brake_first[c][m][b] < stop[m][b], -1 = none.
+ *  Outputs, every byte written by every call, int32: d_brake_first [C][M][T], d_stop [M][T], d_commit [C][M], d_first [C][M].
+ *  The tie: for every class whose row is 169 times the reach table of some v_c, brake_first[c], stop, commit[c] and first[c] equal,
+ *   bit for bit, what fo_scene_hidden_brake gives on the forecast of v_c with the same metric, flow, margin and hidden set.  Per
+ *   cell A <= i iff key <= thr[c][i], outside the window too (0 <= every threshold < NONE); some cell qualifies iff the minimum
+ *   does; after stop the pose is fixed and thr[c][.] does not decrease, so one scan answers the remaining samples of every class.
+ *  Safety of the data: as fo_scene_hidden_brake; key, qmin and the table may hold anything the refusals let through, no index
+ *   depends on them.
+ *  Not claimed: what fo_scene_hidden_brake does not claim; a class speed above the clearance's cap is refused, not clipped.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_brake_classes:"): C outside
+ * [1, 8]; no h_thr; a window outside [1, 32768]^2; r2_cap negative or beyond FO_HIDDEN_REACH_MAX_HALO; M < 0; a_brake negative or
+ * not finite; dt not positive and finite; with M > 0: T outside [1, 254]; C * T > FO_HIDDEN_BRAKE_MAX_TABLE; a row that is
+ * negative, decreases or ends beyond 169 * r2_cap; no d_x / d_y / d_heading; no d_key or d_qmin; no d_v or d_arc; a missing output;
+ * extents refused as by fo_scene_hidden_reach. */
+#define FO_HIDDEN_BRAKE_MAX_CLASSES 8
+#define FO_HIDDEN_BRAKE_MAX_TABLE 896
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearance */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearance's window */
+  int32_t r2_cap;                           /* the clearance's cap: no row of h_thr ends beyond 169 * r2_cap */
+  int32_t C;                                /* classes */
+  const int32_t *d_key;                     /* [win_ny][win_nx] the clearance's key map (INPUT) */
+  const int32_t *d_qmin;                    /* [M][T] the clearance's minimum per pose (INPUT) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  double a_brake, dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  int32_t *d_brake_first;                   /* [C][M][T] */
+  int32_t *d_stop;                          /* [M][T] */
+  int32_t *d_commit, *d_first;              /* [C][M] */
+} fo_hidden_brake_classes_t;
+int fo_scene_hidden_brake_classes(fo_ctx *ctx, const fo_hidden_brake_classes_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

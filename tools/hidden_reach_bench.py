@@ -4,6 +4,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
+                                       [--brake-classes v1,v2,...]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -17,6 +18,12 @@ without heading reuse, the three derivations).
 ``--brake [A]``: ``hidden_brake`` -- the forecast plus the brake clearance of every (candidate, brake start) at A m/s^2 (§5.10
 "Brake clearance"; default: the vehicle's ``a_max``) -- joins the timed loop; also the manoeuvre poses the kernel scanned (from its
 outputs: up to the first hit, one scan for a standing ego), the longest manoeuvre and the candidates by ``commit`` class.
+
+``--brake-classes v1,v2,...``: ``hidden_brake_classes`` for these hidden-user speeds (m/s) at the deceleration of ``--brake`` (§5.10
+"Brake clearance by classes") -- one clearance at the fastest speed plus ONE walk that decides every class -- next to one
+``hidden_brake`` call per speed in the same process; every class's rows are compared with that call's (exact integers); also the
+poses the walk scanned (per manoeuvre the longest of its classes' walks), the poses the per-class walks scan together and the
+longest walk.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -64,6 +71,8 @@ def main():
     ap.add_argument("--witness", action="store_true", help="time hidden_witness next to hidden_reach (needs --metric road)")
     ap.add_argument("--brake", nargs="?", type=float, const=SY.VEHICLE_BMW320I[4], default=None, metavar="A",
                     help="time hidden_brake at A m/s^2 (default: the vehicle's a_max) next to hidden_reach")
+    ap.add_argument("--brake-classes", default=None, metavar="V1,V2,...",
+                    help="time hidden_brake_classes for these hidden-user speeds (m/s) next to one hidden_brake call per speed")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -132,6 +141,33 @@ def main():
         res["commit_classes"] = {"never": int((commit < 0).sum()), "now": int((commit == 0).sum()), "later": int((commit > 0).sum())}
         res["commit_median_of_later"] = float(np.median(commit[commit > 0])) if (commit > 0).any() else None
         res["decided_until_min"] = int(b_out.decided_until().min()) if M else None
+    if a.brake_classes:
+        cls_speeds = tuple(float(v) for v in a.brake_classes.split(","))
+        a_brake = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbc = lambda **kw: sm.hidden_brake_classes(tx, ty, tth, tv, vehicle=veh, speeds=cls_speeds, dt=0.1, a_brake=a_brake, metric=a.metric,
+                                                   flow=a.flow, **kw)
+        per_speed = lambda: [sm.hidden_brake(tx, ty, tth, tv, vehicle=veh, v_max=v, dt=0.1, a_brake=a_brake, metric=a.metric, flow=a.flow)
+                             for v in cls_speeds]
+        c_out, singles = hbc(), per_speed()
+        res["brake_class_speeds"] = list(cls_speeds)
+        res["brake_classes_call_ms"] = _median_ms(hbc, a.calls)
+        res["brake_classes_call_reused_heading_ms"] = _median_ms(lambda: hbc(heading=c_out.clearance.heading), a.calls)
+        res["hidden_brake_call_per_speed_ms"] = _median_ms(per_speed, a.calls)
+        for c, one in enumerate(singles):           # the tie: every class is that speed's own call, bit for bit
+            assert torch.equal(c_out.brake_first[c], one.brake_first) and torch.equal(c_out.commit[c], one.commit), cls_speeds[c]
+            assert torch.equal(c_out.first[c], one.reach.first) and torch.equal(c_out.stop, one.stop), cls_speeds[c]
+        bf, st = c_out.brake_first.cpu().numpy().astype(np.int64), c_out.stop.cpu().numpy().astype(np.int64)
+        b = np.arange(T)[None, :]
+        i0 = np.maximum(st, b + 1)                  # the sample at which the standing pose is first taken
+        moving = np.minimum(i0, T) - (b + 1)        # poses before it
+        per_class = np.where((bf >= 0) & (bf < i0[None]), bf - b[None], (moving + (i0 < T))[None])      # [C, M, T]
+        res["class_walk_poses_scanned"] = int(per_class.max(axis=0).sum())
+        res["per_class_poses_scanned"] = [int(v) for v in per_class.sum(axis=(1, 2))]
+        res["longest_class_walk"] = int(per_class.max(initial=0))
+        res["commit_never_per_class"] = [int(v) for v in (c_out.commit < 0).sum(dim=1).cpu()]
+        vc = c_out.critical_speed()
+        res["candidates_by_critical_speed"] = {str(v): int((vc == v).sum()) for v in sorted(set(cls_speeds))}
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
