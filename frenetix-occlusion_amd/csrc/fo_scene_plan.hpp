@@ -65,6 +65,20 @@ inline int brake_classes_blocks(int M, int T) { return brake_blocks(M, T); }
 inline size_t brake_classes_lds_bytes(int T, int C) {
   return (size_t)brake_per_block(T) * (size_t)T * (6 * sizeof(double) + sizeof(int32_t)) + (size_t)C * (size_t)T * sizeof(int32_t);
 }
+// the brake kernel by road users: the same lanes and grid again; per trajectory one qmin row per map (K maps, one per forecast) joins
+// the six rows, the table follows: brake_per_block(T) * T * (48 + 4 K) + 4 C T bytes.  brake_users_lds_bound: no call needs more --
+// T = 254 (4 trajectories per workgroup), 3 maps and a full table of 896 entries, 64 544 bytes, under the 64 KB of a workgroup.
+// The kernel's class count is 4 or 8 (a single class is fo_scene_hidden_brake_classes' case), its map count is K itself
+constexpr int BRAKE_USERS_MAX_MAPS = 3;    // FO_HIDDEN_BRAKE_MAX_MAPS
+constexpr int BRAKE_USERS_MAX_TABLE = 896; // FO_HIDDEN_BRAKE_MAX_TABLE
+inline int brake_users_width(int C) { return C <= 4 ? 4 : 8; }
+inline int brake_users_blocks(int M, int T) { return brake_blocks(M, T); }
+inline size_t brake_users_lds_bytes(int T, int K, int C) {
+  return (size_t)brake_per_block(T) * (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t)) + (size_t)C * (size_t)T * sizeof(int32_t);
+}
+inline size_t brake_users_lds_bound() {
+  return (size_t)brake_per_block(254) * 254 * (6 * sizeof(double) + BRAKE_USERS_MAX_MAPS * sizeof(int32_t)) + BRAKE_USERS_MAX_TABLE * sizeof(int32_t);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -37,7 +37,7 @@ EXPORTS = [
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
-    "fo_scene_hidden_brake_classes",
+    "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users",
 ]
 
 
@@ -126,6 +126,20 @@ class HiddenBrakeClasses(C.Structure):  # fo_hidden_brake_classes_t
                 ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
                 ("r2_cap", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p), ("d_qmin", C.c_void_p), ("d_v", C.c_void_p),
                 ("d_arc", C.c_void_p), ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
+                ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
+
+
+HIDDEN_BRAKE_MAX_MAPS = 3       # FO_HIDDEN_BRAKE_MAX_MAPS: key maps (forecasts) one fo_scene_hidden_brake_users call walks over
+
+
+class HiddenBrakeUsers(C.Structure):    # fo_hidden_brake_users_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
+                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
+                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
+                ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
                 ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
 
 
@@ -240,6 +254,7 @@ def load():
     lib.fo_scene_hidden_witness.argtypes = [vp, C.POINTER(HiddenWitness), vp]
     lib.fo_scene_hidden_brake.argtypes = [vp, C.POINTER(HiddenBrake), vp]
     lib.fo_scene_hidden_brake_classes.argtypes = [vp, C.POINTER(HiddenBrakeClasses), vp]
+    lib.fo_scene_hidden_brake_users.argtypes = [vp, C.POINTER(HiddenBrakeUsers), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

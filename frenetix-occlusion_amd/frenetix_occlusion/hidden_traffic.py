@@ -581,3 +581,131 @@ def hidden_brake_classes(self, x, y, theta, v, *, vehicle, speeds, dt, a_brake, 
     self.ctx.call("fo_scene_hidden_brake_classes", C.byref(args), N.current_stream(self._dev_index))
     self._hbc_inputs = (tv, arc)                            # (stay referenced until the next call, as in hidden_brake)
     return HiddenBrakeClasses(clearance, speeds, thr, brake_first, stop, commit, first, arc, a_brake, float(dt), tlen)
+
+
+@dataclass
+class HiddenBrakeUsers:
+    """what :meth:`SensorModel.hidden_brake_users` returns (DESIGN.md §5.10 "Brake clearance by road users"): ``users`` the C hidden
+    road users ``(speed, metric, flow)`` in the order given, ``clearances`` one :class:`HiddenClearance` per distinct
+    ``(metric, flow)`` in order of first appearance (``v_cap`` = the fastest of its users), ``map_of`` (tuple of C ints) the
+    clearance each user is held against, ``thr`` (host int32 ``[C, T]``) the threshold table (:func:`hidden_brake_thresholds` of the
+    users' speeds), and (device tensors, int32) ``brake_first [C, M, T]``, ``stop [M, T]``, ``commit [C, M]``, ``first [C, M]``: row c
+    of each is, bit for bit, what ``hidden_brake_classes(speeds=(speed_c,), metric=metric_c, flow=flow_c)`` and
+    ``hidden_brake(v_max=speed_c, metric=metric_c, flow=flow_c)`` give.  ``arc``, ``a_brake``, ``dt``, ``lengths`` as in
+    :class:`HiddenBrake`."""
+    clearances: tuple
+    users: tuple
+    map_of: tuple
+    thr: np.ndarray
+    brake_first: torch.Tensor
+    stop: torch.Tensor
+    commit: torch.Tensor
+    first: torch.Tensor
+    arc: torch.Tensor
+    a_brake: float
+    dt: float
+    lengths: Optional[torch.Tensor] = None
+
+    def decided_until(self):
+        """``[M]`` int32, as :meth:`HiddenBrake.decided_until`: ``stop`` is the same for every user"""
+        return _decided_until(self.stop, self.lengths)
+
+    def critical_user(self):
+        """``[M]`` int64: the index of the slowest user with ``commit[c, m] >= 0`` -- the lowest index among equal speeds --, -1 if
+        the candidate is fail-safe against every user.  Torch ops on the tensors' device, nothing is read back."""
+        dev = self.commit.device
+        speeds = [u[0] for u in self.users]
+        order = sorted(range(len(speeds)), key=lambda c: (speeds[c], c))        # a stable ranking: rank r is user order[r]
+        rank = torch.as_tensor(np.argsort(np.asarray(order, dtype=np.int64)).reshape(-1, 1), device=dev)
+        best = torch.where(self.commit >= 0, rank, len(speeds)).amin(dim=0)
+        users = torch.as_tensor(np.asarray(order + [-1], dtype=np.int64), device=dev)
+        return users[best]
+
+    def critical_speed(self):
+        """``[M]`` float64 (m/s): the speed of :meth:`critical_user`, ``+inf`` if there is none"""
+        dev = self.commit.device
+        sp = torch.as_tensor(np.asarray([u[0] for u in self.users] + [float("inf")], dtype=np.float64), device=dev)
+        return sp[self.critical_user()]
+
+
+def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, margin=None, inflate=0.0, lengths=None, heading=None):
+    """Hidden-traffic brake clearance for mixed road users in one walk (``fo_scene_hidden_brake_users``; DESIGN.md §5.10 "Brake
+    clearance by road users"): ``users`` is a sequence of 1 .. 8 ``(speed, metric, flow)`` -- say ``(2.0, "road", "any")`` for a
+    pedestrian, ``(7.0, "road", "lanes")`` for a cyclist and ``(13.9, "road", "lanes")`` for a car.  Runs one
+    ``hidden_clearance`` per distinct ``(metric, flow)`` (``v_cap`` = the fastest of its users; the first call's heading tensor and
+    device inputs go to the later ones, so there is one host-side heading pass) and then ONE launch that walks the manoeuvre of every
+    (candidate, b) once and decides it for every user on that user's key map; returns a :class:`HiddenBrakeUsers`.
+    ``len(users) * T`` may not exceed ``_native.HIDDEN_BRAKE_MAX_TABLE``.  The other arguments as for :meth:`hidden_brake_classes`.
+    Nothing is read back and nobody waits for the kernels."""
+    try:
+        users = tuple(users)
+    except TypeError:
+        users = ()
+    if not 1 <= len(users) <= N.HIDDEN_BRAKE_MAX_CLASSES:
+        raise ValueError(f"hidden_brake_users: users must hold 1 .. {N.HIDDEN_BRAKE_MAX_CLASSES} triples (speed, metric, flow)")
+    for c, u in enumerate(users):
+        try:
+            s, m, f = u
+            s = float(s)
+        except (TypeError, ValueError):
+            raise ValueError(f"hidden_brake_users: users[{c}] = {u!r} is no triple (speed, metric, flow) with a number for the speed") from None
+    users = tuple((float(s), m, f) for s, m, f in users)
+    for c, (s, m, f) in enumerate(users):
+        if m not in HIDDEN_REACH_METRICS:
+            raise ValueError(f"hidden_brake_users: users[{c}]: metric {m!r}, one of {HIDDEN_REACH_METRICS} is possible")
+        if f not in HIDDEN_REACH_FLOWS:
+            raise ValueError(f"hidden_brake_users: users[{c}]: flow {f!r}, one of {HIDDEN_REACH_FLOWS} is possible")
+        if f == "lanes" and m != "road":
+            raise ValueError(f"hidden_brake_users: users[{c}]: flow 'lanes' follows the lanes along the road: it needs metric 'road', "
+                             f"not {m!r}")
+    if not all(math.isfinite(s) and s >= 0.0 for s, _, _ in users):
+        raise ValueError("hidden_brake_users: the users' speeds must be finite and >= 0")
+    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
+    if len(users) * T > N.HIDDEN_BRAKE_MAX_TABLE:
+        raise ValueError(f"hidden_brake_users: {len(users)} users x {T} samples = {len(users) * T} thresholds, at most "
+                         f"{N.HIDDEN_BRAKE_MAX_TABLE} are possible (they travel as a kernel argument)")
+    maps = []                                               # the distinct (metric, flow) in order of first appearance: at most three
+    for _, m, f in users:
+        if (m, f) not in maps:
+            maps.append((m, f))
+    map_of = tuple(maps.index((m, f)) for _, m, f in users)
+    clearances = []
+    cx, cy, clen = x, y, lengths
+    for k, (m, f) in enumerate(maps):
+        v_cap = max(s for c, (s, _, _) in enumerate(users) if map_of[c] == k)
+        clearances.append(hidden_clearance(self, cx, cy, theta, vehicle=vehicle, v_cap=v_cap, dt=dt, margin=margin, inflate=inflate,
+                                           lengths=clen, metric=m, heading=heading, flow=f))
+        cx, cy, heading, clen = self._hc_inputs             # the later clearances take the first one's device inputs and headings
+    tx, ty, thead, tlen = self._hc_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T):
+        raise ValueError("hidden_brake_users: v must be [M, T]")
+    a_brake = float(a_brake)
+    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
+        raise ValueError("hidden_brake_users: a_brake >= 0 and finite")
+    first_c = clearances[0]
+    dev, w, C_, K_ = self.device, first_c.window, len(users), len(maps)
+    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    tv = N.on_device(v, dev)
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    arc = N.on_device(arc, dev)
+    brake_first = torch.empty((C_, M, T), dtype=torch.int32, device=dev)
+    stop = torch.empty((M, T), dtype=torch.int32, device=dev)
+    commit = torch.empty((C_, M), dtype=torch.int32, device=dev)
+    first = torch.empty((C_, M), dtype=torch.int32, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
+    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
+    args = N.HiddenBrakeUsers(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
+                              hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
+                              win_ny=w.ny, K=K_, C=C_, d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                              d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                              r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
+                              map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(arc), a_brake=a_brake, dt=float(dt),
+                              h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), d_brake_first=N.ptr(brake_first), d_stop=N.ptr(stop),
+                              d_commit=N.ptr(commit), d_first=N.ptr(first))
+    self.ctx.call("fo_scene_hidden_brake_users", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_classes -- the clearances' maps too: the caller may drop the result)
+    self._hbu_inputs = (tv, arc, tuple(clearances))
+    return HiddenBrakeUsers(tuple(clearances), users, map_of, thr, brake_first, stop, commit, first, arc, a_brake, float(dt), tlen)

@@ -433,6 +433,25 @@ class FOInterface:
                                                       a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate, metric=metric,
                                                       flow=flow)
 
+    def hidden_brake_users(self, trajectories, users, a_brake=None, margin=None, inflate=0.0):
+        """EXTENSION, not part of the reference: the fail-safe question of :meth:`hidden_brake_classes` for hidden road users that do
+        not share a forecast -- ``users`` is 1 .. 8 triples ``(speed, metric, flow)``, say ``(2.0, "road", "any")`` for a pedestrian
+        and ``(7.0, "road", "lanes")``, ``(13.9, "road", "lanes")`` for a cyclist and a car -- from one clearance per distinct
+        ``(metric, flow)`` and ONE walk of every braking manoeuvre (:meth:`SensorModel.hidden_brake_users`; returns its
+        :class:`~frenetix_occlusion.sensor_model.HiddenBrakeUsers`: ``commit [C, M]``, ``first [C, M]``, ``brake_first [C, M, T]``,
+        ``stop [M, T]``, row c as ``hidden_brake(v_max=speed_c, metric=metric_c, flow=flow_c)`` gives them; ``.critical_user()`` the
+        slowest user a candidate is not fail-safe against).  Defaults as for :meth:`hidden_brake_classes`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_users needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        return self.sensor_model.hidden_brake_users(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], users=users,
+                                                    margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                    a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate)
+
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
         metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of

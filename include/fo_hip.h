@@ -641,6 +641,67 @@ typedef struct {
 } fo_hidden_brake_classes_t;
 int fo_scene_hidden_brake_classes(fo_ctx *ctx, const fo_hidden_brake_classes_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic BRAKE CLEARANCE BY ROAD USERS (DESIGN.md §5.10 "Brake clearance by road
+ * users") -- the brake clearance by classes for hidden road users that do not share a forecast: a pedestrian anywhere on the road, a
+ * cyclist and a car along the lanes.  Every class names one of up to FO_HIDDEN_BRAKE_MAX_MAPS key maps; every manoeuvre is walked
+ * ONCE and each braking pose's footprint is traversed once for all maps.  Opt-in and additive: one launch, nothing is read back, no
+ * other output changes.
+ *  Inputs: those of K clearance calls of this step over the same trajectories, headings, d_len_or_null, hl, hw, wb and window,
+ *   1 <= K <= FO_HIDDEN_BRAKE_MAX_MAPS; per map k: d_key[k] [win_ny][win_nx], d_qmin[k] [M][T] and r2_cap[k], of
+ *   fo_scene_hidden_clearance or fo_scene_hidden_clearance_flow, any metric; d_v, d_arc [M][T], a_brake >= 0 and dt > 0 as in
+ *   fo_scene_hidden_brake_classes; C classes, 1 <= C <= FO_HIDDEN_BRAKE_MAX_CLASSES, C * T <= FO_HIDDEN_BRAKE_MAX_TABLE, T <= 254;
+ *   map_of[c] in [0, K) per class; the host table h_thr [C][T] int32, every row non-decreasing with 0 <= thr[c][j] and
+ *   thr[c][T-1] <= 169 * r2_cap[map_of[c]].  A map that no class names is allowed (it is not read); two maps
+ *   may be the same buffer (the maps are only read, none of the outputs may overlap them).  Entries of d_key, d_qmin and
+ *   r2_cap beyond K and of map_of beyond C are not looked at.  Lm = T clipped by len[m].
+ *  For trajectory m, brake start b in 0 .. T-1 and class c with k = map_of[c]:
+ *  1. Steps 1 - 3 of fo_scene_hidden_brake word for word: stop[m][b], the speed profile vn, the re-sampled poses (xn, yn) and the
+ *   heading rule.  They depend on neither the class nor the map.
+ *  2. q_k(i) = the minimum of key_k over the footprint cells of the braking pose i, with the scan, the clipping and the rule outside
+ *   the window of fo_scene_hidden_clearance (key 0 on raster road, FO_HIDDEN_CLEARANCE_NONE elsewhere -- the same for every map); NONE
+ *   for an empty footprint.
+ *  3. hit_c(i) iff q_k(i) <= thr[c][i].
+ *  4. brake_first[c][m][b] = min { i in (b, Lm) : hit_c(i) }, -1 = none (and for b >= Lm, where stop[m][b] = -1).
+ *  5. first[c][m] = min { j < Lm : qmin_k[m][j] <= thr[c][j] }, -1 = none.
+ *  6. commit[c][m] = the smallest b in [0, Lm) with 0 <= first[c][m] <= b or 0 <= brake_first[c][m][b] < stop[m][b], -1 = none.
+ *  Outputs, every byte written by every call, int32: d_brake_first [C][M][T], d_stop [M][T], d_commit [C][M], d_first [C][M].
+ *  The tie: row c of every output equals, bit for bit, what fo_scene_hidden_brake_classes gives on (key_k, qmin_k, r2_cap_k) with
+ *   the single threshold row thr[c] -- and through that entry's tie fo_scene_hidden_brake on the forecast of that class's speed,
+ *   metric and flow.  With K = 1 the whole result is fo_scene_hidden_brake_classes' on the same inputs.
+ *  Safety of the data: as fo_scene_hidden_brake_classes; the keys, qmin, the table and map_of may hold anything the refusals let
+ *   through, no index depends on them.
+ *  Not claimed: what fo_scene_hidden_brake_classes does not claim; that the K maps belong to the same step, trajectories and window
+ *   is the caller's word.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_brake_users:"): K outside
+ * [1, 3]; C outside [1, 8]; no h_thr; a window outside [1, 32768]^2; an r2_cap[k], k < K, negative or beyond
+ * FO_HIDDEN_REACH_MAX_HALO; map_of[c], c < C, outside [0, K); M < 0; a_brake negative or not finite; dt not positive and finite; with
+ * M > 0: T outside [1, 254]; C * T > FO_HIDDEN_BRAKE_MAX_TABLE; a row that is negative, decreases or ends beyond
+ * 169 * r2_cap[map_of[c]]; no d_x / d_y / d_heading; no d_key[k] or d_qmin[k], k < K; no d_v or d_arc; a missing output; extents
+ * refused as by fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+#define FO_HIDDEN_BRAKE_MAX_MAPS 3
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  double a_brake, dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  int32_t *d_brake_first;                   /* [C][M][T] */
+  int32_t *d_stop;                          /* [M][T] */
+  int32_t *d_commit, *d_first;              /* [C][M] */
+} fo_hidden_brake_users_t;
+int fo_scene_hidden_brake_users(fo_ctx *ctx, const fo_hidden_brake_users_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

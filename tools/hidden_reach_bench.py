@@ -4,7 +4,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
-                                       [--brake-classes v1,v2,...]
+                                       [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -24,6 +24,12 @@ outputs: up to the first hit, one scan for a standing ego), the longest manoeuvr
 ``hidden_brake`` call per speed in the same process; every class's rows are compared with that call's (exact integers); also the
 poses the walk scanned (per manoeuvre the longest of its classes' walks), the poses the per-class walks scan together and the
 longest walk.
+
+``--brake-users v:metric:flow,...`` (say ``2:road:any,7:road:lanes,13.9:road:lanes``): ``hidden_brake_users`` for these hidden road
+users at the deceleration of ``--brake`` (§5.10 "Brake clearance by road users") -- one clearance per distinct forecast plus ONE walk
+-- next to one ``hidden_brake_classes`` call per forecast in the same process, with and without the headings handed over; in every
+run every user's rows are compared with its forecast's own call (exact integers); also the poses the one walk scanned and the poses
+the per-forecast walks scan.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -73,6 +79,8 @@ def main():
                     help="time hidden_brake at A m/s^2 (default: the vehicle's a_max) next to hidden_reach")
     ap.add_argument("--brake-classes", default=None, metavar="V1,V2,...",
                     help="time hidden_brake_classes for these hidden-user speeds (m/s) next to one hidden_brake call per speed")
+    ap.add_argument("--brake-users", default=None, metavar="V:METRIC:FLOW,...",
+                    help="time hidden_brake_users for these hidden road users next to one hidden_brake_classes call per forecast")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -168,6 +176,45 @@ def main():
         res["commit_never_per_class"] = [int(v) for v in (c_out.commit < 0).sum(dim=1).cpu()]
         vc = c_out.critical_speed()
         res["candidates_by_critical_speed"] = {str(v): int((vc == v).sum()) for v in sorted(set(cls_speeds))}
+    if a.brake_users:
+        users = tuple((float(s), m, f) for s, m, f in (u.split(":") for u in a.brake_users.split(",")))
+        a_brake = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbu = lambda **kw: sm.hidden_brake_users(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake, **kw)
+        u_out = hbu()
+        groups = [[c for c in range(len(users)) if u_out.map_of[c] == k] for k in range(len(u_out.clearances))]
+
+        def per_map(heading=None):      # what the call replaces: one hidden_brake_classes call per forecast, the headings handed over
+            outs = []
+            for k, members in enumerate(groups):
+                _, m, f = users[members[0]]
+                outs.append(sm.hidden_brake_classes(tx, ty, tth, tv, vehicle=veh, speeds=tuple(users[c][0] for c in members), dt=0.1,
+                                                    a_brake=a_brake, metric=m, flow=f, heading=heading))
+                heading = outs[-1].clearance.heading
+            return outs
+
+        parts = per_map()
+        for members, part in zip(groups, parts):    # the tie, in every run: every user's rows are its forecast's own classes call's
+            for n, c in enumerate(members):
+                assert torch.equal(u_out.brake_first[c], part.brake_first[n]) and torch.equal(u_out.commit[c], part.commit[n]), users[c]
+                assert torch.equal(u_out.first[c], part.first[n]) and torch.equal(u_out.stop, part.stop), users[c]
+        res["brake_users"] = [list(u) for u in users]
+        res["brake_users_maps"] = [list(m) for m in dict.fromkeys((m, f) for _, m, f in users)]
+        res["brake_users_call_ms"] = _median_ms(hbu, a.calls)
+        res["brake_users_call_reused_heading_ms"] = _median_ms(lambda: hbu(heading=u_out.clearances[0].heading), a.calls)
+        res["brake_classes_call_per_map_ms"] = _median_ms(per_map, a.calls)
+        res["brake_classes_call_per_map_reused_heading_ms"] = _median_ms(lambda: per_map(u_out.clearances[0].heading), a.calls)
+        bf, st = u_out.brake_first.cpu().numpy().astype(np.int64), u_out.stop.cpu().numpy().astype(np.int64)
+        b = np.arange(T)[None, :]
+        i0 = np.maximum(st, b + 1)                  # the sample at which the standing pose is first taken
+        moving = np.minimum(i0, T) - (b + 1)        # poses before it
+        per_user = np.where((bf >= 0) & (bf < i0[None]), bf - b[None], (moving + (i0 < T))[None])        # [C, M, T]
+        res["users_walk_poses_scanned"] = int(per_user.max(axis=0).sum())
+        res["per_map_walk_poses_scanned"] = [int(per_user[members].max(axis=0).sum()) for members in groups]
+        res["longest_users_walk"] = int(per_user.max(initial=0))
+        res["commit_never_per_user"] = [int(v) for v in (u_out.commit < 0).sum(dim=1).cpu()]
+        cu = u_out.critical_user()
+        res["candidates_by_critical_user"] = {str(c): int((cu == c).sum()) for c in range(-1, len(users))}
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
