@@ -15,7 +15,7 @@ constexpr int NAC = 16;    // per-agent constants (fo_agent_row below)
 struct fo_agent_table_t {
   double *tab = nullptr, *cst = nullptr;   // [A][Ta][NAF], [A][NAC]
   int32_t *aint = nullptr;                 // [A][2]
-  int *status = nullptr;                   // [2] generation tags (unusable covariance, correlated covariance)
+  int *status = nullptr;                   // [3] generation tags (unusable covariance, correlated covariance, refused rule list)
   int gen = 0;
   double ego_mass = 0, hlA = 0, hwA = 0;
   fo_harm_coeff_t hc{};
@@ -147,6 +147,9 @@ __device__ __forceinline__ void fo_agent_row(int i, int Ta, const double *__rest
   // valid length clamped to the table: the sweep indexes rows with min(t, L-1) and assumes L <= Ta; a longer claim
   // would read the next agent's rows
   const int L = min(max(len[k], 0), Ta);
+  // FO_LEN_REFUSED is how fo_scene_spawn_rule_agents marks the first slot of a REFUSED rule list (fo_hip.h): no live
+  // samples like any negative length, and the set delivers no verdict -- status[2], read by fo_reduce_kernel
+  if (t == 0 && len[k] == FO_LEN_REFUSED) atomicMax(status + 2, gen);
   fo_agent_sample_t q;
   q.px = pos[2 * (size_t)i]; q.py = pos[2 * (size_t)i + 1];
   q.ppx = t >= 1 ? pos[2 * (size_t)i - 2] : 0.0; q.ppy = t >= 1 ? pos[2 * (size_t)i - 1] : 0.0;

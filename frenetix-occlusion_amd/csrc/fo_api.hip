@@ -5,6 +5,7 @@
 #include "fo_ctx.hpp"
 #include "fo_agent_rows.hpp"
 #include "fo_prep_traj.hpp"
+#include "fo_rule_plan.hpp"
 
 extern "C" void fo_scene_destroy_(fo_ctx *ctx);  // fo_scene.hip
 extern "C" void *fo_step_direct_mirror_(fo_ctx *ctx, const fo_step_t *p);   // fo_scene.hip
@@ -43,8 +44,8 @@ int fo_create(fo_ctx **out, int device) {
   fo_ctx *ctx = new (std::nothrow) fo_ctx();
   if (!ctx) return FO_E_NOMEM;
   ctx->device = device;
-  if (hipMalloc((void **)&ctx->d_status, 2 * sizeof(int)) != hipSuccess) { delete ctx; return FO_E_NOMEM; }
-  if (hipMemset(ctx->d_status, 0, 2 * sizeof(int)) != hipSuccess) { (void)hipFree(ctx->d_status); delete ctx; return FO_E_HIP; }
+  if (hipMalloc((void **)&ctx->d_status, fo_ctx::kStatusWords * sizeof(int)) != hipSuccess) { delete ctx; return FO_E_NOMEM; }
+  if (hipMemset(ctx->d_status, 0, fo_ctx::kStatusWords * sizeof(int)) != hipSuccess) { (void)hipFree(ctx->d_status); delete ctx; return FO_E_HIP; }
   if (fo_sweep_init_(ctx) != FO_OK) { fo_destroy(ctx); return FO_E_HIP; }
   *out = ctx;
   return FO_OK;
@@ -86,12 +87,17 @@ int fo_sweep_check(fo_ctx *ctx, void *stream) {
   if (!ctx) return FO_E_ARG;
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   FO_HIP_TRY(ctx, hipStreamSynchronize((hipStream_t)stream));
-  int st = 0;
-  FO_HIP_TRY(ctx, hipMemcpy(&st, ctx->d_status, sizeof(int), hipMemcpyDeviceToHost));
-  if (st != 0 && st == ctx->status_gen)  // recorded by the latest fo_sweep_set_agents
+  int st[fo_ctx::kStatusWords] = {};
+  FO_HIP_TRY(ctx, hipMemcpy(st, ctx->d_status, sizeof(st), hipMemcpyDeviceToHost));
+  if (st[0] != 0 && st[0] == ctx->status_gen)  // recorded by the latest fo_sweep_set_agents
     return fo_fail(ctx, FO_E_UNSUPPORTED_COV,
                    "an agent's covariance is no usable matrix (asymmetric, not positive, or |correlation| > 0.99): "
                    "the affected collision probabilities are NaN");
+  if (st[2] != 0 && st[2] == ctx->status_gen)  // the rule agents' first slot said so (fo_spawn_rule_predict_kernel, fo_agent_row)
+    return fo_fail(ctx, FO_E_STATE,
+                   "the spawn rule tables ran out of space at this step (a rule line of more than %d samples, or an obstacle's "
+                   "centre on too many lanelets): the rule list was refused, the agent set is short of it -- every cost is NaN, "
+                   "no trajectory is safe", RL_MAXSAMP);
   return FO_OK;
 }
 

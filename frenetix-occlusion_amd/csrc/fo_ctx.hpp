@@ -29,9 +29,10 @@ struct fo_ctx {
   void *d_gl_tab = nullptr;         // Gauss-Legendre nodes / weights (box probabilities under correlated covariances)
   int32_t *d_agent_int = nullptr;   // [A][2] protection class, valid length
   size_t cap_agent_int = 0;
-  int *d_status = nullptr;          // [2] device status words: generation of the last fo_sweep_set_agents call that met
-                                    // [0] an unusable covariance, [1] a correlated one (compared with status_gen;
-                                    // never cleared, so no per-step memset)
+  static constexpr int kStatusWords = 3;
+  int *d_status = nullptr;          // [3] device status words: generation of the last agent set that met
+                                    // [0] an unusable covariance, [1] a correlated one, [2] a refused rule list (compared
+                                    // with status_gen; never cleared, so no per-step memset)
   int status_gen = 0;
   size_t cap_agent_tab = 0, cap_agent_const = 0;
 

@@ -179,14 +179,11 @@ __global__ void fo_spawn_rules_select_kernel(RuleView v, RuleParams pr, int O, c
   // instead of in HBM -- the rules step does not move, same box, two passes: 0.0845 / 0.0831 against 0.0830 / 0.0850 ms)
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   // a rule that ran out of table space left -1 in its validity word: the step's list would be short of a point the reference
-  // finds, so there is NO list -- the count says -1 and the callers refuse it (fo_hip.h)
-  bool over = pr.behind_turn && pr.intention != 0 && recs[0] < 0.0;
-  for (int o = 0; o < O; ++o) {   // (no short cuts: the loads of all records go out together)
-    const double *r = recs + (size_t)(1 + o) * RL_REC;
-    const double role = r[1], v0 = r[2], v1 = r[8];
-    over = over | ((role == 2.0) & (v0 < 0.0)) | ((role == 1.0) & ((v0 < 0.0) | (v1 < 0.0)));
-  }
-  if (over) { *n_out = -1; return; }
+  // finds, so there is NO list -- the count says -1, and a sweep over the step's agents delivers no verdict (fo_hip.h).  Only
+  // a record the selection below CONSUMES can refuse the step: the turn record with the turn rule on, an obstacle the
+  // distance-ordered loops visit before their maxima break.  The reference's list does not depend on the obstacles behind
+  // the break, so neither does the refusal.
+  bool over = false;
   int n = 0;
   auto put = [&](double type, double x, double y, double yaw, double s, double d, double src, double ob) {
     if (n < max_out) {
@@ -216,6 +213,7 @@ __global__ void fo_spawn_rules_select_kernel(RuleView v, RuleParams pr, int O, c
       const double *r = recs + (size_t)(1 + o) * RL_REC;
       last_d = r[0]; last_o = o;
       if (n_dyn > pr.max_dynamic) break;                                           // :212
+      if (r[2] < 0.0) { over = true; continue; }
       if (r[2] != 0.0) { put(RL_TYPE_CAR, r[3], r[4], NAN, NAN, NAN, RL_SRC_DYNAMIC, o); ++n_dyn; }
       if (r[5] != 0.0) { put(RL_TYPE_BICYCLE, r[6], r[7], NAN, NAN, NAN, RL_SRC_DYNAMIC, o); ++n_dyn; }
     }
@@ -230,6 +228,7 @@ __global__ void fo_spawn_rules_select_kernel(RuleView v, RuleParams pr, int O, c
       const double *r = recs + (size_t)(1 + o) * RL_REC;
       last_d = r[0]; last_o = o;
       if (n_st > pr.max_static) break;                                             // :365
+      if (r[2] < 0.0 || r[8] < 0.0) { over = true; continue; }                     // (both cross lines of a visited obstacle count)
       for (int li = 0; li < 2; ++li) {
         const double *q = r + 2 + 6 * li;
         if (q[0] == 0.0) continue;
@@ -245,7 +244,8 @@ __global__ void fo_spawn_rules_select_kernel(RuleView v, RuleParams pr, int O, c
   }
   if (pr.behind_turn && pr.intention != 0) {
     const double *r = recs;
-    if (r[0] != 0.0) {
+    if (r[0] < 0.0) over = true;
+    else if (r[0] != 0.0) {
       bool ok = true;
       for (int o = 0; o < O && ok; ++o)                                            // :557: no visible obstacle within the 0.5 m disc
         if ((oflags[o] & 1) && ovis[o] && rl_seg_rect_distance(r[1], r[2], r[1], r[2], ocorn + 8 * (size_t)o) <= 0.5) ok = false;
@@ -258,7 +258,7 @@ __global__ void fo_spawn_rules_select_kernel(RuleView v, RuleParams pr, int O, c
       if (ok) put(RL_TYPE_PED, r[1], r[2], NAN, r[3], r[4], r[5], -1.0);
     }
   }
-  *n_out = n < max_out ? n : max_out;
+  *n_out = over ? -1 : n < max_out ? n : max_out;
 }
 
 
@@ -275,7 +275,8 @@ __global__ __launch_bounds__(64) void fo_spawn_rule_predict_kernel(
     double *__restrict__ yaw0, PredOut o, int table_on, fo_agent_table_t at) {
   const int lane = threadIdx.x;
   const int i = blockIdx.x / R, r = blockIdx.x % R, slot = slot0 + blockIdx.x;
-  const int n = min(max(*n_points, 0), max_points);
+  const int n_raw = *n_points;
+  const int n = min(max(n_raw, 0), max_points);
   const double vpow = pow(factor, (double)lane);   // (spawn_write_slot; here: under the first round trip)
   const bool on = i < n;
   const double *rec = points + 8 * (size_t)i;
@@ -308,6 +309,15 @@ __global__ __launch_bounds__(64) void fo_spawn_rule_predict_kernel(
   if (r == 0 && lane == 0) { pos0[2 * (agent0 + i)] = px; pos0[2 * (agent0 + i) + 1] = py; yaw0[agent0 + i] = a0; }
   spawn_write_slot(lane, slot, r, on, px, py, a0, type, ty.speed[ti], ty.raw_l[ti], ty.raw_w[ti], ty.infl_l[ti], ty.infl_w[ti], ll, rv, T,
                    dt, var0, factor, o, table_on, at, vpow, -1.0);
+  // A refused list (the selection kernel's -1) adds no rule agents -- and must not read as "nothing hidden there": the first
+  // rule slot's length says so to whoever takes the arrays (fo_prep_agents_kernel raises the status word for it, the host
+  // views read it as 0 live samples), and where this kernel writes the sweep's table itself it raises the word here.
+  // fo_reduce_kernel turns the word into NaN costs and safe = 0 (fo_hip.h, fo_sweep_check).  After spawn_write_slot: the
+  // same lane's later store to the same word.
+  if (n_raw < 0 && blockIdx.x == 0 && lane == 0) {
+    o.len[slot] = FO_LEN_REFUSED;
+    if (table_on) atomicMax(at.status + 2, at.gen);
+  }
 }
 
 }  // namespace

@@ -21,6 +21,7 @@
 #include "fo_agent_rows.hpp"
 #include "fo_prep_traj.hpp"
 #include "fo_sweep_plan.hpp"
+#include "fo_verdict.hpp"
 #include "fo_sweep_common.hpp"
 #include "fo_sweep_generic.hpp"
 #include "fo_sweep_queue.hpp"
@@ -155,7 +156,7 @@ int fo_sweep_agents_begin_(fo_ctx *ctx, int A, int Ta, void *stream, fo_agent_ta
   ctx->A = A;
   ctx->Ta = Ta;
   if (ctx->status_gen >= (1 << 30)) {  // generations never run out in practice; start over cleanly if they do
-    FO_HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0, 2 * sizeof(int), s));
+    FO_HIP_TRY(ctx, hipMemsetAsync(ctx->d_status, 0, fo_ctx::kStatusWords * sizeof(int), s));
     FO_HIP_TRY(ctx, hipMemsetAsync(ctx->d_agent_const, 0, ctx->cap_agent_const * sizeof(double), s));   // (the tagged slots as well)
     ctx->status_gen = 0;
   }

@@ -161,27 +161,16 @@ __global__ __launch_bounds__(64 * RED_WAVES) void fo_reduce_kernel(int M, int Mp
     flag = fmax(flag, p[PS_DCE_FLAG * 64]);
     max_btn = fmax(max_btn, p[NPS * 64]);
   }
-  bool ok = true;
-  if (A > 0) {  // no agents -> ({}, True)  (metric.py:44-45)
-    if ((mask & FO_M_HR) && max_hwc > thr.harm) ok = false;  // NaN thresholds compare false = disabled
-    if ((mask & FO_M_HR) && max_or > thr.risk) ok = false;
-    if ((mask & FO_M_HR) && max_cp > thr.cp) ok = false;
-    if ((mask & FO_M_TTC) && min_ttc < thr.ttc) ok = false;
-    if ((mask & FO_M_DCE) && flag > 0.0) ok = false;
-    if ((mask & FO_M_BE) && max_btn > thr.be) ok = false;  // metric.py:54-61
-    // The current agent set holds an off-diagonal covariance (fo_prep_agents_kernel poisoned those rows and tagged
-    // the status word with this generation): fmax() above drops the NaNs, so say it here -- nothing that depends
-    // on a collision probability may read as "safe", whether or not the caller runs fo_sweep_check.
-    if ((mask & (FO_M_CP | FO_M_HR)) && gen > 0 && *status == gen) {
-      ok = false;
-      max_cp = max_er = max_or = max_hwc = NAN;
-    }
-  }
+  // the status words of this agent set (fo_ctx.hpp; wave-uniform addresses: scalar loads, once per workgroup): [0] an unusable
+  // covariance, [2] a refused rule list -- what they take away from the row: fo_verdict.hpp
+  const bool cov_unusable = gen > 0 && status[0] == gen, refused = gen > 0 && status[2] == gen;
+  fo_folded_t f{min_ttc, min_dce, max_er, max_or, max_eh, max_oh, max_cp, max_hwc, min_ttce, arg_dce, arg_ttc, arg_or, max_btn, flag};
+  const bool ok = fo_verdict(A, mask, thr, cov_unusable, refused, f);
   double *c = cost + (size_t)m * FO_NC;
-  c[FO_C_WTTC] = min_ttc; c[FO_C_MIN_DCE] = min_dce; c[FO_C_MAX_EGO_RISK] = max_er; c[FO_C_MAX_OBST_RISK] = max_or;
-  c[FO_C_MAX_EGO_HARM] = max_eh; c[FO_C_MAX_OBST_HARM] = max_oh; c[FO_C_MAX_CP] = max_cp;
-  c[FO_C_HARM_WITH_CP] = max_hwc; c[FO_C_MIN_TTCE] = min_ttce; c[FO_C_ARGMIN_DCE] = arg_dce;
-  c[FO_C_ARGMIN_TTC] = arg_ttc; c[FO_C_ARGMAX_RISK] = arg_or; c[FO_C_SAFE] = ok ? 1.0 : 0.0; c[FO_C_MAX_BTN] = max_btn;
+  c[FO_C_WTTC] = f.min_ttc; c[FO_C_MIN_DCE] = f.min_dce; c[FO_C_MAX_EGO_RISK] = f.max_er; c[FO_C_MAX_OBST_RISK] = f.max_or;
+  c[FO_C_MAX_EGO_HARM] = f.max_eh; c[FO_C_MAX_OBST_HARM] = f.max_oh; c[FO_C_MAX_CP] = f.max_cp;
+  c[FO_C_HARM_WITH_CP] = f.max_hwc; c[FO_C_MIN_TTCE] = f.min_ttce; c[FO_C_ARGMIN_DCE] = f.arg_dce;
+  c[FO_C_ARGMIN_TTC] = f.arg_ttc; c[FO_C_ARGMAX_RISK] = f.arg_or; c[FO_C_SAFE] = ok ? 1.0 : 0.0; c[FO_C_MAX_BTN] = f.max_btn;
   c[FO_C_RES0] = 0.0; c[FO_C_RES1] = 0.0;
   safe[m] = ok ? 1 : 0;
 }

@@ -243,7 +243,7 @@ struct SweepArgs {
   const double2 *erf_tab;  // [ERF_N]
   const double *exp_tab;   // [EXP_N]  2^(j/EXP_N)
   const double *gl;        // [GL_TOTAL][2] Gauss-Legendre nodes and weights (correlated covariances)
-  const int *status;       // [2] generation tags of fo_prep_agents_kernel: [0] unusable covariance, [1] correlated one
+  const int *status;       // [3] generation tags of fo_prep_agents_kernel: [0] unusable covariance, [1] correlated one, [2] refused rule list
   int gen;                 // generation of the current agent set
   const int32_t *aint;     // [A][2] protection class, valid length
   double *partial;       // [n_chunks][NPS][Mp]

@@ -25,6 +25,22 @@ METRIC_BITS = {"dce": 1, "cp": 2, "ttc": 4, "ttce": 8, "wttc": 16, "be": 32, "hr
 TYPE_CODES = {"car": 0, "truck": 1, "bus": 2, "bicycle": 3, "pedestrian": 4, "priorityvehicle": 5,
               "parkedvehicle": 6, "train": 7, "motorcycle": 8, "taxi": 9, "unknown": 10}
 
+LEN_REFUSED = -2**31     # FO_LEN_REFUSED (INT32_MIN): the length in the first rule slot of a refused rule list (include/fo_hip.h)
+
+
+def _header_constant(header, name):
+    """an integer ``constexpr int NAME = value;`` of a csrc header the library is built from: the one place the number is
+    written down (the package carries its sources next to the library, __graft_entry__.build compiles them)"""
+    import re
+    with open(os.path.join(os.path.dirname(_HERE), "csrc", header)) as f:
+        m = re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, f.read())
+    if not m:
+        raise ImportError(f"{header}: no integer constant {name}")
+    return int(m.group(1))
+
+
+RULE_MAX_SAMPLES = _header_constant("fo_rule_plan.hpp", "RL_MAXSAMP")   # samples of a rule line (one every cell / 8) the device holds
+
 # every symbol include/fo_hip.h declares (tests check the library exports all of them)
 EXPORTS = [
     "fo_abi_version", "fo_build_id", "fo_create", "fo_destroy", "fo_last_error",

@@ -118,7 +118,9 @@ class ShardedAssessment:
 
 def select_trajectory(cost: torch.Tensor, key: str = "max_obst_risk_all") -> int:
     """index of the trajectory the planner would take: the safe one with the smallest `key` (ties: lowest index);
-    if none is safe, the one with the smallest `max_obst_harm_with_cp_all` (emergency fallback).  -1 for M = 0."""
+    if none is safe, the one with the smallest `max_obst_harm_with_cp_all` (emergency fallback).  -1 for M = 0.
+    RuntimeError when no row is safe and the fallback column holds no number at all: the cost rows of a step whose rule
+    list was refused (include/fo_hip.h, "A refused rule list") -- there is nothing to choose by."""
     if cost.shape[0] == 0:
         return -1
     safe = cost[:, N.COST["safe"]] > 0.5
@@ -126,4 +128,7 @@ def select_trajectory(cost: torch.Tensor, key: str = "max_obst_risk_all") -> int
         v = torch.where(safe, cost[:, N.COST[key]], torch.full_like(cost[:, 0], float("inf")))
     else:
         v = cost[:, N.COST["max_obst_harm_with_cp_all"]]
+        if bool(torch.isnan(v).all()):
+            raise RuntimeError("select_trajectory: no trajectory is safe and every fallback cost is NaN -- the sweep delivered no "
+                               "verdict for this step (a refused spawn rule list, or unusable covariances)")
     return int(torch.argmin(v).item())

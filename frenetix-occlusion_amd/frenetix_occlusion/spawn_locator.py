@@ -25,7 +25,8 @@ from .utils.curvilinear import pathlength
 MIN_AHEAD = 3.0            # spawn_locator.py:234,381 "ahead by >= 3 m"
 S_THRESHOLD_TIME = 4.0     # spawn_locator.py:65-66,113: s_threshold = s_ego + max(4 v, 25)
 S_THRESHOLD_MIN = 25.0
-RULE_MAX_SAMPLES = 1024    # samples of a rule line the device holds (csrc/fo_rule_plan.hpp: RL_MAXSAMP)
+RULE_MAX_SAMPLES = N.RULE_MAX_SAMPLES    # samples of a rule line the device holds (read from csrc/fo_rule_plan.hpp: RL_MAXSAMP)
+TURN_WINDOW = 40.0         # metres of reference path the turn rule samples (spawn_locator.py:678-693)
 
 TYPE_NAME = {0: "Car", 1: "Truck", 3: "Bicycle", 4: "Pedestrian"}
 TYPE_CODE = {"car": 0, "truck": 1, "bicycle": 3, "pedestrian": 4}
@@ -48,9 +49,43 @@ def rule_point_capacity(max_dynamic: int, max_static: int) -> int:
     return max_dynamic + max_static + 4
 
 
+def rule_line_samples(total: float, cell_size: float) -> int:
+    """samples the device takes of a rule line of ``total`` metres (csrc/fo_rule_pedestrian.hpp: one every cell / 8, half a step
+    beyond the end): a line of more than ``RULE_MAX_SAMPLES`` refuses the step"""
+    step = cell_size / 8.0
+    return int(math.ceil((total + 0.5 * step) / step))
+
+
 def turn_line_outgrows_table(cell_size: float) -> bool:
     """The turn rule samples its 40 m reference window every cell / 8 (+ the two ends): more samples than the device holds?"""
-    return 40.0 / (cell_size / 8.0) + 2.0 > RULE_MAX_SAMPLES
+    return TURN_WINDOW / (cell_size / 8.0) + 2.0 > RULE_MAX_SAMPLES
+
+
+def turn_line_min_cell() -> float:
+    """the cell size below which :func:`turn_line_outgrows_table` says yes (its own inequality solved for the cell size)"""
+    return 8.0 * TURN_WINDOW / (RULE_MAX_SAMPLES - 2.0)
+
+
+def cross_line_limit(cell_size: float) -> float:
+    """metres of an obstacle's cross line (its extent across the path + 1.6 m) the static rule's sample table holds"""
+    return RULE_MAX_SAMPLES * cell_size / 8.0
+
+
+def rule_table_warning(cell_size: float, behind_turn: bool, behind_static: bool):
+    """the set-up warning about the rule families' sample table, or None: every number in it comes from ``RULE_MAX_SAMPLES``
+    and from the check that raises it"""
+    if not ((behind_turn or behind_static) and turn_line_outgrows_table(cell_size)):
+        return None
+    parts = []
+    if behind_turn:
+        parts.append(f"the turn rule samples the {TURN_WINDOW:g} m reference window (needs cells >= {turn_line_min_cell():.4f} m): at a "
+                     "turn the step's rule list is refused")
+    if behind_static:
+        parts.append(f"the static-obstacle rule samples an obstacle's cross line and refuses the step for one longer than "
+                     f"{cross_line_limit(cell_size):g} m")
+    return (f"SpawnLocator: cells of {cell_size} m -- the spawn rules sample their lines every cell / 8 and hold {RULE_MAX_SAMPLES} "
+            "samples; " + "; ".join(parts) + ".  A refused step has no spawn-point list (RuntimeError when it is read) and its sweep "
+            "delivers NaN costs and no safe trajectory.  Use larger cells or switch the rule off.")
 
 
 def intention_from_curvature(k) -> int:
@@ -175,7 +210,9 @@ class PhantomBatch:
                 n = int(np.prod(shp)) * 8
                 out[name] = h[o:o + n].view(np.float64).reshape(shp)
                 o += n
-            out["len"] = h[o:o + 4 * S_].view(np.int32)
+            # (a refused rule list marks its first slot with the length FO_LEN_REFUSED for the sweep, include/fo_hip.h --
+            # to every reader here that is what it is to the kernels, no live sample)
+            out["len"] = np.maximum(h[o:o + 4 * S_].view(np.int32), 0)
             self._host_body = out
         return self._host_body
 
@@ -191,7 +228,8 @@ class PhantomBatch:
             cnt = h[o3:o4].view(np.int32)
             if Rp and int(cnt[1]) < 0:
                 raise RuntimeError("fo_scene_spawn_rules: a rule family ran out of table space at this step (a sampled line of more "
-                                   "than 1 024 cells / 8: include/fo_hip.h) -- there is no spawn-point list; use cells of >= 0.32 m")
+                                   f"than {RULE_MAX_SAMPLES} cells / 8, or an obstacle's centre on too many lanelets: include/fo_hip.h) "
+                                   "-- there is no spawn-point list, and the step's costs are NaN")
             self._host = dict(n=int(cnt[0]) if self.n_cell_agents else 0, rule_n=min(int(cnt[1]), Rp) if Rp else 0,
                               pos0=h[:o1].view(np.float64).reshape(A, 2), yaw0=h[o1:o2].view(np.float64),
                               rule_points=h[o2:o3].view(np.float64).reshape(Rp, 8), type=h[o4:o4 + 4 * S_].view(np.int32))
@@ -460,14 +498,13 @@ class SpawnLocator:
                               max_static=int(sl.get("max_static_spawn_points", 1)),
                               max_dynamic=int(sl.get("max_dynamic_spawn_points", 1)),
                               ped_width=float(ped["width"]), ped_length=float(ped["length"]))
-        # the turn rule samples its 40 m window every cell / 8 and holds 1 024 samples (include/fo_hip.h: a longer line comes back
-        # as a refused point count, which only whoever READS the step's list gets to see): say so once, up front
+        # the rules sample their lines every cell / 8 into a table of RULE_MAX_SAMPLES (include/fo_hip.h: a longer line refuses the
+        # step -- no list, NaN costs): say so once, up front
         cs = float(getattr(sm, "cell_size", 0.5))
-        if self._rule_cfg["behind_turn"] and turn_line_outgrows_table(cs):
+        text = rule_table_warning(cs, bool(self._rule_cfg["behind_turn"]), bool(self._rule_cfg["behind_static"]))
+        if text:
             import warnings
-            warnings.warn(f"SpawnLocator: cells of {cs} m -- the turn rule of the spawn locator samples the 40 m reference window "
-                          "every cell / 8 and holds 1 024 samples (cells >= 0.32 m); at a turn the step's spawn-point list will be "
-                          "refused (RuntimeError when it is read).  Use larger cells or spawn_points_behind_turn: False.")
+            warnings.warn(text)
         self._rules_ready = True
 
     def _frame_setup(self):

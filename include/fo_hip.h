@@ -102,7 +102,12 @@ int fo_sweep_reserve(fo_ctx *ctx, int max_M, int max_T, int max_A, int max_Ta);
 enum { FO_LISTS_F64 = 0, FO_LISTS_F32 = 1, FO_LISTS_F32_EXACT = 2 };
 int fo_sweep_set_list_format(fo_ctx *ctx, int format);
 
-/* replaces: agent_manager.predictions (agent.py:179-183) as read by every metric */
+/* replaces: agent_manager.predictions (agent.py:179-183) as read by every metric.
+ * d_len [A]: valid samples of every prediction, clamped to [0, Ta] (a negative length is an unused slot, like 0).  ONE
+ * value, FO_LEN_REFUSED (INT32_MIN: what fo_scene_spawn_rule_agents leaves in the first rule slot of a refused rule list),
+ * counts as 0 live samples too AND marks the whole set as one that cannot be judged: see "A refused rule list" at
+ * fo_sweep_check. */
+#define FO_LEN_REFUSED (-2147483647 - 1)
 int fo_sweep_set_agents(fo_ctx *ctx, int A, int Ta, const double *d_pos, const double *d_yaw, const double *d_v,
                         const double *d_cov, const double *d_shape, const double *d_raw_dims, const int32_t *d_type,
                         const int32_t *d_len, void *stream);
@@ -131,7 +136,18 @@ int fo_sweep_autotune(fo_ctx *ctx, int M, int T, const double *d_x, const double
  * that is no usable covariance -- asymmetric, not positive, or |correlation| > 0.99 (those agents' collision
  * probabilities are NaN and no trajectory reads as safe) -- else FO_OK.  Diagonal covariances take the closed form,
  * symmetric ones with correlation are integrated numerically (the reference hands any matrix to scipy's mvnun,
- * collision_probability.py:117).  Not capturable in a hipGraph. */
+ * collision_probability.py:117).  Not capturable in a hipGraph.
+ *
+ * A refused rule list.  When the spawn rule families ran out of table space at a step (fo_scene_spawn_rules:
+ * *d_n_out = -1), the agent set of that step is short of road users the reference would have put there, and a sweep over
+ * it delivers NO usable verdict -- on the device, without any host read, whether or not anybody calls this function.
+ * For every trajectory m: safe[m] = 0, cost[m][FO_C_SAFE] = 0, every other float column of cost[m] is NaN, FO_C_RES0 and
+ * FO_C_RES1 keep their 0.  That holds in every output mode, for every metric mask (unlike the covariance poison it is not
+ * gated on CP / HR), for FO_SPAWN_RULES and FO_SPAWN_BOTH, in both forms of fo_step_run, and for the stage calls
+ * fo_scene_spawn_rule_agents -> fo_sweep_set_agents -> fo_sweep_run.  The pair and list buffers of such a step are
+ * UNSPECIFIED: do not read them.  fo_sweep_check then returns FO_E_STATE with a message that names the rule tables (an
+ * unusable covariance in the same set is reported first).  The mark carries the generation of its agent set: the next
+ * fo_sweep_set_agents / fo_step_run on the context starts clean. */
 int fo_sweep_check(fo_ctx *ctx, void *stream);
 
 /* HIP-event timing of the sweep kernel alone (events recorded on the launch stream around that one kernel):
@@ -773,8 +789,15 @@ typedef struct {
  * Table space: the turn rule holds a reference window of <= 1 536 path vertices, the dynamic-obstacle rule flags for <= 9 409
  * lanelets and every fifth of <= 2 560 window vertices, max_static <= 15 -- beyond: FO_E_ARG.  What only the device can tell: an
  * obstacle's centre on more than sixteen lanelets or on more than seven relevant ones, a line a rule samples (cell size / 8
- * apart: the 40 m window, an obstacle's cross line) of more than 1 024 samples -- then *d_n_out = -1 and there is no list
- * (fo_scene_spawn_rule_agents and fo_step_run add no rule agents; whoever reads the count must refuse it). */
+ * apart: the 40 m window, an obstacle's cross line: its extent across the path + 1.6 m) of more than 1 024 samples -- then
+ * *d_n_out = -1 and there is no list.  Only a record the selection consumes can refuse the step: the turn record with the
+ * turn rule on, an obstacle the distance-ordered selection visits before max_dynamic / max_static end it (the reference's
+ * list does not depend on the obstacles behind that point).
+ * What the library guarantees for a refused step: fo_scene_spawn_rule_agents and fo_step_run add no rule agents and mark
+ * the agent set, and every sweep over it fails closed -- NaN costs, safe = 0, FO_E_STATE from fo_sweep_check ("A refused
+ * rule list" at fo_sweep_check).  What is left to the caller: d_out and the pair / list buffers of such a step are
+ * unspecified, and a host that reads the spawn-point list itself must refuse a negative count (the Python host view
+ * raises RuntimeError). */
 int fo_scene_spawn_rules(fo_ctx *ctx, const uint8_t *d_cls, int win_ix0, int win_iy0, int win_nx, int win_ny, int n_path,
                          const double *d_path6, int O, const double *d_ocorn, const double *d_ocen, const double *d_oyaw,
                          const double *d_odims, const uint8_t *d_oflags, const uint8_t *d_obst_vis,
@@ -805,7 +828,10 @@ typedef struct { double speed[3], raw_l[3], raw_w[3], infl_l[3], infl_w[3]; } fo
  *     candidate route of that lanelet (the min-var(v) Frenet sample, see fo_scene_spawn), heading of record = first
  *     segment of route 0; off-lanelet or without a route table: heading towards d_path, one straight prediction.
  * d_pos0 [max_points][2] / d_yaw0 [max_points]: spawn position and initial heading per point (host views read them
- * lazily). */
+ * lazily).
+ * A refused list (*d_n_points < 0): every slot is inactive, and d_len[0] -- the first rule slot -- is FO_LEN_REFUSED instead
+ * of 0: fo_sweep_set_agents reads that as "this set cannot be judged" and the sweep fails closed ("A refused rule list" at
+ * fo_sweep_check); everybody else treats it as 0 live samples. */
 int fo_scene_spawn_rule_agents(fo_ctx *ctx, int max_points, const double *d_points, const int32_t *d_n_points, int routes,
                                const fo_rule_agent_types_t *types, int n_path, const double *d_path, int T, double dt,
                                double var0, double var_factor, double *d_pos0, double *d_yaw0, double *d_pos, double *d_yaw,
@@ -827,7 +853,10 @@ int fo_scene_spawn_rule_agents(fo_ctx *ctx, int max_points, const double *d_poin
  *      FO_STEP_STAGES=1 in the environment: the plain stage calls.
  *      With spawn_mode FO_SPAWN_RULES / FO_SPAWN_BOTH the rule families run between the visibility and the sweep:
  *      fo_scene_spawn_rules (two launches) and fo_scene_spawn_rule_agents (one, which also writes its slots' rows of the
- *      agent table) -- the reference's find_spawn_points -> add_agent flow (interface.py:186-198) without leaving HBM. */
+ *      agent table) -- the reference's find_spawn_points -> add_agent flow (interface.py:186-198) without leaving HBM.
+ *      A step whose rule list is refused (*d_n_rule_points = -1) still returns FO_OK -- nothing is read back -- and fails
+ *      closed on the device: d_cost is NaN, d_safe 0, in both forms, also with the cell sampler's agents in the set
+ *      (FO_SPAWN_BOTH); d_pair_f / d_pair_i / d_lists are unspecified ("A refused rule list" at fo_sweep_check). */
 typedef struct {
   /* fo_scene_fan */
   int32_t n_rays, polygon_footprint;

@@ -158,7 +158,10 @@ def test_table_space_of_the_rules_is_enough_or_refused(torch_cuda):
         warnings.simplefilter("always")
         with pytest.raises(RuntimeError, match="table space"):
             _both(torch_cuda, main + side, [], path, ego, 0.0, 6.0, cell_size=0.25)
-    assert any("0.32" in str(w.message) for w in rec)       # (and the locator said so when it was set up)
+    from frenetix_occlusion import spawn_locator as SL      # (and the locator said so when it was set up, in the check's own numbers)
+    said = [str(w.message) for w in rec if "SpawnLocator: cells of 0.25 m" in str(w.message)]
+    assert said and all(f"{SL.turn_line_min_cell():.4f} m" in t and f"{SL.cross_line_limit(0.25):g} m" in t for t in said)
+    assert all("turn rule" in t and "static-obstacle rule" in t for t in said)
 
 
 def test_car_and_bicycle_behind_an_oncoming_truck(torch_cuda):
