@@ -46,6 +46,7 @@
 //   fo_hidden_clearance.hpp  fo_hc_*_kernel  hidden-traffic clearance: the key map behind every reach table, its minimum per pose
 //   fo_hidden_brake_classes.hpp  fo_hr_brake_classes_kernel  brake clearance for several hidden-user speeds: one walk over the key map
 //   fo_hidden_brake_users.hpp  fo_hr_brake_users_kernel  ... for road users on different forecasts: one walk over up to three key maps
+//   fo_hidden_brake_ladder.hpp  fo_hr_brake_ladder_kernel  brake clearance at a ladder of decelerations: a lane per (m, b, level)
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -60,6 +61,7 @@
 #include "fo_hidden_clearance.hpp"
 #include "fo_hidden_brake_classes.hpp"
 #include "fo_hidden_brake_users.hpp"
+#include "fo_hidden_brake_ladder.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
 #include "fo_future_visibility.hpp"
@@ -960,6 +962,53 @@ int fo_scene_hidden_brake_users(fo_ctx *ctx, const fo_hidden_brake_users_t *p, v
   hipStream_t s = (hipStream_t)stream;
   if (brake_users_width(C) == 4) hbu_launch<4>(K, grid, block, lds, s, a, thr);
   else hbu_launch<8>(K, grid, block, lds, s, a, thr);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+// the brake clearance of every (trajectory, brake start < B) at every level of a ladder of decelerations, and the first clear level:
+// one launch over the arrival map of any forecast (fo_hidden_brake_ladder.hpp); the levels travel as a kernel argument
+int fo_scene_hidden_brake_ladder(fo_ctx *ctx, const fo_hidden_brake_ladder_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_brake_ladder";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  const fo_hidden_reach_t &b = p->base;
+  if ((rc = hr_check_table(ctx, b.J, b.h_r2, fn))) return rc;
+  if (!b.d_arrival)
+    return fo_fail(ctx, FO_E_ARG, "%s: the map of the forecast is required (base.d_arrival [win_ny][win_nx])", fn);
+  if ((rc = hr_check_extent(ctx, b.win_nx, b.win_ny, fn))) return rc;
+  if ((rc = hr_check_table_values(ctx, b.J, b.h_r2, fn))) return rc;
+  if (b.M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, b.M);
+  if (p->K < 1 || p->K > FO_HIDDEN_BRAKE_MAX_LEVELS)
+    return fo_fail(ctx, FO_E_ARG, "%s: K = %d outside [1, FO_HIDDEN_BRAKE_MAX_LEVELS = %d]", fn, p->K, FO_HIDDEN_BRAKE_MAX_LEVELS);
+  if (!p->h_levels) return fo_fail(ctx, FO_E_ARG, "%s: no decelerations h_levels [K]", fn);
+  for (int k = 0; k < p->K; ++k)
+    if (!(p->h_levels[k] >= 0.0) || !std::isfinite(p->h_levels[k]))      // (NaN fails every comparison)
+      return fo_fail(ctx, FO_E_ARG, "%s: h_levels[%d] = %g, a finite deceleration >= 0 is needed", fn, k, p->h_levels[k]);
+  if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return fo_fail(ctx, FO_E_ARG, "%s: dt = %g, a finite step > 0 is needed", fn, p->dt);
+  if (b.M > 0) {
+    if (b.T < 1 || b.T > b.J)
+      return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, J = %d] (every sample needs its reach)", fn, b.T, b.J);
+    if (p->B < 1 || p->B > b.T) return fo_fail(ctx, FO_E_ARG, "%s: B = %d outside [1, T = %d]", fn, p->B, b.T);
+    if (!b.d_x || !b.d_y || !b.d_heading || !b.d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T], d_heading [M][T][2] and d_first [M] of the forecast are required with M > 0", fn);
+    if (!p->d_v || !p->d_arc) return fo_fail(ctx, FO_E_ARG, "%s: d_v and d_arc [M][T] are required with M > 0", fn);
+    if (!p->d_brake_first || !p->d_stop || !p->d_required || !p->d_last_unclear || !p->d_commit)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_brake_first, d_stop [M][B][K], d_required, d_last_unclear [M][B] and d_commit [M][K] are required "
+                     "with M > 0", fn);
+    if ((rc = hr_check_footprint(ctx, b.hl, b.hw, b.wb, fn))) return rc;
+  }
+  if (b.M == 0) return FO_OK;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HrBrakeLadderArgs a{b.M, b.T, p->B, p->K, brake_ladder_width(p->K), brake_ladder_group(b.T, p->K, p->B), b.d_x, b.d_y, b.d_heading,
+                            b.d_len_or_null, b.hl, b.hw, b.wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx,
+                            sc->map->rny, b.win_ix0, b.win_iy0, b.win_nx, b.win_ny, b.d_arrival, b.d_first, p->d_v, p->d_arc, p->dt,
+                            p->d_brake_first, p->d_stop, p->d_required, p->d_last_unclear, p->d_commit};
+  HbLevels lv;
+  for (int k = 0; k < FO_HIDDEN_BRAKE_MAX_LEVELS; ++k) lv.v[k] = k < p->K ? p->h_levels[k] : 0.0;
+  hipLaunchKernelGGL(fo_hr_brake_ladder_kernel, dim3((unsigned)brake_ladder_blocks(b.M, b.T, p->K, p->B)), dim3(HB_THREADS),
+                     brake_ladder_lds_bytes(b.T, p->K, p->B), (hipStream_t)stream, a, lv);
   FO_HIP_TRY(ctx, hipGetLastError());
   return FO_OK;
 }

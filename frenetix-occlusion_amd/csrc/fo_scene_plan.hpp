@@ -79,6 +79,28 @@ inline size_t brake_users_lds_bytes(int T, int K, int C) {
 inline size_t brake_users_lds_bound() {
   return (size_t)brake_per_block(254) * 254 * (6 * sizeof(double) + BRAKE_USERS_MAX_MAPS * sizeof(int32_t)) + BRAKE_USERS_MAX_TABLE * sizeof(int32_t);
 }
+// the brake ladder: a lane per (m, b, k), k fastest, padded to Kp = the power of two >= K (brake_ladder_width); G lanes per
+// trajectory = the power of two >= min(B * Kp, HB_THREADS) -- then doubled while the six rows of the workgroup's HB_THREADS / G
+// trajectories (48 T bytes each) exceed BRAKE_LADDER_ROWS_BYTES: the lanes' rule alone would stage 256 trajectories with B * K = 1,
+// 3 MB at T = 254.  Half of the 64 KB a workgroup may take: a CU then holds four such workgroups, not two.  Behind the rows
+// stands one int32 per lane of the workgroup, through which the waves of a trajectory (G > 64) meet for commit
+constexpr int BRAKE_LADDER_MAX_LEVELS = 64;       // FO_HIDDEN_BRAKE_MAX_LEVELS
+constexpr int BRAKE_LADDER_ROWS_BYTES = 32768;
+inline int brake_ladder_width(int K) { int Kp = 1; while (Kp < K && Kp < BRAKE_LADDER_MAX_LEVELS) Kp <<= 1; return Kp; }
+inline int brake_ladder_group(int T, int K, int B) {
+  int G = brake_ladder_width(K);
+  while (G < HB_THREADS && (int64_t)G < (int64_t)B * brake_ladder_width(K)) G <<= 1;
+  while (G < HB_THREADS && (size_t)(HB_THREADS / G) * 6 * (size_t)T * sizeof(double) > (size_t)BRAKE_LADDER_ROWS_BYTES) G <<= 1;
+  return G;
+}
+inline int brake_ladder_per_block(int T, int K, int B) { return HB_THREADS / brake_ladder_group(T, K, B); }
+inline int brake_ladder_blocks(int M, int T, int K, int B) {
+  const int p = brake_ladder_per_block(T, K, B);
+  return (int)(((int64_t)M + p - 1) / p);
+}
+inline size_t brake_ladder_lds_bytes(int T, int K, int B) {
+  return (size_t)brake_ladder_per_block(T, K, B) * 6 * (size_t)T * sizeof(double) + HB_THREADS * sizeof(int32_t);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -53,7 +53,7 @@ EXPORTS = [
     "fo_scene_hidden_reach_road", "fo_scene_hidden_clearance", "fo_scene_set_occlusion_memory_road",
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
-    "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users",
+    "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
 ]
 
 
@@ -157,6 +157,15 @@ class HiddenBrakeUsers(C.Structure):    # fo_hidden_brake_users_t
                 ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
                 ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
                 ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
+
+
+HIDDEN_BRAKE_MAX_LEVELS = 64    # FO_HIDDEN_BRAKE_MAX_LEVELS: decelerations one fo_scene_hidden_brake_ladder call evaluates
+
+
+class HiddenBrakeLadder(C.Structure):   # fo_hidden_brake_ladder_t
+    _fields_ = [("base", HiddenReach), ("d_v", C.c_void_p), ("d_arc", C.c_void_p), ("h_levels", C.POINTER(C.c_double)),
+                ("K", C.c_int32), ("B", C.c_int32), ("dt", C.c_double), ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p),
+                ("d_required", C.c_void_p), ("d_last_unclear", C.c_void_p), ("d_commit", C.c_void_p)]
 
 
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
@@ -271,6 +280,7 @@ def load():
     lib.fo_scene_hidden_brake.argtypes = [vp, C.POINTER(HiddenBrake), vp]
     lib.fo_scene_hidden_brake_classes.argtypes = [vp, C.POINTER(HiddenBrakeClasses), vp]
     lib.fo_scene_hidden_brake_users.argtypes = [vp, C.POINTER(HiddenBrakeUsers), vp]
+    lib.fo_scene_hidden_brake_ladder.argtypes = [vp, C.POINTER(HiddenBrakeLadder), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

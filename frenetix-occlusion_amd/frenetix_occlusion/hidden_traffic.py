@@ -1,5 +1,6 @@
-"""Hidden traffic (an extension): the reach forecast for one speed and the clearance that serves every speed up to
-a cap.  ``hidden_reach`` and ``hidden_clearance`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods (``self``)."""
+"""Hidden traffic (an extension): the reach forecast for one speed, the clearance that serves every speed up to
+a cap, the witnesses, and the brake clearance with its siblings (by classes, by road users, at a ladder of decelerations).  The
+functions that take ``self`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods."""
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -490,6 +491,115 @@ def hidden_brake(self, x, y, theta, v, *, vehicle, v_max, dt, a_brake, margin=No
     self.ctx.call("fo_scene_hidden_brake", C.byref(args), N.current_stream(self._dev_index))
     self._hb_inputs = (tv, arc)                             # (stay referenced until the next call, as in hidden_reach)
     return HiddenBrake(reach, brake_first, stop, commit, arc, a_brake, float(dt), tlen)
+
+
+def reference_deceleration_ladder(lo, hi):
+    """the deceleration vector the reference's manoeuvre routine makes of ``deceleration=[lo, hi]``: ``np.arange(lo, hi, 0.1)``
+    (metrics/be.py:106-107), float64 -- ``hi`` itself is not on it, and its entries are arange's ``lo + n * 0.1``, not decimals"""
+    return np.arange(lo, hi, 0.1)
+
+
+@dataclass
+class HiddenBrakeLadder:
+    """what :meth:`SensorModel.hidden_brake_ladder` returns (DESIGN.md §5.10 "Brake ladder"): ``reach`` is the :class:`HiddenReach` of
+    the forecast the manoeuvres were held against, ``decelerations`` (host float64 ``[K]``, strictly ascending) the ladder, and (device
+    tensors, int32) ``brake_first [M, B, K]`` and ``stop [M, B, K]`` -- slice k is, bit for bit, ``brake_first`` / ``stop`` of
+    ``hidden_brake(a_brake=decelerations[k])`` at the brake starts ``b < B`` --, ``commit [M, K]`` -- that call's ``commit`` where it
+    is ``< B``, else -1 --, ``required [M, B]`` -- the first level at which "follow candidate m until sample b, then brake" stays
+    clear of hidden traffic while it moves, -1 = no level of the ladder does --, ``last_unclear [M, B]`` -- the last level at which
+    it does not, -1 = every level is clear.  Both are -1 where there is no manoeuvre (``b >= lengths[m]``).  ``arc``, ``dt``,
+    ``lengths`` as in :class:`HiddenBrake`.
+
+    Not claimed: what :class:`HiddenBrake` does not claim; the answer is only as fine as the ladder; ``required`` is the first clear
+    level, not a root -- harder braking is not always safer against an arrival map (:meth:`monotone`)."""
+    reach: HiddenReach
+    brake_first: torch.Tensor
+    stop: torch.Tensor
+    commit: torch.Tensor
+    required: torch.Tensor
+    last_unclear: torch.Tensor
+    decelerations: np.ndarray
+    arc: torch.Tensor
+    dt: float
+    lengths: Optional[torch.Tensor] = None
+
+    def level(self, k):
+        """``(brake_first [M, B], stop [M, B], commit [M])`` of level k: what ``hidden_brake(a_brake=decelerations[k])`` gives at the
+        brake starts ``b < B`` (views, nothing is copied)"""
+        return self.brake_first[:, :, k], self.stop[:, :, k], self.commit[:, k]
+
+    def required_deceleration(self):
+        """``[M, B]`` float64 (m/s^2): ``decelerations[required]``; ``+inf`` where a manoeuvre exists and no level of the ladder is
+        clear; ``nan`` where there is no manoeuvre (``required == last_unclear == -1``).  Torch ops on the tensors' device, nothing
+        is read back."""
+        dev = self.required.device
+        levels = torch.as_tensor(np.append(np.asarray(self.decelerations, dtype=np.float64), np.inf), device=dev)
+        req = self.required.to(torch.int64)
+        out = levels[torch.where(req >= 0, req, len(levels) - 1)]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        return torch.where((req < 0) & (self.last_unclear < 0), nan, out)
+
+    def brake_threat_number(self, a_max):
+        """``[M, B]`` float64: :meth:`required_deceleration` divided by ``a_max`` -- the reference's ``break_threat_number``
+        (metrics/be.py:56) against hidden traffic"""
+        return self.required_deceleration() / float(a_max)
+
+    def monotone(self):
+        """``[M, B]`` bool: ``required == last_unclear + 1`` or ``required == -1`` -- below the first clear level everything is
+        unclear and from it on everything is clear: where the reference's bisection would have been sound"""
+        return (self.required == self.last_unclear + 1) | (self.required == -1)
+
+
+def hidden_brake_ladder(self, x, y, theta, v, *, vehicle, v_max, dt, decelerations, starts=None, margin=None, inflate=0.0, lengths=None,
+                        metric="euclid", flow="any"):
+    """Hidden-traffic brake ladder (``fo_scene_hidden_brake_ladder``; DESIGN.md §5.10 "Brake ladder"): runs ``hidden_reach(...)``
+    with these arguments and, on the very same device inputs, ONE more launch that holds the manoeuvre "follow the candidate until
+    sample b, then brake" of every (candidate, b) against the forecast's arrival map at every deceleration of ``decelerations``
+    (1 .. 64 finite values >= 0, strictly ascending, m/s^2) for the brake starts ``b < starts`` (an integer in ``[1, T]``, None =
+    T); returns a :class:`HiddenBrakeLadder`, whose ``required`` is the gentlest deceleration of the ladder that keeps the moving ego
+    clear.  The other arguments as for :meth:`hidden_brake`.  Nothing is read back and nobody waits for the kernels."""
+    reach = hidden_reach(self, x, y, theta, vehicle=vehicle, v_max=v_max, dt=dt, margin=margin, inflate=inflate, lengths=lengths,
+                         metric=metric, flow=flow)
+    tx, ty, heading, tlen = self._hr_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T):
+        raise ValueError("hidden_brake_ladder: v must be [M, T]")
+    levels = np.zeros(0)                                   # (what is no 1-D sequence of numbers is refused as an empty ladder is)
+    if not isinstance(decelerations, (str, bytes)) and np.ndim(decelerations) == 1:
+        try:
+            levels = np.array([float(a) for a in decelerations], dtype=np.float64)
+        except (TypeError, ValueError):
+            pass
+    if not 1 <= len(levels) <= N.HIDDEN_BRAKE_MAX_LEVELS or not (np.isfinite(levels) & (levels >= 0.0)).all():
+        raise ValueError(f"hidden_brake_ladder: decelerations must hold 1 .. {N.HIDDEN_BRAKE_MAX_LEVELS} finite values >= 0")
+    if not (np.diff(levels) > 0.0).all():
+        raise ValueError("hidden_brake_ladder: decelerations must be strictly ascending (required is then the gentlest clear one)")
+    if starts is None:
+        starts = T
+    if isinstance(starts, bool) or not isinstance(starts, (int, np.integer)) or not 1 <= int(starts) <= T:
+        raise ValueError(f"hidden_brake_ladder: starts = {starts!r}, an integer in [1, T = {T}] or None")
+    B, K = int(starts), len(levels)
+    dev, w = self.device, reach.window
+    tv = N.on_device(v, dev)
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    arc = N.on_device(arc, dev)
+    brake_first = torch.empty((M, B, K), dtype=torch.int32, device=dev)
+    stop = torch.empty((M, B, K), dtype=torch.int32, device=dev)
+    required = torch.empty((M, B), dtype=torch.int32, device=dev)
+    last_unclear = torch.empty((M, B), dtype=torch.int32, device=dev)
+    commit = torch.empty((M, K), dtype=torch.int32, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    base = N.HiddenReach(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(heading), d_len_or_null=N.ptr(tlen),
+                         hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, J=T,
+                         h_r2=reach.r2.ctypes.data_as(C.POINTER(C.c_int32)), win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx, win_ny=w.ny,
+                         d_arrival=reach.arrival.data_ptr(), d_first=N.ptr(reach.first))
+    args = N.HiddenBrakeLadder(base=base, d_v=N.ptr(tv), d_arc=N.ptr(arc), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), K=K, B=B,
+                               dt=float(dt), d_brake_first=N.ptr(brake_first), d_stop=N.ptr(stop), d_required=N.ptr(required),
+                               d_last_unclear=N.ptr(last_unclear), d_commit=N.ptr(commit))
+    self.ctx.call("fo_scene_hidden_brake_ladder", C.byref(args), N.current_stream(self._dev_index))
+    self._hbl_inputs = (tv, arc)                            # (stay referenced until the next call, as in hidden_brake)
+    return HiddenBrakeLadder(reach, brake_first, stop, commit, required, last_unclear, levels, arc, float(dt), tlen)
 
 
 def hidden_brake_thresholds(speeds, dt, margin, cell_size, T):

@@ -414,6 +414,36 @@ class FOInterface:
                                               margin=om["margin"] if margin is None else margin, dt=self.dt,
                                               a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate, metric=metric, flow=flow)
 
+    def hidden_brake_ladder(self, trajectories, decelerations=None, starts=None, v_max=None, margin=None, inflate=0.0, metric="euclid",
+                            flow="any"):
+        """EXTENSION, not part of the reference: the fail-safe question of :meth:`hidden_brake` at a ladder of decelerations from one
+        launch, and per candidate and brake start the gentlest level that keeps the moving ego clear of hidden traffic -- a brake
+        threat number against hidden traffic (:meth:`SensorModel.hidden_brake_ladder`; returns its
+        :class:`~frenetix_occlusion.sensor_model.HiddenBrakeLadder`: ``required``, ``last_unclear [M, B]``, ``commit [M, K]``,
+        ``brake_first``, ``stop [M, B, K]``; ``.required_deceleration()``, ``.brake_threat_number(a_max)``, ``.monotone()``).
+        ``decelerations`` defaults to 0.5, 1.0, ... up to ``vehicle_params.a_max``, with ``a_max`` itself appended if it is not on
+        that grid (more than 64 levels are refused); ``starts`` (None = every sample) is the number of brake starts considered.
+        The other arguments and defaults as for :meth:`hidden_brake`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_ladder needs a previous evaluate_scenario")
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        if decelerations is None:
+            a_max = float(vt[4])
+            n = int(a_max // 0.5) if 0.5 <= a_max < float("inf") else 0      # levels on the 0.5 grid
+            on_grid = n > 0 and 0.5 * n == a_max
+            if n + (not on_grid) > N.HIDDEN_BRAKE_MAX_LEVELS:
+                raise ValueError(f"hidden_brake_ladder: the default ladder 0.5, 1.0, ... up to a_max = {a_max} m/s^2 has more than "
+                                 f"{N.HIDDEN_BRAKE_MAX_LEVELS} levels (hand decelerations over)")
+            decelerations = [0.5 * (k + 1) for k in range(n)] + ([] if on_grid else [a_max])
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        return self.sensor_model.hidden_brake_ladder(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3],
+                                                     v_max=om["v_max"] if v_max is None else v_max,
+                                                     margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                     decelerations=decelerations, starts=starts, inflate=inflate, metric=metric, flow=flow)
+
     def hidden_brake_classes(self, trajectories, speeds, a_brake=None, margin=None, inflate=0.0, metric="euclid", flow="any"):
         """EXTENSION, not part of the reference: the fail-safe question of :meth:`hidden_brake` for several hidden road users at
         once -- ``speeds`` (m/s, 1 .. 8 values: a pedestrian, a cyclist, a car) -- from one clearance and one walk over its key map

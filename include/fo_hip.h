@@ -718,6 +718,52 @@ typedef struct {
 } fo_hidden_brake_users_t;
 int fo_scene_hidden_brake_users(fo_ctx *ctx, const fo_hidden_brake_users_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic BRAKE LADDER (DESIGN.md §5.10 "Brake ladder") -- the brake clearance above
+ * at a ladder of K decelerations from ONE launch, and per candidate and brake start the first level of the ladder at which the
+ * moving ego stays clear of road hidden traffic may have reached: a brake threat number against hidden traffic (the reference's
+ * BE metric, metrics/be.py:31-82, asks it of phantom rectangles and searches by bisection; its manoeuvre routine takes a ladder,
+ * be.py:106-107).  Harder braking is NOT always at least as safe against an arrival map -- a harder-braking ego may still crawl
+ * through a cell when hidden traffic reaches it, which the gentler manoeuvre had left --, so every level is evaluated and
+ * last_unclear says where a bisection's assumption fails.  Opt-in and additive: one launch, nothing is read back, no other
+ * output changes.
+ *  Inputs: those of fo_scene_hidden_brake -- one forecast call's trajectories, headings, d_len_or_null, extents, window, J = T, h_r2,
+ *   A = base.d_arrival, first = base.d_first, d_v, d_arc, dt -- and in place of a_brake: h_levels [K], float64 on the HOST, read
+ *   during the call as h_r2 is (they travel as a kernel argument), 1 <= K <= FO_HIDDEN_BRAKE_MAX_LEVELS, every level finite and
+ *   >= 0, in any order, repeats allowed; B, the number of brake starts considered, b = 0 .. B-1, 1 <= B <= T.
+ *  For trajectory m, brake start b < B and level k:
+ *  1. Steps 1 - 4 of fo_scene_hidden_brake word for word with a_brake = levels[k]: brake_first[m][b][k] and stop[m][b][k], both -1
+ *   where b >= Lm.
+ *  2. unclear(m, b, k) iff 0 <= first[m] <= b or 0 <= brake_first[m][b][k] < stop[m][b][k].
+ *  3. required[m][b] = the smallest k that is not unclear, -1 if every level is unclear.  last_unclear[m][b] = the largest k that
+ *   is unclear, -1 if none is.  For b >= Lm both are -1: that pair cannot occur for a real manoeuvre, it marks "no manoeuvre".
+ *  4. commit[m][k] = the smallest b < min(B, Lm) with unclear(m, b, k), -1 = none.
+ *  Outputs, every byte written by every call, int32: d_brake_first [M][B][K], d_stop [M][B][K], d_required [M][B],
+ *   d_last_unclear [M][B], d_commit [M][K] (K innermost: lanes dealt along the levels store next to each other).
+ *  The tie: slice k of brake_first and stop equals, bit for bit, what fo_scene_hidden_brake gives with a_brake = levels[k] at the
+ *   brake starts b < B; commit[.][k] is that entry's commit where it is < B, else -1.
+ *  Safety of the data: as fo_scene_hidden_brake; the levels may hold anything the refusals let through, no index depends on them.
+ *  Not claimed: what fo_scene_hidden_brake does not claim; the ladder's answer is only as fine as its levels; required is the
+ *   first clear level BY INDEX, not a root of anything (with ascending levels it is the gentlest clear deceleration of the ladder).
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_brake_ladder:"): J outside
+ * [1, 254]; no h_r2 or base.d_arrival; a window outside [1, 32768]^2; h_r2 refused as by fo_scene_hidden_reach; M < 0; K outside
+ * [1, 64]; no h_levels; a level negative or not finite; dt not positive and finite; with M > 0: T outside [1, J], B outside
+ * [1, T], no d_x / d_y / d_heading / d_first, no d_v or d_arc, a missing output buffer, or extents refused as by
+ * fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+#define FO_HIDDEN_BRAKE_MAX_LEVELS 64
+typedef struct {
+  fo_hidden_reach_t base;                   /* as in fo_hidden_brake_t: d_arrival and d_first are INPUTS here */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  const double *h_levels;                   /* HOST [K] decelerations, m/s^2 */
+  int32_t K;                                /* levels */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  double dt;
+  int32_t *d_brake_first, *d_stop;          /* [M][B][K] */
+  int32_t *d_required, *d_last_unclear;     /* [M][B] */
+  int32_t *d_commit;                        /* [M][K] */
+} fo_hidden_brake_ladder_t;
+int fo_scene_hidden_brake_ladder(fo_ctx *ctx, const fo_hidden_brake_ladder_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

@@ -4,7 +4,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
 
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
-                                       [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...]
+                                       [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...] [--brake-ladder K]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -30,6 +30,11 @@ users at the deceleration of ``--brake`` (§5.10 "Brake clearance by road users"
 -- next to one ``hidden_brake_classes`` call per forecast in the same process, with and without the headings handed over; in every
 run every user's rows are compared with its forecast's own call (exact integers); also the poses the one walk scanned and the poses
 the per-forecast walks scan.
+
+``--brake-ladder K``: ``hidden_brake_ladder`` at the K decelerations ``linspace(0.5, A, K)`` (A: the deceleration of ``--brake``; K = 23
+at the vehicle's ``a_max`` = 11.5 is the interface's default ladder 0.5, 1.0, ...) from every brake start (§5.10 "Brake ladder") --
+the forecast plus ONE launch -- next to K ``hidden_brake`` calls in the same process; every level's slice is compared with that
+call's (exact integers); also the poses the ladder scanned, the histogram of ``required`` and the non-monotone pairs.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -81,6 +86,8 @@ def main():
                     help="time hidden_brake_classes for these hidden-user speeds (m/s) next to one hidden_brake call per speed")
     ap.add_argument("--brake-users", default=None, metavar="V:METRIC:FLOW,...",
                     help="time hidden_brake_users for these hidden road users next to one hidden_brake_classes call per forecast")
+    ap.add_argument("--brake-ladder", type=int, default=None, metavar="K",
+                    help="time hidden_brake_ladder at K decelerations up to the one of --brake next to K hidden_brake calls")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -215,6 +222,38 @@ def main():
         res["commit_never_per_user"] = [int(v) for v in (u_out.commit < 0).sum(dim=1).cpu()]
         cu = u_out.critical_user()
         res["candidates_by_critical_user"] = {str(c): int((cu == c).sum()) for c in range(-1, len(users))}
+    if a.brake_ladder:
+        a_top = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
+        levels = np.linspace(0.5, a_top, a.brake_ladder) if a.brake_ladder > 1 else np.array([a_top])
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbl = lambda: sm.hidden_brake_ladder(tx, ty, tth, tv, vehicle=veh, v_max=a.v_max, dt=0.1, decelerations=levels, metric=a.metric,
+                                             flow=a.flow)
+        per_level = lambda: [sm.hidden_brake(tx, ty, tth, tv, vehicle=veh, v_max=a.v_max, dt=0.1, a_brake=float(lv), metric=a.metric, flow=a.flow)
+                             for lv in levels]
+        l_out, singles = hbl(), per_level()
+        for k, one in enumerate(singles):           # the tie: every level is that deceleration's own call, bit for bit
+            bf_k, st_k, cm_k = l_out.level(k)
+            assert torch.equal(bf_k, one.brake_first) and torch.equal(st_k, one.stop) and torch.equal(cm_k, one.commit), float(levels[k])
+        res["brake_ladder_levels"] = [float(lv) for lv in levels]
+        res["brake_ladder_call_ms"] = _median_ms(hbl, a.calls)
+        res["hidden_brake_call_per_level_ms"] = _median_ms(per_level, a.calls)
+        bf, st = (t.cpu().numpy().astype(np.int64) for t in (l_out.brake_first, l_out.stop))      # [M, B, K]
+        b = np.arange(T)[None, :, None]
+        i0 = np.maximum(st, b + 1)                  # the sample at which the standing pose is first taken
+        moving = np.minimum(i0, T) - (b + 1)        # poses before it
+        scans = np.where((bf >= 0) & (bf < i0), bf - b, moving + (i0 < T))
+        req, lu = (t.cpu().numpy().astype(np.int64) for t in (l_out.required, l_out.last_unclear))
+        res["ladder_manoeuvres"] = int(M * T * len(levels))
+        res["ladder_poses_scanned"] = int(scans.sum())
+        res["ladder_poses_scanned_per_level"] = [int(v) for v in scans.sum(axis=(0, 1))]
+        res["longest_ladder_manoeuvre_scanned"] = int(scans.max(initial=0))
+        res["required_histogram"] = {str(k): int((req == k).sum()) for k in range(-1, len(levels))}
+        fm = l_out.reach.first.cpu().numpy().astype(np.int64)[:, None]
+        blocked = (fm >= 0) & (fm <= np.arange(T)[None, :])       # the candidate itself is in reached road: no level can be clear
+        res["pairs_blocked_by_first"] = int(blocked.sum())
+        res["pairs_without_a_clear_level_unblocked"] = int(((req < 0) & ~blocked).sum())
+        res["non_monotone_pairs"] = int((~l_out.monotone()).sum())
+        res["non_monotone_required_below_last_unclear"] = int(((req >= 0) & (req < lu)).sum())
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
