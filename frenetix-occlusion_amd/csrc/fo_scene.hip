@@ -47,6 +47,7 @@
 //   fo_hidden_brake_classes.hpp  fo_hr_brake_classes_kernel  brake clearance for several hidden-user speeds: one walk over the key map
 //   fo_hidden_brake_users.hpp  fo_hr_brake_users_kernel  ... for road users on different forecasts: one walk over up to three key maps
 //   fo_hidden_brake_ladder.hpp  fo_hr_brake_ladder_kernel  brake clearance at a ladder of decelerations: a lane per (m, b, level)
+//   fo_hidden_brake_ladder_users.hpp  fo_hr_brake_ladder_users_kernel  ... the ladder for road users on different forecasts in one walk
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -62,6 +63,7 @@
 #include "fo_hidden_brake_classes.hpp"
 #include "fo_hidden_brake_users.hpp"
 #include "fo_hidden_brake_ladder.hpp"
+#include "fo_hidden_brake_ladder_users.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
 #include "fo_future_visibility.hpp"
@@ -1009,6 +1011,94 @@ int fo_scene_hidden_brake_ladder(fo_ctx *ctx, const fo_hidden_brake_ladder_t *p,
   for (int k = 0; k < FO_HIDDEN_BRAKE_MAX_LEVELS; ++k) lv.v[k] = k < p->K ? p->h_levels[k] : 0.0;
   hipLaunchKernelGGL(fo_hr_brake_ladder_kernel, dim3((unsigned)brake_ladder_blocks(b.M, b.T, p->K, p->B)), dim3(HB_THREADS),
                      brake_ladder_lds_bytes(b.T, p->K, p->B), (hipStream_t)stream, a, lv);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+// the brake ladder of every (trajectory, brake start < B) against every class of road user on the key map it names, and the first
+// level clear of all of them: one launch (fo_hidden_brake_ladder_users.hpp); the levels, map_of and the table travel as kernel arguments
+int fo_scene_hidden_brake_ladder_users(fo_ctx *ctx, const fo_hidden_brake_ladder_users_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_brake_ladder_users";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  if (p->K < 1 || p->K > FO_HIDDEN_BRAKE_MAX_MAPS)
+    return fo_fail(ctx, FO_E_ARG, "%s: K = %d outside [1, FO_HIDDEN_BRAKE_MAX_MAPS = %d]", fn, p->K, FO_HIDDEN_BRAKE_MAX_MAPS);
+  if (p->C < 1 || p->C > FO_HIDDEN_BRAKE_MAX_CLASSES)
+    return fo_fail(ctx, FO_E_ARG, "%s: C = %d outside [1, FO_HIDDEN_BRAKE_MAX_CLASSES = %d]", fn, p->C, FO_HIDDEN_BRAKE_MAX_CLASSES);
+  if (!p->h_thr) return fo_fail(ctx, FO_E_ARG, "%s: no threshold table h_thr [C][T]", fn);
+  if ((rc = hr_check_extent(ctx, p->win_nx, p->win_ny, fn))) return rc;
+  const int K = p->K, C = p->C;
+  for (int k = 0; k < K; ++k) {
+    if (p->r2_cap[k] < 0) return fo_fail(ctx, FO_E_ARG, "%s: r2_cap[%d] = %d is negative", fn, k, p->r2_cap[k]);
+    static const char *const names[FO_HIDDEN_BRAKE_MAX_MAPS] = {"r2_cap[0]", "r2_cap[1]", "r2_cap[2]"};
+    if ((rc = hr_check_halo(ctx, p->r2_cap[k], names[k], "v_cap", fn))) return rc;
+  }
+  for (int c = 0; c < C; ++c)
+    if (p->map_of[c] < 0 || p->map_of[c] >= K)
+      return fo_fail(ctx, FO_E_ARG, "%s: map_of[%d] = %d outside [0, K = %d)", fn, c, p->map_of[c], K);
+  if (p->M < 0) return fo_fail(ctx, FO_E_ARG, "%s: M = %d", fn, p->M);
+  if (p->L < 1 || p->L > FO_HIDDEN_BRAKE_MAX_LEVELS)
+    return fo_fail(ctx, FO_E_ARG, "%s: L = %d outside [1, FO_HIDDEN_BRAKE_MAX_LEVELS = %d]", fn, p->L, FO_HIDDEN_BRAKE_MAX_LEVELS);
+  if (!p->h_levels) return fo_fail(ctx, FO_E_ARG, "%s: no decelerations h_levels [L]", fn);
+  const int L = p->L;
+  for (int l = 0; l < L; ++l)
+    if (!(p->h_levels[l] >= 0.0) || !std::isfinite(p->h_levels[l]))      // (NaN fails every comparison)
+      return fo_fail(ctx, FO_E_ARG, "%s: h_levels[%d] = %g, a finite deceleration >= 0 is needed", fn, l, p->h_levels[l]);
+  if (!(p->dt > 0.0) || !std::isfinite(p->dt)) return fo_fail(ctx, FO_E_ARG, "%s: dt = %g, a finite step > 0 is needed", fn, p->dt);
+  if (p->M == 0) return FO_OK;
+  const int T = p->T, B = p->B;
+  if (T < 1 || T > HR_MAX_J) return fo_fail(ctx, FO_E_ARG, "%s: T = %d outside [1, %d]", fn, T, HR_MAX_J);
+  if (B < 1 || B > T) return fo_fail(ctx, FO_E_ARG, "%s: B = %d outside [1, T = %d]", fn, B, T);
+  if (C * T > FO_HIDDEN_BRAKE_MAX_TABLE)
+    return fo_fail(ctx, FO_E_ARG, "%s: C * T = %d * %d = %d entries, the table is a kernel argument of at most "
+                   "FO_HIDDEN_BRAKE_MAX_TABLE = %d", fn, C, T, C * T, FO_HIDDEN_BRAKE_MAX_TABLE);
+  if (4 * C * T + 8 * L > FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES)
+    return fo_fail(ctx, FO_E_ARG, "%s: %d thresholds (C * T = %d * %d) and %d levels take 4 * %d + 8 * %d = %d bytes, they travel as a "
+                   "kernel argument of at most FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES = %d", fn, C * T, C, T, L, C * T, L,
+                   4 * C * T + 8 * L, FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES);
+  for (int c = 0; c < C; ++c) {
+    const int32_t *row = p->h_thr + (size_t)c * T;
+    const int64_t cap = (int64_t)169 * p->r2_cap[p->map_of[c]];
+    if (row[0] < 0) return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d][0] = %d is negative", fn, c, row[0]);
+    for (int j = 1; j < T; ++j)
+      if (row[j] < row[j - 1])
+        return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d] decreases at entry %d (%d after %d)", fn, c, j, row[j], row[j - 1]);
+    if (row[T - 1] > cap)
+      return fo_fail(ctx, FO_E_ARG, "%s: h_thr[%d][T-1] = %d lies beyond 169 r2_cap[%d] = %lld (the key map of class %d ends at its cap)",
+                     fn, c, row[T - 1], p->map_of[c], (long long)cap, c);
+  }
+  if (!p->d_x || !p->d_y || !p->d_heading)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_x, d_y [M][T] and d_heading [M][T][2] are required with M > 0", fn);
+  for (int k = 0; k < K; ++k)
+    if (!p->d_key[k] || !p->d_qmin[k])
+      return fo_fail(ctx, FO_E_ARG, "%s: d_key[%d] [win_ny][win_nx] and d_qmin[%d] [M][T] of clearance %d are required with M > 0", fn,
+                     k, k, k);
+  if (!p->d_v || !p->d_arc) return fo_fail(ctx, FO_E_ARG, "%s: d_v and d_arc [M][T] are required with M > 0", fn);
+  if (!p->d_required || !p->d_last_unclear || !p->d_commit || !p->d_first || !p->d_required_all || !p->d_last_unclear_all || !p->d_blocking)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_required, d_last_unclear [C][M][B], d_commit [C][M][L], d_first [C][M], d_required_all, "
+                   "d_last_unclear_all and d_blocking [M][B] are required with M > 0", fn);
+  if (!p->d_brake_first_or_null != !p->d_stop_or_null)
+    return fo_fail(ctx, FO_E_ARG, "%s: the detail d_brake_first_or_null [C][M][B][L] and d_stop_or_null [M][B][L] is given whole or not "
+                   "at all (%s is missing)", fn, p->d_stop_or_null ? "d_brake_first_or_null" : "d_stop_or_null");
+  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  HrBrakeLadderUsersArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_users_group(T, K, L, B), p->d_x, p->d_y, p->d_heading,
+                           p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx,
+                           sc->map->rny, p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, p->d_key[0], K > 1 ? p->d_key[1] : nullptr,
+                           K > 2 ? p->d_key[2] : nullptr, p->d_qmin[0], K > 1 ? p->d_qmin[1] : nullptr, K > 2 ? p->d_qmin[2] : nullptr, 0u,
+                           p->d_v, p->d_arc, p->dt, p->d_required, p->d_last_unclear, p->d_commit, p->d_first, p->d_required_all,
+                           p->d_last_unclear_all, p->d_blocking, p->d_brake_first_or_null, p->d_stop_or_null};
+  for (int c = 0; c < C; ++c) a.map_of |= (uint32_t)p->map_of[c] << (2 * c);
+  HbluPack pk;
+  memset(pk.w, 0, sizeof pk.w);
+  memcpy(pk.w, p->h_levels, (size_t)L * sizeof(double));        // (little endian: low word first)
+  memcpy(pk.w + 2 * L, p->h_thr, (size_t)C * T * sizeof(int32_t));
+  const dim3 grid((unsigned)brake_ladder_users_blocks(p->M, T, K, L, B)), block(HB_THREADS);
+  const size_t lds = brake_ladder_users_lds_bytes(T, K, C, L, B);
+  hipStream_t s = (hipStream_t)stream;
+  if (brake_users_width(C) == 4) hblu_launch<4>(K, grid, block, lds, s, a, pk);
+  else hblu_launch<8>(K, grid, block, lds, s, a, pk);
   FO_HIP_TRY(ctx, hipGetLastError());
   return FO_OK;
 }

@@ -101,6 +101,39 @@ inline int brake_ladder_blocks(int M, int T, int K, int B) {
 inline size_t brake_ladder_lds_bytes(int T, int K, int B) {
   return (size_t)brake_ladder_per_block(T, K, B) * 6 * (size_t)T * sizeof(double) + HB_THREADS * sizeof(int32_t);
 }
+// the brake ladder by road users: the ladder's lanes -- a lane per (m, b, l), l fastest, padded to Lp = brake_ladder_width(L); G
+// lanes per trajectory = the power of two >= min(B * Lp, HB_THREADS), then doubled while the rows of the workgroup's HB_THREADS / G
+// trajectories exceed BRAKE_LADDER_ROWS_BYTES -- with the users kernel's rows: per trajectory the six float64 rows and one int32 qmin
+// row per map, T * (48 + 4 K) bytes.  Behind them the table (4 C T bytes) and the commit exchange, one int32 per class and lane of
+// the workgroup.  brake_ladder_users_lds_bound: no call needs more -- the rows stay within BRAKE_LADDER_ROWS_BYTES wherever a
+// workgroup holds two trajectories or more, a single one takes at most 254 * 60 bytes; the table is part of the argument
+// (4 C T + 8 L <= BRAKE_LADDER_USERS_MAX_ARG_BYTES); the exchange is at most 8 classes wide: 44 544 bytes, under the 64 KB of a
+// workgroup
+constexpr int BRAKE_LADDER_USERS_MAX_ARG_BYTES = 3584;   // FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES
+constexpr int BRAKE_LADDER_USERS_MAX_CLASSES = 8;        // FO_HIDDEN_BRAKE_MAX_CLASSES
+inline int brake_ladder_users_width(int L) { return brake_ladder_width(L); }
+inline int brake_ladder_users_group(int T, int K, int L, int B) {
+  const int Lp = brake_ladder_users_width(L);
+  const size_t per_traj = (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t));
+  int G = Lp;
+  while (G < HB_THREADS && (int64_t)G < (int64_t)B * Lp) G <<= 1;
+  while (G < HB_THREADS && (size_t)(HB_THREADS / G) * per_traj > (size_t)BRAKE_LADDER_ROWS_BYTES) G <<= 1;
+  return G;
+}
+inline int brake_ladder_users_per_block(int T, int K, int L, int B) { return HB_THREADS / brake_ladder_users_group(T, K, L, B); }
+inline int brake_ladder_users_blocks(int M, int T, int K, int L, int B) {
+  const int p = brake_ladder_users_per_block(T, K, L, B);
+  return (int)(((int64_t)M + p - 1) / p);
+}
+inline size_t brake_ladder_users_lds_bytes(int T, int K, int C, int L, int B) {
+  return (size_t)brake_ladder_users_per_block(T, K, L, B) * (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t)) +
+         (size_t)C * (size_t)T * sizeof(int32_t) + (size_t)C * HB_THREADS * sizeof(int32_t);
+}
+inline size_t brake_ladder_users_lds_bound() {
+  const size_t one = (size_t)254 * (6 * sizeof(double) + BRAKE_USERS_MAX_MAPS * sizeof(int32_t));
+  return (one > (size_t)BRAKE_LADDER_ROWS_BYTES ? one : (size_t)BRAKE_LADDER_ROWS_BYTES) + BRAKE_LADDER_USERS_MAX_ARG_BYTES +
+         (size_t)BRAKE_LADDER_USERS_MAX_CLASSES * HB_THREADS * sizeof(int32_t);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -54,6 +54,7 @@ EXPORTS = [
     "fo_scene_set_lane_moves", "fo_scene_hidden_reach_flow", "fo_scene_hidden_clearance_flow",
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
     "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
+    "fo_scene_hidden_brake_ladder_users",
 ]
 
 
@@ -166,6 +167,23 @@ class HiddenBrakeLadder(C.Structure):   # fo_hidden_brake_ladder_t
     _fields_ = [("base", HiddenReach), ("d_v", C.c_void_p), ("d_arc", C.c_void_p), ("h_levels", C.POINTER(C.c_double)),
                 ("K", C.c_int32), ("B", C.c_int32), ("dt", C.c_double), ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p),
                 ("d_required", C.c_void_p), ("d_last_unclear", C.c_void_p), ("d_commit", C.c_void_p)]
+
+
+# FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES: 4 bytes per threshold (C * T) and 8 per level of one fo_scene_hidden_brake_ladder_users call
+HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES = 3584
+
+
+class HiddenBrakeLadderUsers(C.Structure):      # fo_hidden_brake_ladder_users_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
+                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
+                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
+                ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
+                ("h_thr", C.POINTER(C.c_int32)), ("d_required", C.c_void_p), ("d_last_unclear", C.c_void_p), ("d_commit", C.c_void_p),
+                ("d_first", C.c_void_p), ("d_required_all", C.c_void_p), ("d_last_unclear_all", C.c_void_p), ("d_blocking", C.c_void_p),
+                ("d_brake_first_or_null", C.c_void_p), ("d_stop_or_null", C.c_void_p)]
 
 
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
@@ -281,6 +299,7 @@ def load():
     lib.fo_scene_hidden_brake_classes.argtypes = [vp, C.POINTER(HiddenBrakeClasses), vp]
     lib.fo_scene_hidden_brake_users.argtypes = [vp, C.POINTER(HiddenBrakeUsers), vp]
     lib.fo_scene_hidden_brake_ladder.argtypes = [vp, C.POINTER(HiddenBrakeLadder), vp]
+    lib.fo_scene_hidden_brake_ladder_users.argtypes = [vp, C.POINTER(HiddenBrakeLadderUsers), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -1,6 +1,6 @@
 """Hidden traffic (an extension): the reach forecast for one speed, the clearance that serves every speed up to
-a cap, the witnesses, and the brake clearance with its siblings (by classes, by road users, at a ladder of decelerations).  The
-functions that take ``self`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods."""
+a cap, the witnesses, and the brake clearance with its siblings (by classes, by road users, at a ladder of decelerations, and the
+ladder by road users).  The functions that take ``self`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods."""
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -550,6 +550,30 @@ class HiddenBrakeLadder:
         return (self.required == self.last_unclear + 1) | (self.required == -1)
 
 
+def _ladder_levels(decelerations, fn):
+    """the ladder of ``fn`` (hidden_brake_ladder and its sibling by road users) as float64 ``[L]``, or its refusal"""
+    levels = np.zeros(0)                                   # (what is no 1-D sequence of numbers is refused as an empty ladder is)
+    if not isinstance(decelerations, (str, bytes)) and np.ndim(decelerations) == 1:
+        try:
+            levels = np.array([float(a) for a in decelerations], dtype=np.float64)
+        except (TypeError, ValueError):
+            pass
+    if not 1 <= len(levels) <= N.HIDDEN_BRAKE_MAX_LEVELS or not (np.isfinite(levels) & (levels >= 0.0)).all():
+        raise ValueError(f"{fn}: decelerations must hold 1 .. {N.HIDDEN_BRAKE_MAX_LEVELS} finite values >= 0")
+    if not (np.diff(levels) > 0.0).all():
+        raise ValueError(f"{fn}: decelerations must be strictly ascending (required is then the gentlest clear one)")
+    return levels
+
+
+def _ladder_starts(starts, T, fn):
+    """the number of brake starts of ``fn``: ``starts``, an integer in ``[1, T]``, None = T"""
+    if starts is None:
+        starts = T
+    if isinstance(starts, bool) or not isinstance(starts, (int, np.integer)) or not 1 <= int(starts) <= T:
+        raise ValueError(f"{fn}: starts = {starts!r}, an integer in [1, T = {T}] or None")
+    return int(starts)
+
+
 def hidden_brake_ladder(self, x, y, theta, v, *, vehicle, v_max, dt, decelerations, starts=None, margin=None, inflate=0.0, lengths=None,
                         metric="euclid", flow="any"):
     """Hidden-traffic brake ladder (``fo_scene_hidden_brake_ladder``; DESIGN.md §5.10 "Brake ladder"): runs ``hidden_reach(...)``
@@ -564,21 +588,8 @@ def hidden_brake_ladder(self, x, y, theta, v, *, vehicle, v_max, dt, deceleratio
     M, T = (int(a) for a in tx.shape)
     if tuple(v.shape) != (M, T):
         raise ValueError("hidden_brake_ladder: v must be [M, T]")
-    levels = np.zeros(0)                                   # (what is no 1-D sequence of numbers is refused as an empty ladder is)
-    if not isinstance(decelerations, (str, bytes)) and np.ndim(decelerations) == 1:
-        try:
-            levels = np.array([float(a) for a in decelerations], dtype=np.float64)
-        except (TypeError, ValueError):
-            pass
-    if not 1 <= len(levels) <= N.HIDDEN_BRAKE_MAX_LEVELS or not (np.isfinite(levels) & (levels >= 0.0)).all():
-        raise ValueError(f"hidden_brake_ladder: decelerations must hold 1 .. {N.HIDDEN_BRAKE_MAX_LEVELS} finite values >= 0")
-    if not (np.diff(levels) > 0.0).all():
-        raise ValueError("hidden_brake_ladder: decelerations must be strictly ascending (required is then the gentlest clear one)")
-    if starts is None:
-        starts = T
-    if isinstance(starts, bool) or not isinstance(starts, (int, np.integer)) or not 1 <= int(starts) <= T:
-        raise ValueError(f"hidden_brake_ladder: starts = {starts!r}, an integer in [1, T = {T}] or None")
-    B, K = int(starts), len(levels)
+    levels = _ladder_levels(decelerations, "hidden_brake_ladder")
+    B, K = _ladder_starts(starts, T, "hidden_brake_ladder"), len(levels)
     dev, w = self.device, reach.window
     tv = N.on_device(v, dev)
     arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
@@ -738,42 +749,41 @@ class HiddenBrakeUsers:
         return sp[self.critical_user()]
 
 
-def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, margin=None, inflate=0.0, lengths=None, heading=None):
-    """Hidden-traffic brake clearance for mixed road users in one walk (``fo_scene_hidden_brake_users``; DESIGN.md §5.10 "Brake
-    clearance by road users"): ``users`` is a sequence of 1 .. 8 ``(speed, metric, flow)`` -- say ``(2.0, "road", "any")`` for a
-    pedestrian, ``(7.0, "road", "lanes")`` for a cyclist and ``(13.9, "road", "lanes")`` for a car.  Runs one
-    ``hidden_clearance`` per distinct ``(metric, flow)`` (``v_cap`` = the fastest of its users; the first call's heading tensor and
-    device inputs go to the later ones, so there is one host-side heading pass) and then ONE launch that walks the manoeuvre of every
-    (candidate, b) once and decides it for every user on that user's key map; returns a :class:`HiddenBrakeUsers`.
-    ``len(users) * T`` may not exceed ``_native.HIDDEN_BRAKE_MAX_TABLE``.  The other arguments as for :meth:`hidden_brake_classes`.
-    Nothing is read back and nobody waits for the kernels."""
+def _road_users(users, x, fn):
+    """the users of ``fn`` (hidden_brake_users and its ladder) as a tuple of ``(float speed, metric, flow)``, or its refusal"""
     try:
         users = tuple(users)
     except TypeError:
         users = ()
     if not 1 <= len(users) <= N.HIDDEN_BRAKE_MAX_CLASSES:
-        raise ValueError(f"hidden_brake_users: users must hold 1 .. {N.HIDDEN_BRAKE_MAX_CLASSES} triples (speed, metric, flow)")
+        raise ValueError(f"{fn}: users must hold 1 .. {N.HIDDEN_BRAKE_MAX_CLASSES} triples (speed, metric, flow)")
     for c, u in enumerate(users):
         try:
             s, m, f = u
             s = float(s)
         except (TypeError, ValueError):
-            raise ValueError(f"hidden_brake_users: users[{c}] = {u!r} is no triple (speed, metric, flow) with a number for the speed") from None
+            raise ValueError(f"{fn}: users[{c}] = {u!r} is no triple (speed, metric, flow) with a number for the speed") from None
     users = tuple((float(s), m, f) for s, m, f in users)
     for c, (s, m, f) in enumerate(users):
         if m not in HIDDEN_REACH_METRICS:
-            raise ValueError(f"hidden_brake_users: users[{c}]: metric {m!r}, one of {HIDDEN_REACH_METRICS} is possible")
+            raise ValueError(f"{fn}: users[{c}]: metric {m!r}, one of {HIDDEN_REACH_METRICS} is possible")
         if f not in HIDDEN_REACH_FLOWS:
-            raise ValueError(f"hidden_brake_users: users[{c}]: flow {f!r}, one of {HIDDEN_REACH_FLOWS} is possible")
+            raise ValueError(f"{fn}: users[{c}]: flow {f!r}, one of {HIDDEN_REACH_FLOWS} is possible")
         if f == "lanes" and m != "road":
-            raise ValueError(f"hidden_brake_users: users[{c}]: flow 'lanes' follows the lanes along the road: it needs metric 'road', "
+            raise ValueError(f"{fn}: users[{c}]: flow 'lanes' follows the lanes along the road: it needs metric 'road', "
                              f"not {m!r}")
     if not all(math.isfinite(s) and s >= 0.0 for s, _, _ in users):
-        raise ValueError("hidden_brake_users: the users' speeds must be finite and >= 0")
+        raise ValueError(f"{fn}: the users' speeds must be finite and >= 0")
     T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
     if len(users) * T > N.HIDDEN_BRAKE_MAX_TABLE:
-        raise ValueError(f"hidden_brake_users: {len(users)} users x {T} samples = {len(users) * T} thresholds, at most "
+        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds, at most "
                          f"{N.HIDDEN_BRAKE_MAX_TABLE} are possible (they travel as a kernel argument)")
+    return users
+
+
+def _users_clearances(self, users, x, y, theta, *, vehicle, dt, margin, inflate, lengths, heading):
+    """``(maps, map_of, clearances)``: one ``hidden_clearance`` per distinct ``(metric, flow)`` of ``users`` in order of first
+    appearance, each at the fastest of its users; the first call's device inputs and heading tensor go to the later ones"""
     maps = []                                               # the distinct (metric, flow) in order of first appearance: at most three
     for _, m, f in users:
         if (m, f) not in maps:
@@ -786,6 +796,21 @@ def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, mar
         clearances.append(hidden_clearance(self, cx, cy, theta, vehicle=vehicle, v_cap=v_cap, dt=dt, margin=margin, inflate=inflate,
                                            lengths=clen, metric=m, heading=heading, flow=f))
         cx, cy, heading, clen = self._hc_inputs             # the later clearances take the first one's device inputs and headings
+    return maps, map_of, clearances
+
+
+def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, margin=None, inflate=0.0, lengths=None, heading=None):
+    """Hidden-traffic brake clearance for mixed road users in one walk (``fo_scene_hidden_brake_users``; DESIGN.md §5.10 "Brake
+    clearance by road users"): ``users`` is a sequence of 1 .. 8 ``(speed, metric, flow)`` -- say ``(2.0, "road", "any")`` for a
+    pedestrian, ``(7.0, "road", "lanes")`` for a cyclist and ``(13.9, "road", "lanes")`` for a car.  Runs one
+    ``hidden_clearance`` per distinct ``(metric, flow)`` (``v_cap`` = the fastest of its users; the first call's heading tensor and
+    device inputs go to the later ones, so there is one host-side heading pass) and then ONE launch that walks the manoeuvre of every
+    (candidate, b) once and decides it for every user on that user's key map; returns a :class:`HiddenBrakeUsers`.
+    ``len(users) * T`` may not exceed ``_native.HIDDEN_BRAKE_MAX_TABLE``.  The other arguments as for :meth:`hidden_brake_classes`.
+    Nothing is read back and nobody waits for the kernels."""
+    users = _road_users(users, x, "hidden_brake_users")
+    maps, map_of, clearances = _users_clearances(self, users, x, y, theta, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
+                                                 lengths=lengths, heading=heading)
     tx, ty, thead, tlen = self._hc_inputs
     M, T = (int(a) for a in tx.shape)
     if tuple(v.shape) != (M, T):
@@ -819,3 +844,136 @@ def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, mar
     # (stay referenced until the next call, as in hidden_brake_classes -- the clearances' maps too: the caller may drop the result)
     self._hbu_inputs = (tv, arc, tuple(clearances))
     return HiddenBrakeUsers(tuple(clearances), users, map_of, thr, brake_first, stop, commit, first, arc, a_brake, float(dt), tlen)
+
+
+@dataclass
+class HiddenBrakeLadderUsers:
+    """what :meth:`SensorModel.hidden_brake_ladder_users` returns (DESIGN.md §5.10 "Brake ladder by road users"): ``clearances``,
+    ``users``, ``map_of`` and ``thr`` as in :class:`HiddenBrakeUsers`, ``decelerations`` (host float64 ``[L]``, strictly ascending) the
+    ladder, and (device tensors, int32) per user ``required [C, M, B]``, ``last_unclear [C, M, B]``, ``commit [C, M, L]`` -- row c is
+    what :class:`HiddenBrakeLadder` holds against that user's forecast -- and ``first [C, M]``; over the users ``required_all [M, B]``
+    -- the first level at which "follow candidate m until sample b, then brake" stays clear of EVERY user while it moves, -1 = no
+    level of the ladder does --, ``last_unclear_all [M, B]`` -- the last level at which some user is not clear, -1 = none -- and
+    ``blocking [M, B]``, a bit mask: bit c is set iff user c is unclear at level ``required_all - 1`` (at the last level where
+    ``required_all`` is -1; 0 where it is 0) -- the users that keep the ego from the next gentler level.  All four are -1 (``blocking``
+    0) where there is no manoeuvre (``b >= lengths[m]``).  With ``detail``: ``brake_first [C, M, B, L]`` and ``stop [M, B, L]`` -- slice
+    l is ``hidden_brake_users(a_brake=decelerations[l])`` at the brake starts ``b < B``, bit for bit --, else both None.  ``arc``,
+    ``dt``, ``lengths`` as in :class:`HiddenBrake`.
+
+    Not claimed: what :class:`HiddenBrakeUsers` and :class:`HiddenBrakeLadder` do not claim.  ``required_all`` is NOT the maximum of
+    the users' ``required``: harder braking is not always safer against a map, so the first level clear of every user can lie above
+    every single user's own."""
+    clearances: tuple
+    users: tuple
+    map_of: tuple
+    thr: np.ndarray
+    decelerations: np.ndarray
+    required: torch.Tensor
+    last_unclear: torch.Tensor
+    commit: torch.Tensor
+    first: torch.Tensor
+    required_all: torch.Tensor
+    last_unclear_all: torch.Tensor
+    blocking: torch.Tensor
+    brake_first: Optional[torch.Tensor]
+    stop: Optional[torch.Tensor]
+    arc: torch.Tensor
+    dt: float
+    lengths: Optional[torch.Tensor] = None
+
+    def _pair(self, user):
+        if user is None:
+            return self.required_all, self.last_unclear_all
+        return self.required[user], self.last_unclear[user]
+
+    def required_deceleration(self, user=None):
+        """``[M, B]`` float64 (m/s^2): ``decelerations[required_all]`` -- of ``required[user]`` with ``user`` --; ``+inf`` where a
+        manoeuvre exists and no level of the ladder is clear; ``nan`` where there is no manoeuvre.  Torch ops on the tensors' device,
+        nothing is read back."""
+        required, last_unclear = self._pair(user)
+        dev = required.device
+        levels = torch.as_tensor(np.append(np.asarray(self.decelerations, dtype=np.float64), np.inf), device=dev)
+        req = required.to(torch.int64)
+        out = levels[torch.where(req >= 0, req, len(levels) - 1)]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        return torch.where((req < 0) & (last_unclear < 0), nan, out)
+
+    def brake_threat_number(self, a_max, user=None):
+        """``[M, B]`` float64: :meth:`required_deceleration` divided by ``a_max`` -- the reference's ``break_threat_number``
+        (metrics/be.py:56) against the hidden road users, or one of them"""
+        return self.required_deceleration(user) / float(a_max)
+
+    def monotone(self, user=None):
+        """``[M, B]`` bool, as :meth:`HiddenBrakeLadder.monotone`, over all users or for one"""
+        required, last_unclear = self._pair(user)
+        return (required == last_unclear + 1) | (required == -1)
+
+    def blocking_users(self):
+        """``[C, M, B]`` bool: bit c of ``blocking``"""
+        bits = torch.arange(len(self.users), dtype=torch.int32, device=self.blocking.device).reshape(-1, 1, 1)
+        return (self.blocking.unsqueeze(0) >> bits & 1) != 0
+
+    def level(self, l):
+        """``(brake_first [C, M, B], stop [M, B], commit [C, M])`` of level l: what ``hidden_brake_users(a_brake=decelerations[l])``
+        gives at the brake starts ``b < B`` (views, nothing is copied); needs ``detail``"""
+        if self.brake_first is None:
+            raise ValueError("HiddenBrakeLadderUsers.level: brake_first and stop were not asked for (detail=True)")
+        return self.brake_first[..., l], self.stop[..., l], self.commit[..., l]
+
+
+def hidden_brake_ladder_users(self, x, y, theta, v, *, vehicle, users, dt, decelerations, starts=None, detail=False, margin=None,
+                              inflate=0.0, lengths=None, heading=None):
+    """Hidden-traffic brake ladder for mixed road users in one walk (``fo_scene_hidden_brake_ladder_users``; DESIGN.md §5.10 "Brake
+    ladder by road users"): ``users`` as for :meth:`hidden_brake_users`, ``decelerations`` and ``starts`` as for
+    :meth:`hidden_brake_ladder`.  Runs one ``hidden_clearance`` per distinct ``(metric, flow)`` as :meth:`hidden_brake_users` does and
+    then ONE launch that walks the manoeuvre of every (candidate, b, deceleration) once and decides it for every user on that user's
+    key map; returns a :class:`HiddenBrakeLadderUsers`, whose ``required_all`` is the gentlest deceleration of the ladder that keeps
+    the moving ego clear of every user.  ``detail``: also ``brake_first [C, M, B, L]`` and ``stop [M, B, L]`` (4 (C + 1) M B L bytes).
+    ``4 * len(users) * T + 8 * len(decelerations)`` may not exceed ``_native.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES``.  Nothing is read
+    back and nobody waits for the kernels."""
+    fn = "hidden_brake_ladder_users"
+    users = _road_users(users, x, fn)
+    levels = _ladder_levels(decelerations, fn)
+    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
+    if 4 * len(users) * T + 8 * len(levels) > N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES:
+        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds of 4 bytes and {len(levels)} decelerations "
+                         f"of 8 bytes are {4 * len(users) * T + 8 * len(levels)} bytes, at most "
+                         f"{N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES} are possible (they travel as a kernel argument)")
+    maps, map_of, clearances = _users_clearances(self, users, x, y, theta, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
+                                                 lengths=lengths, heading=heading)
+    tx, ty, thead, tlen = self._hc_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T):
+        raise ValueError(f"{fn}: v must be [M, T]")
+    B = _ladder_starts(starts, T, fn)
+    first_c = clearances[0]
+    dev, w, C_, K_, L_ = self.device, first_c.window, len(users), len(maps), len(levels)
+    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    tv = N.on_device(v, dev)
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    arc = N.on_device(arc, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    required, last_unclear, commit, first = new(C_, M, B), new(C_, M, B), new(C_, M, L_), new(C_, M)
+    required_all, last_unclear_all, blocking = new(M, B), new(M, B), new(M, B)
+    brake_first, stop = (new(C_, M, B, L_), new(M, B, L_)) if detail else (None, None)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
+    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
+    args = N.HiddenBrakeLadderUsers(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
+                                    hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0,
+                                    win_nx=w.nx, win_ny=w.ny, K=K_, C=C_,
+                                    d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                    d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                    r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
+                                    map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(arc),
+                                    h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B, dt=float(dt),
+                                    h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), d_required=N.ptr(required),
+                                    d_last_unclear=N.ptr(last_unclear), d_commit=N.ptr(commit), d_first=N.ptr(first),
+                                    d_required_all=N.ptr(required_all), d_last_unclear_all=N.ptr(last_unclear_all),
+                                    d_blocking=N.ptr(blocking), d_brake_first_or_null=N.ptr(brake_first), d_stop_or_null=N.ptr(stop))
+    self.ctx.call("fo_scene_hidden_brake_ladder_users", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_users)
+    self._hblu_inputs = (tv, arc, tuple(clearances))
+    return HiddenBrakeLadderUsers(tuple(clearances), users, map_of, thr, levels, required, last_unclear, commit, first, required_all,
+                                  last_unclear_all, blocking, brake_first, stop, arc, float(dt), tlen)

@@ -66,6 +66,18 @@ def occlusion_memory_vehicles(acc):
     return vehicles
 
 
+def _default_brake_ladder(a_max, fn):
+    """the default ladder of ``fn`` (hidden_brake_ladder and hidden_brake_ladder_users): 0.5, 1.0, ... up to ``a_max``, with ``a_max``
+    itself appended if it is not on that grid"""
+    a_max = float(a_max)
+    n = int(a_max // 0.5) if 0.5 <= a_max < float("inf") else 0      # levels on the 0.5 grid
+    on_grid = n > 0 and 0.5 * n == a_max
+    if n + (not on_grid) > N.HIDDEN_BRAKE_MAX_LEVELS:
+        raise ValueError(f"{fn}: the default ladder 0.5, 1.0, ... up to a_max = {a_max} m/s^2 has more than "
+                         f"{N.HIDDEN_BRAKE_MAX_LEVELS} levels (hand decelerations over)")
+    return [0.5 * (k + 1) for k in range(n)] + ([] if on_grid else [a_max])
+
+
 class FOInterface:
     def __init__(self, scenario, reference_path, vehicle_params, dt, config_path=None, cosy_cl=None, share_map_with=None):
         """Signature of the reference (interface.py:69) plus ``share_map_with``: another FOInterface of the same scenario
@@ -430,13 +442,7 @@ class FOInterface:
             raise RuntimeError("hidden_brake_ladder needs a previous evaluate_scenario")
         vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
         if decelerations is None:
-            a_max = float(vt[4])
-            n = int(a_max // 0.5) if 0.5 <= a_max < float("inf") else 0      # levels on the 0.5 grid
-            on_grid = n > 0 and 0.5 * n == a_max
-            if n + (not on_grid) > N.HIDDEN_BRAKE_MAX_LEVELS:
-                raise ValueError(f"hidden_brake_ladder: the default ladder 0.5, 1.0, ... up to a_max = {a_max} m/s^2 has more than "
-                                 f"{N.HIDDEN_BRAKE_MAX_LEVELS} levels (hand decelerations over)")
-            decelerations = [0.5 * (k + 1) for k in range(n)] + ([] if on_grid else [a_max])
+            decelerations = _default_brake_ladder(vt[4], "hidden_brake_ladder")
         arr = trajectories_to_arrays(trajectories)
         om = self.occlusion_memory
         return self.sensor_model.hidden_brake_ladder(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3],
@@ -481,6 +487,28 @@ class FOInterface:
         return self.sensor_model.hidden_brake_users(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], users=users,
                                                     margin=om["margin"] if margin is None else margin, dt=self.dt,
                                                     a_brake=vt[4] if a_brake is None else a_brake, inflate=inflate)
+
+    def hidden_brake_ladder_users(self, trajectories, users, decelerations=None, starts=None, detail=False, margin=None, inflate=0.0):
+        """EXTENSION, not part of the reference: the brake threat number of :meth:`hidden_brake_ladder` against hidden road users that
+        do not share a forecast -- ``users`` as for :meth:`hidden_brake_users` -- from one clearance per distinct ``(metric, flow)``
+        and ONE walk of every braking manoeuvre at every deceleration (:meth:`SensorModel.hidden_brake_ladder_users`; returns its
+        :class:`~frenetix_occlusion.sensor_model.HiddenBrakeLadderUsers`: ``required_all``, ``last_unclear_all``, ``blocking [M, B]``,
+        per user ``required``, ``last_unclear [C, M, B]``, ``commit [C, M, L]``, ``first [C, M]``; ``.required_deceleration(user)``,
+        ``.brake_threat_number(a_max, user)``, ``.monotone(user)``, ``.blocking_users()``; with ``detail`` also ``brake_first`` and
+        ``stop``).  ``decelerations`` and ``starts`` default as for :meth:`hidden_brake_ladder`, the rest as for
+        :meth:`hidden_brake_users`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_ladder_users needs a previous evaluate_scenario")
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        if decelerations is None:
+            decelerations = _default_brake_ladder(vt[4], "hidden_brake_ladder_users")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        return self.sensor_model.hidden_brake_ladder_users(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], users=users,
+                                                           margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                           decelerations=decelerations, starts=starts, detail=detail, inflate=inflate)
 
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the

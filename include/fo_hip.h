@@ -764,6 +764,75 @@ typedef struct {
 } fo_hidden_brake_ladder_t;
 int fo_scene_hidden_brake_ladder(fo_ctx *ctx, const fo_hidden_brake_ladder_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic BRAKE LADDER BY ROAD USERS (DESIGN.md §5.10 "Brake ladder by road users") --
+ * the brake ladder above for hidden road users that do not share a forecast: per candidate and brake start the first level of a
+ * ladder of L decelerations at which the moving ego stays clear of EVERY class of road user, each class held against the key map it
+ * names, from ONE launch that walks every manoeuvre (m, b, level) once for all classes.  Harder braking is not always safer against
+ * a map, so that level can lie above every single class's own: it is not a maximum over per-class ladders.  Opt-in and additive:
+ * one launch, nothing is read back, no other output changes.
+ *  Inputs: those of fo_scene_hidden_brake_users word for word -- K maps with d_key[k], d_qmin[k], r2_cap[k]; C classes, map_of[c],
+ *   the host table h_thr [C][T]; trajectories, headings, d_len_or_null, extents and window; d_v, d_arc, dt -- and in place of
+ *   a_brake: h_levels [L], float64 on the HOST, read during the call (they travel as a kernel argument, with the table),
+ *   1 <= L <= FO_HIDDEN_BRAKE_MAX_LEVELS, every level finite and >= 0, in any order, repeats allowed; B, the number of brake starts
+ *   considered, b = 0 .. B-1, 1 <= B <= T.  4 * C * T + 8 * L <= FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES.
+ *  For trajectory m, brake start b < B, level l and class c with k = map_of[c]:
+ *  1. Steps 1 - 5 of fo_scene_hidden_brake_users word for word with a_brake = levels[l]: stop[m][b][l] (the same for every class) and
+ *   brake_first[c][m][b][l], both -1 where b >= Lm; first[c][m], which does not depend on the level.
+ *  2. unclear(c, m, b, l) iff 0 <= first[c][m] <= b or 0 <= brake_first[c][m][b][l] < stop[m][b][l].
+ *  3. Per class, for b < Lm: required[c][m][b] = the smallest l that is not unclear, -1 if every level is unclear;
+ *   last_unclear[c][m][b] = the largest unclear l, -1 if none is; commit[c][m][l] = the smallest b < min(B, Lm) with
+ *   unclear(c, m, b, l), -1 = none.
+ *  4. Over the classes, for b < Lm: required_all[m][b] = the smallest l at which NO class is unclear, -1 if there is none;
+ *   last_unclear_all[m][b] = the largest l at which some class is unclear, -1 if there is none; blocking[m][b] = a bit mask, bit c
+ *   set iff class c is unclear at level required_all - 1 -- at level L - 1 where required_all = -1, and 0 where required_all = 0:
+ *   the classes that keep the ego from the next gentler level.
+ *  5. For b >= Lm required, last_unclear, required_all and last_unclear_all are -1 and blocking is 0: "no manoeuvre".
+ *  Outputs, int32, every byte of every buffer handed over written by every call: d_required, d_last_unclear [C][M][B]; d_commit
+ *   [C][M][L]; d_first [C][M]; d_required_all, d_last_unclear_all, d_blocking [M][B]; the detail d_brake_first_or_null
+ *   [C][M][B][L] and d_stop_or_null [M][B][L]: both given or both null.
+ *  The ties: slice l of brake_first and stop, and first, equal bit for bit what fo_scene_hidden_brake_users gives with
+ *   a_brake = levels[l] at the brake starts b < B, commit[c][.][l] is that entry's commit where it is < B, else -1; row c of
+ *   required, last_unclear and commit is what fo_scene_hidden_brake_ladder gives on the arrival map of class c's forecast.
+ *  Safety of the data: as fo_scene_hidden_brake_users; the levels may hold anything the refusals let through, no index depends
+ *   on them.
+ *  Not claimed: what fo_scene_hidden_brake_users and fo_scene_hidden_brake_ladder do not claim; one ladder serves every class.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_ladder_users:"), in this order: K outside [1, 3]; C outside [1, 8]; no h_thr; a window outside
+ * [1, 32768]^2; an r2_cap[k], k < K, negative or beyond FO_HIDDEN_REACH_MAX_HALO; map_of[c], c < C, outside [0, K); M < 0; L outside
+ * [1, 64]; no h_levels; a level negative or not finite; dt not positive and finite; with M > 0: T outside [1, 254]; B outside
+ * [1, T]; C * T > FO_HIDDEN_BRAKE_MAX_TABLE; 4 * C * T + 8 * L > FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES; a row that is negative,
+ * decreases or ends beyond 169 * r2_cap[map_of[c]]; no d_x / d_y / d_heading; no d_key[k] or d_qmin[k], k < K; no d_v or d_arc; a
+ * missing output; one detail buffer without the other; extents refused as by fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+#define FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES 3584
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  const double *h_levels;                   /* HOST [L] decelerations, m/s^2 */
+  int32_t L;                                /* levels */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  double dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  int32_t *d_required, *d_last_unclear;     /* [C][M][B] */
+  int32_t *d_commit;                        /* [C][M][L] */
+  int32_t *d_first;                         /* [C][M] */
+  int32_t *d_required_all, *d_last_unclear_all, *d_blocking;   /* [M][B] */
+  int32_t *d_brake_first_or_null;           /* [C][M][B][L] the detail: both or neither */
+  int32_t *d_stop_or_null;                  /* [M][B][L] */
+} fo_hidden_brake_ladder_users_t;
+int fo_scene_hidden_brake_ladder_users(fo_ctx *ctx, const fo_hidden_brake_ladder_users_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

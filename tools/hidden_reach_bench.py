@@ -5,6 +5,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
                                        [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...] [--brake-ladder K]
+                                       [--brake-ladder-users]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -35,6 +36,13 @@ the per-forecast walks scan.
 at the vehicle's ``a_max`` = 11.5 is the interface's default ladder 0.5, 1.0, ...) from every brake start (§5.10 "Brake ladder") --
 the forecast plus ONE launch -- next to K ``hidden_brake`` calls in the same process; every level's slice is compared with that
 call's (exact integers); also the poses the ladder scanned, the histogram of ``required`` and the non-monotone pairs.
+
+``--brake-ladder-users``: ``hidden_brake_ladder_users`` for the README's road users -- 2.0 road/any, 7.0 road/lanes, 13.9 road/lanes --
+at the interface's default ladder 0.5, 1.0, ... 11.5 from every brake start (§5.10 "Brake ladder by road users"): the clearances plus
+ONE launch, with the detail and without it, next to one ``hidden_brake_ladder`` call per user in the same process.  In every run both
+ties are asserted (exact integers): every level's slice is ``hidden_brake_users`` at that deceleration, every user's rows are
+``hidden_brake_ladder`` on that user's forecast.  Also the pairs whose ``required_all`` lies above every user's own ``required``
+and how ``blocking`` is spread over the users.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -88,6 +96,8 @@ def main():
                     help="time hidden_brake_users for these hidden road users next to one hidden_brake_classes call per forecast")
     ap.add_argument("--brake-ladder", type=int, default=None, metavar="K",
                     help="time hidden_brake_ladder at K decelerations up to the one of --brake next to K hidden_brake calls")
+    ap.add_argument("--brake-ladder-users", action="store_true",
+                    help="time hidden_brake_ladder_users for the README's three road users next to one hidden_brake_ladder call per user")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -254,6 +264,42 @@ def main():
         res["pairs_without_a_clear_level_unblocked"] = int(((req < 0) & ~blocked).sum())
         res["non_monotone_pairs"] = int((~l_out.monotone()).sum())
         res["non_monotone_required_below_last_unclear"] = int(((req >= 0) & (req < lu)).sum())
+    if a.brake_ladder_users:
+        users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
+        levels = np.array([0.5 * (k + 1) for k in range(23)])          # FOInterface's default ladder at a_max = 11.5
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hblu = lambda **kw: sm.hidden_brake_ladder_users(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, decelerations=levels, **kw)
+        per_user = lambda: [sm.hidden_brake_ladder(tx, ty, tth, tv, vehicle=veh, v_max=s, dt=0.1, decelerations=levels, metric=m, flow=f)
+                            for s, m, f in users]
+        d_out, s_out, ladders = hblu(detail=True), hblu(), per_user()
+        for k in ("required", "last_unclear", "commit", "first", "required_all", "last_unclear_all", "blocking"):
+            assert torch.equal(getattr(d_out, k), getattr(s_out, k)), k         # the detail changes nothing else
+        for n, lv in enumerate(levels):             # the tie by levels: every slice is hidden_brake_users at that deceleration
+            one = sm.hidden_brake_users(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=float(lv), heading=d_out.clearances[0].heading)
+            bf_n, st_n, cm_n = d_out.level(n)
+            assert torch.equal(bf_n, one.brake_first) and torch.equal(st_n, one.stop) and torch.equal(cm_n, one.commit), float(lv)
+            assert torch.equal(d_out.first, one.first), float(lv)
+        for c, one in enumerate(ladders):           # the tie by users: every row is hidden_brake_ladder on that user's forecast
+            assert torch.equal(d_out.required[c], one.required) and torch.equal(d_out.last_unclear[c], one.last_unclear), users[c]
+            assert torch.equal(d_out.commit[c], one.commit) and torch.equal(d_out.brake_first[c], one.brake_first), users[c]
+            assert torch.equal(d_out.stop, one.stop) and torch.equal(d_out.first[c], one.reach.first), users[c]
+        res["brake_ladder_users"] = [list(u) for u in users]
+        res["brake_ladder_users_levels"] = [float(lv) for lv in levels]
+        res["brake_ladder_users_call_ms"] = _median_ms(hblu, a.calls)
+        res["brake_ladder_users_call_detail_ms"] = _median_ms(lambda: hblu(detail=True), a.calls)
+        res["brake_ladder_users_call_reused_heading_ms"] = _median_ms(lambda: hblu(heading=d_out.clearances[0].heading), a.calls)
+        res["hidden_brake_ladder_call_per_user_ms"] = _median_ms(per_user, a.calls)
+        req, ra, blocking = (t.cpu().numpy().astype(np.int64) for t in (s_out.required, s_out.required_all, s_out.blocking))
+        own = np.where(req < 0, len(levels), req)
+        above = (req >= 0).all(axis=0) & (np.where(ra < 0, len(levels), ra) > own.max(axis=0))
+        res["pairs"] = int(M * T)
+        res["pairs_required_all_above_every_user"] = int(above.sum())
+        res["pairs_required_all_above_the_users_maximum"] = int((np.where(ra < 0, len(levels), ra) > own.max(axis=0)).sum())
+        res["required_all_histogram"] = {str(k): int((ra == k).sum()) for k in range(-1, len(levels))}
+        res["non_monotone_pairs_all_users"] = int((~s_out.monotone()).sum())
+        res["non_monotone_pairs_per_user"] = [int((~s_out.monotone(c)).sum()) for c in range(len(users))]
+        res["pairs_blocked_by_user"] = [int((blocking >> c & 1).sum()) for c in range(len(users))]
+        res["pairs_by_blocking_mask"] = {format(k, "03b"): int((blocking == k).sum()) for k in range(1 << len(users))}
     if a.clearance:
         speeds = (2.0, 7.0, a.v_max)
         hc = lambda **kw: sm.hidden_clearance(tx, ty, tth, vehicle=veh, v_cap=a.v_max, dt=0.1, metric=a.metric, flow=a.flow, **kw)
