@@ -134,6 +134,32 @@ inline size_t brake_ladder_users_lds_bound() {
   return (one > (size_t)BRAKE_LADDER_ROWS_BYTES ? one : (size_t)BRAKE_LADDER_ROWS_BYTES) + BRAKE_LADDER_USERS_MAX_ARG_BYTES +
          (size_t)BRAKE_LADDER_USERS_MAX_CLASSES * HB_THREADS * sizeof(int32_t);
 }
+// the pose preparation of the fail-safe verdict: a lane per trajectory (its arc is a serial sum), 64 trajectories per workgroup
+constexpr int POSES_THREADS = 64;
+inline int poses_blocks(int M) { return (int)(((int64_t)M + POSES_THREADS - 1) / POSES_THREADS); }
+// the fail-safe verdict: the users kernel's lanes over the first B brake starts only -- a lane per (m, b), b < B (b = lane,
+// lane + G, ..), G = the power of two >= min(B, 64) lanes per trajectory, all in one wave.  A workgroup serves HB_THREADS / G
+// trajectories, or fewer where their rows (the users kernel's: T * (48 + 4 K) bytes each) would exceed BRAKE_LADDER_ROWS_BYTES: the
+// lanes' rule alone would stage 256 trajectories at B = 1, 3.9 MB at T = 254, K = 3.  The lanes beyond per_block * G take part in
+// the staging and then have no trajectory.  Behind the rows stands the table (4 C T bytes).  brake_verdict_lds_bound: no call needs
+// more -- a single trajectory takes at most 254 * 60 bytes, under the rows' bound
+inline int brake_verdict_group(int B) { int G = 1; while (G < B && G < 64) G <<= 1; return G; }
+inline int brake_verdict_per_block(int T, int K, int B) {
+  const size_t per_traj = (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t));
+  const int by_lanes = HB_THREADS / brake_verdict_group(B);
+  const int by_rows = (int)((size_t)BRAKE_LADDER_ROWS_BYTES / per_traj);
+  const int p = by_lanes < by_rows ? by_lanes : by_rows;
+  return p < 1 ? 1 : p;
+}
+inline int brake_verdict_blocks(int M, int T, int K, int B) {
+  const int p = brake_verdict_per_block(T, K, B);
+  return (int)(((int64_t)M + p - 1) / p);
+}
+inline size_t brake_verdict_lds_bytes(int T, int K, int C, int B) {
+  return (size_t)brake_verdict_per_block(T, K, B) * (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t)) +
+         (size_t)C * (size_t)T * sizeof(int32_t);
+}
+inline size_t brake_verdict_lds_bound() { return (size_t)BRAKE_LADDER_ROWS_BYTES + BRAKE_USERS_MAX_TABLE * sizeof(int32_t); }
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -1,6 +1,7 @@
 """Hidden traffic (an extension): the reach forecast for one speed, the clearance that serves every speed up to
 a cap, the witnesses, and the brake clearance with its siblings (by classes, by road users, at a ladder of decelerations, and the
-ladder by road users).  The functions that take ``self`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods."""
+ladder by road users), the device pose preparation and the fail-safe verdict that folds into a step's cost rows.  The functions
+that take ``self`` are :class:`~frenetix_occlusion.sensor_model.SensorModel`'s methods."""
 import ctypes as C
 import math
 from dataclasses import dataclass
@@ -977,3 +978,133 @@ def hidden_brake_ladder_users(self, x, y, theta, v, *, vehicle, users, dt, decel
     self._hblu_inputs = (tv, arc, tuple(clearances))
     return HiddenBrakeLadderUsers(tuple(clearances), users, map_of, thr, levels, required, last_unclear, commit, first, required_all,
                                   last_unclear_all, blocking, brake_first, stop, arc, float(dt), tlen)
+
+
+@dataclass
+class HiddenPoses:
+    """what :meth:`SensorModel.hidden_poses` returns (device tensors; DESIGN.md §5.10 "Fail-safe verdict"): ``heading [M, T, 2]``
+    float64 -- (cos, sin) of the sample headings from one ``sincos`` per sample, the bits the sweep rotates the ego rectangle by;
+    ``arc [M, T]`` float64 -- the travelled chord length as numpy's :func:`travelled_arc` sums it on host arrays (sequentially);
+    ``finite [M]`` uint8 -- 1 iff every x, y, theta, v of the samples ``k < lengths[m]`` is finite.  Hand it to a later call of the
+    SAME candidates as ``poses=``."""
+    heading: torch.Tensor
+    arc: torch.Tensor
+    finite: torch.Tensor
+
+
+def hidden_poses(self, x, y, theta, v, lengths=None):
+    """Device pose preparation (``fo_scene_hidden_poses``): (cos, sin), travelled arc and finite flag of the candidates
+    ``x, y, theta, v [M, T]`` in one launch on the current stream; returns a :class:`HiddenPoses`.  Candidates that live on the device
+    stay there: nothing is copied back and nobody waits (host arrays are uploaded first).  Needs no previous ``launch()``."""
+    fn = "hidden_poses"
+    shape = tuple(x.shape)
+    if len(shape) != 2 or any(tuple(q.shape) != shape for q in (y, theta, v)):
+        raise ValueError(f"{fn}: x, y, theta and v must be [M, T]")
+    M, T = (int(a) for a in shape)
+    if M and not 1 <= T <= N.HIDDEN_REACH_MAX_J:
+        raise ValueError(f"{fn}: {T} samples per trajectory, 1 .. {N.HIDDEN_REACH_MAX_J} are possible")
+    if lengths is not None and tuple(np.shape(lengths)) != (M,):
+        raise ValueError(f"{fn}: lengths must be [M]")
+    dev = self.device
+    tx, ty, tth, tv = (N.on_device(q, dev) for q in (x, y, theta, v))
+    tlen = None if lengths is None else N.on_device(lengths, dev, "int32")
+    heading = torch.empty((M, T, 2), dtype=torch.float64, device=dev)
+    arc = torch.empty((M, T), dtype=torch.float64, device=dev)
+    finite = torch.empty((M,), dtype=torch.uint8, device=dev)
+    args = N.HiddenPoses(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_theta=N.ptr(tth), d_v=N.ptr(tv), d_len_or_null=N.ptr(tlen),
+                         d_heading=N.ptr(heading), d_arc=N.ptr(arc), d_finite=N.ptr(finite))
+    self.ctx.call("fo_scene_hidden_poses", C.byref(args), N.current_stream(self._dev_index))
+    self._hp_inputs = (tx, ty, tth, tv, tlen)               # (stay referenced until the next call, as in hidden_reach)
+    return HiddenPoses(heading, arc, finite)
+
+
+@dataclass
+class HiddenBrakeVerdict:
+    """what :meth:`SensorModel.hidden_brake_verdict` returns (DESIGN.md §5.10 "Fail-safe verdict"; device tensors, int32):
+    ``fail_safe [M]`` -- the number of leading brake starts, of the ``starts`` that were walked, from which braking keeps the moving
+    ego clear of every user (0: not even now; ``starts``: throughout); ``user [M]`` -- the lowest user that ends them, -1 = none,
+    -2 = the candidate has a non-finite pose and fails closed (``fail_safe`` 0); ``commit [C, M]`` -- ``hidden_brake_users``' commit
+    where it is below ``starts``, else -1; ``first [C, M]`` -- that call's ``first``.  ``poses`` the :class:`HiddenPoses` it walked
+    on, ``commit_min`` the bound below which a candidate lost its safety flag, ``users``, ``map_of``, ``thr``, ``clearances`` as in
+    :class:`HiddenBrakeUsers`."""
+    fail_safe: torch.Tensor
+    user: torch.Tensor
+    commit: torch.Tensor
+    first: torch.Tensor
+    poses: HiddenPoses
+    starts: int
+    commit_min: int
+    users: tuple = ()
+    map_of: tuple = ()
+    thr: Optional[np.ndarray] = None
+    clearances: tuple = ()
+
+    def critical_user(self):
+        """``[M]`` int64: the user that ends a candidate's fail-safe brake starts (the lowest index among those that do so at the
+        same start), -1 where the candidate is fail-safe throughout ``starts``, -2 where it has a non-finite pose.  Nothing is read
+        back."""
+        return self.user.to(torch.int64)
+
+
+def hidden_brake_verdict(self, x, y, theta, v, *, vehicle, users, dt, a_brake, starts, commit_min, cost=None, safe=None, margin=None,
+                         inflate=0.0, lengths=None, poses=None):
+    """Hidden-traffic fail-safe verdict (``fo_scene_hidden_brake_verdict``; DESIGN.md §5.10 "Fail-safe verdict"): for the hidden road
+    ``users`` of :meth:`hidden_brake_users`, over the first ``starts`` brake starts alone (an integer in ``[1, T]``, None = T: what a
+    planner executes before it replans), how long each candidate stays fail-safe -- and, with ``cost [M, 16]`` float64 / ``safe [M]``
+    uint8 of a sweep or planning step over the SAME candidates (both or neither), that answer in the two reserved cost columns, and
+    ``safe = 0`` where ``fail_safe < commit_min`` (``0 <= commit_min <= starts``).  The stage only ever takes safety away.
+
+    Everything runs on the device and on the current stream: the pose preparation (:meth:`hidden_poses`; ``poses=`` an earlier
+    :class:`HiddenPoses` of the same candidates skips it, ``theta`` may then be None), one ``hidden_clearance`` per distinct
+    ``(metric, flow)`` on the device headings, and ONE launch for the walk and the fold.  Nothing is read back and nobody waits;
+    returns a :class:`HiddenBrakeVerdict`.  The other arguments as for :meth:`hidden_brake_users`."""
+    fn = "hidden_brake_verdict"
+    users = _road_users(users, x, fn)
+    if poses is None:
+        poses = hidden_poses(self, x, y, theta, v, lengths)
+    maps, map_of, clearances = _users_clearances(self, users, x, y, None, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
+                                                 lengths=lengths, heading=poses.heading)
+    tx, ty, thead, tlen = self._hc_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T) or tuple(poses.arc.shape) != (M, T) or tuple(poses.finite.shape) != (M,):
+        raise ValueError(f"{fn}: v and poses.arc must be [M, T], poses.finite [M]")
+    a_brake = float(a_brake)
+    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
+        raise ValueError(f"{fn}: a_brake >= 0 and finite")
+    B = _ladder_starts(starts, T, fn)
+    if isinstance(commit_min, bool) or not isinstance(commit_min, (int, np.integer)) or not 0 <= int(commit_min) <= B:
+        raise ValueError(f"{fn}: commit_min = {commit_min!r}, an integer in [0, starts = {B}]")
+    commit_min = int(commit_min)
+    dev = self.device
+    if (cost is None) != (safe is None):
+        raise ValueError(f"{fn}: cost and safe go together: give both or neither")
+    if cost is not None:
+        ok = (torch.is_tensor(cost) and torch.is_tensor(safe) and cost.device == tx.device == safe.device and cost.dtype == torch.float64
+              and safe.dtype == torch.uint8 and tuple(cost.shape) == (M, N.NC) and tuple(safe.shape) == (M,) and cost.is_contiguous()
+              and safe.is_contiguous())
+        if not ok:
+            raise ValueError(f"{fn}: cost must be a contiguous float64 [M, {N.NC}] and safe a uint8 [M] tensor on the model's device "
+                             "(they are written in place)")
+    first_c = clearances[0]
+    w, C_, K_ = first_c.window, len(users), len(maps)
+    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    tv = N.on_device(v, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    fail_safe, user, commit, first = new(M), new(M), new(C_, M), new(C_, M)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
+    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
+    args = N.HiddenBrakeVerdict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
+                                hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
+                                win_ny=w.ny, K=K_, C=C_, d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
+                                map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(poses.arc), a_brake=a_brake, dt=float(dt),
+                                h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), B=B, commit_min=commit_min,
+                                d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe),
+                                d_fail_safe=N.ptr(fail_safe), d_user=N.ptr(user), d_commit=N.ptr(commit), d_first=N.ptr(first))
+    self.ctx.call("fo_scene_hidden_brake_verdict", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_users)
+    self._hbv_inputs = (tv, poses, tuple(clearances), cost, safe)
+    return HiddenBrakeVerdict(fail_safe, user, commit, first, poses, B, commit_min, users, map_of, thr, tuple(clearances))

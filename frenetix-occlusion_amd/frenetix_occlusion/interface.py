@@ -510,6 +510,27 @@ class FOInterface:
                                                            margin=om["margin"] if margin is None else margin, dt=self.dt,
                                                            decelerations=decelerations, starts=starts, detail=detail, inflate=inflate)
 
+    def hidden_brake_verdict(self, trajectories, users, commit_min, starts=None, a_brake=None, cost=None, safe=None, margin=None,
+                             inflate=0.0):
+        """EXTENSION, not part of the reference: the fail-safe VERDICT against the hidden road users of :meth:`hidden_brake_users` --
+        for how many of the first ``starts`` brake starts (None: all) each candidate can still brake clear of every user, and which
+        user ends them (:meth:`SensorModel.hidden_brake_verdict`; returns its
+        :class:`~frenetix_occlusion.sensor_model.HiddenBrakeVerdict`: ``fail_safe [M]``, ``user [M]``, ``commit [C, M]``,
+        ``first [C, M]``).  With ``cost [M, 16]`` / ``safe [M]`` of a sweep over the same candidates the verdict is folded into the
+        two reserved columns, and candidates with ``fail_safe < commit_min`` lose their safety flag.  Defaults as for
+        :meth:`hidden_brake_users`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_verdict needs a previous evaluate_scenario")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        return self.sensor_model.hidden_brake_verdict(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], users=users,
+                                                      margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                      a_brake=vt[4] if a_brake is None else a_brake, starts=starts,
+                                                      commit_min=commit_min, cost=cost, safe=safe, inflate=inflate)
+
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
         metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of

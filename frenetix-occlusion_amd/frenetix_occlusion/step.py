@@ -19,8 +19,15 @@ from .sweep import SweepResult
 
 class PlanningStep:
     def __init__(self, sensor_model, spawn_locator, sweep, x, y, theta, v, a=None, mode="reduced", lists="f64", shard=None,
-                 mirror=False):
-        """``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
+                 mirror=False, hidden_verdict=None):
+        """``hidden_verdict`` (an extension, DESIGN.md §5.10 "Fail-safe verdict"): a dict of the keyword arguments of
+        :meth:`SensorModel.hidden_brake_verdict` -- ``vehicle``, ``users``, ``dt``, ``a_brake``, ``starts``, ``commit_min`` and
+        optionally ``margin``, ``inflate``, ``lengths`` -- :meth:`run` then queues the pose preparation, the clearances and the
+        verdict behind the step on the same stream, folded into this step's ``cost`` and ``safe`` (with ``shard``: into this
+        rank's rows, before the all-gather); ``out.hidden_verdict`` is its
+        :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeVerdict`.  None: the step queues exactly what it queues without.
+
+        ``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
         :class:`~frenetix_occlusion.distributed.CostGather` for the batch size -- this rank's step covers its contiguous
         block of the candidates (scene stage and phantoms replicated), writes the block's cost rows into the collective's
         block and :meth:`run` ends with the ONE all-gather of the path: ``out.cost_all`` = cost [M_total, 16] on every rank,
@@ -72,6 +79,17 @@ class PlanningStep:
         sweep.reserve(self.M, self.T, A, spawn_locator.T)
         self._s = None
         self._key = None
+        self._hidden_verdict = None
+        if hidden_verdict is not None:
+            hv = dict(hidden_verdict)
+            unknown = set(hv) - {"vehicle", "users", "dt", "a_brake", "starts", "commit_min", "margin", "inflate", "lengths"}
+            missing = {"vehicle", "users", "dt", "a_brake", "starts", "commit_min"} - set(hv)
+            if unknown or missing:
+                raise ValueError(f"PlanningStep: hidden_verdict takes vehicle, users, dt, a_brake, starts, commit_min and optionally "
+                                 f"margin, inflate, lengths (unknown: {sorted(unknown)}, missing: {sorted(missing)})")
+            if self.gather is not None and hv.get("lengths") is not None:
+                hv["lengths"] = hv["lengths"][self.gather.lo:self.gather.hi]
+            self._hidden_verdict = hv
 
     def _fill(self, w, O):
         """everything that does not change from step to step"""
@@ -168,6 +186,11 @@ class PlanningStep:
         sm.occluded_idx_buffer, sm.n_occluded = b["occ"], b["n_occ"]
         self.sw.A, self.sw.Ta = int(self.batch.pos.shape[0]), sl.T
         self.ctx.list_format = self.lists
+        if self._hidden_verdict is not None:
+            # behind the step, on its stream, on this rank's rows -- and before the collective, which then carries the two columns
+            tx, ty, tth, tv = self.traj[:4]
+            self.out.hidden_verdict = sm.hidden_brake_verdict(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
+                                                              **self._hidden_verdict)
         if self.gather is not None:
             # the one collective of the path, queued behind the step
             self.out.cost_all = self.gather.gather(None if self._direct or self.M == 0 else self.out.cost)

@@ -41,6 +41,8 @@ class SweepResult:
     # rank's rows [rows[0], rows[1]) of the batch; cost_all is the all-gathered cost matrix [M_total, 16] of every rank
     cost_all: Optional[torch.Tensor] = None
     rows: Optional[tuple] = None
+    # PlanningStep(hidden_verdict=...): the HiddenBrakeVerdict whose fold stands in cost[:, RES0], cost[:, RES1] and safe
+    hidden_verdict: Optional[object] = None
 
     def list_views(self):
         """five strided [A, T-1, M] views (no copy), order of ``_native.LST``"""

@@ -147,7 +147,9 @@ int fo_sweep_autotune(fo_ctx *ctx, int M, int T, const double *d_x, const double
  * fo_scene_spawn_rule_agents -> fo_sweep_set_agents -> fo_sweep_run.  The pair and list buffers of such a step are
  * UNSPECIFIED: do not read them.  fo_sweep_check then returns FO_E_STATE with a message that names the rule tables (an
  * unusable covariance in the same set is reported first).  The mark carries the generation of its agent set: the next
- * fo_sweep_set_agents / fo_step_run on the context starts clean. */
+ * fo_sweep_set_agents / fo_step_run on the context starts clean.  A fo_scene_hidden_brake_verdict stage queued behind such a
+ * step writes FO_C_RES0 and FO_C_RES1 of the poisoned rows too (its fail_safe and user), and leaves their NaNs, safe = 0 and
+ * FO_C_SAFE = 0 as they are: it only ever takes safety away. */
 int fo_sweep_check(fo_ctx *ctx, void *stream);
 
 /* HIP-event timing of the sweep kernel alone (events recorded on the launch stream around that one kernel):
@@ -832,6 +834,87 @@ typedef struct {
   int32_t *d_stop_or_null;                  /* [M][B][L] */
 } fo_hidden_brake_ladder_users_t;
 int fo_scene_hidden_brake_ladder_users(fo_ctx *ctx, const fo_hidden_brake_ladder_users_t *p, void *stream);
+
+/* EXTENSION, not part of the reference: DEVICE POSE PREPARATION of the hidden-traffic answers (DESIGN.md §5.10 "Fail-safe verdict")
+ * -- what the brake entries above take as data, made on the device from candidates that live there: one launch, nothing is read
+ * back.  Needs a context, no scene.
+ *  Inputs: d_x, d_y, d_theta, d_v [M][T] float64, d_len_or_null [M]; Lm = T clipped by len[m].
+ *  heading[m][k] = (cos, sin) of theta[m][k] from ONE sincos(theta, &s, &c) per sample: the bits the sweep's trajectory preparation
+ *   rotates the ego rectangle by.  The forecast and the walks still take no trigonometry; a checker is handed this heading as data.
+ *  arc[m][0] = 0, arc[m][k] = arc[m][k-1] + sqrt((x[k] - x[k-1])^2 + (y[k] - y[k-1])^2): be.py's
+ *   insert(cumsum(sqrt(diff(x)^2 + diff(y)^2)), 0, 0) as a SEQUENTIAL float64 sum in index order, without contraction -- numpy's
+ *   result on host arrays --, over all T samples whatever len says.
+ *  finite[m] = 1 iff every x, y, theta, v of the samples k < Lm is finite (a non-finite value at k >= Lm does not count), else 0.
+ *  Outputs, every byte written by every call: d_heading [M][T][2] float64, d_arc [M][T] float64, d_finite [M] uint8.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, messages prefixed "fo_scene_hidden_poses:"): no parameters;
+ * M < 0; with M > 0: T outside [1, 254], a missing input or output.  FO_E_STATE: no context. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y, *d_theta, *d_v;  /* [M][T] */
+  const int32_t *d_len_or_null;             /* [M] */
+  double *d_heading;                        /* [M][T][2] unit (cos, sin) */
+  double *d_arc;                            /* [M][T] travelled chord length, m */
+  uint8_t *d_finite;                        /* [M] */
+} fo_hidden_poses_t;
+int fo_scene_hidden_poses(fo_ctx *ctx, const fo_hidden_poses_t *p, void *stream);
+
+/* EXTENSION, not part of the reference: hidden-traffic FAIL-SAFE VERDICT (DESIGN.md §5.10 "Fail-safe verdict") -- "is this candidate
+ * still fail-safe against hidden traffic from every brake start up to the replanning interval?", folded into what a planner acts
+ * on: the two reserved columns of the cost row and the safety flag that fo_step_run leaves in HBM.  The walk of
+ * fo_scene_hidden_brake_users over the first B brake starts alone, without brake_first and stop.  Opt-in and additive: one launch on
+ * the caller's stream, behind the step whose cost rows it folds into; nothing is read back.
+ *  Inputs: those of fo_scene_hidden_brake_users word for word, and: B, the number of brake starts walked, 1 <= B <= T; commit_min,
+ *   0 <= commit_min <= B; d_finite_or_null [M] uint8 (of fo_scene_hidden_poses; null: every candidate counts as finite);
+ *   d_cost_or_null [M][FO_NC] and d_safe_or_null [M], the outputs of a sweep / step over the SAME M trajectories: both or neither.
+ *  Write commit_users[c][m] and first_users[c][m] for what fo_scene_hidden_brake_users writes on the same inputs.
+ *  1. commit[c][m] = commit_users[c][m] if 0 <= commit_users[c][m] < B, else -1; first[c][m] = first_users[c][m].
+ *  2. fail_safe[m] = the smallest commit[c][m] >= 0 over the classes, B when there is none: the number of leading brake starts from
+ *   which braking at a_brake keeps the moving ego clear of every user.  0 = "not even now", B = "throughout what was asked".
+ *  3. user[m] = the lowest c with commit[c][m] == fail_safe[m], -1 when fail_safe[m] == B.
+ *  4. finite[m] == 0: fail_safe[m] = 0 and user[m] = -2, whatever the walk found (a NaN pose fails every footprint comparison and
+ *   would read as "no hit": this case fails CLOSED).
+ *  5. With d_cost / d_safe: cost[m][FO_C_RES0] = (double)fail_safe[m], cost[m][FO_C_RES1] = (double)user[m]; if
+ *   fail_safe[m] < commit_min: safe[m] = 0 and cost[m][FO_C_SAFE] = 0.0, otherwise both are left as found -- the stage only ever
+ *   takes safety away; a row that a refused rule list or an unusable covariance poisoned keeps its NaNs and safe = 0 and gets the
+ *   two columns.  No other column is touched.
+ *  Outputs, int32, every byte written by every call: d_fail_safe [M], d_user [M], d_commit [C][M], d_first [C][M].
+ *  Safety of the data: as fo_scene_hidden_brake_users; finite may hold anything, no index depends on it.
+ *  Not claimed: what fo_scene_hidden_brake_users does not claim; brake starts b >= B are not looked at; that cost / safe belong to
+ *   the same candidates is the caller's word.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_verdict:"), in this order: K outside [1, 3]; C outside [1, 8]; no h_thr; a window outside [1, 32768]^2; an
+ * r2_cap[k], k < K, negative or beyond FO_HIDDEN_REACH_MAX_HALO; map_of[c], c < C, outside [0, K); M < 0; a_brake negative or not
+ * finite; dt not positive and finite; with M > 0: T outside [1, 254]; B outside [1, T]; commit_min outside [0, B];
+ * C * T > FO_HIDDEN_BRAKE_MAX_TABLE; a row that is negative, decreases or ends beyond 169 * r2_cap[map_of[c]]; no d_x / d_y /
+ * d_heading; no d_key[k] or d_qmin[k], k < K; no d_v or d_arc; a missing output; only one of d_cost_or_null / d_safe_or_null;
+ * extents refused as by fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+#define FO_HIDDEN_VERDICT_NOT_FINITE (-2)
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  double a_brake, dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  int32_t commit_min;                       /* fail_safe below it takes safety away */
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC] of the step: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  int32_t *d_fail_safe, *d_user;            /* [M] */
+  int32_t *d_commit, *d_first;              /* [C][M] */
+} fo_hidden_brake_verdict_t;
+int fo_scene_hidden_brake_verdict(fo_ctx *ctx, const fo_hidden_brake_verdict_t *p, void *stream);
 
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least

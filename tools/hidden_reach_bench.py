@@ -5,7 +5,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
                                        [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...] [--brake-ladder K]
-                                       [--brake-ladder-users]
+                                       [--brake-ladder-users] [--brake-verdict B]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -43,6 +43,12 @@ ONE launch, with the detail and without it, next to one ``hidden_brake_ladder`` 
 ties are asserted (exact integers): every level's slice is ``hidden_brake_users`` at that deceleration, every user's rows are
 ``hidden_brake_ladder`` on that user's forecast.  Also the pairs whose ``required_all`` lies above every user's own ``required``
 and how ``blocking`` is spread over the users.
+
+``--brake-verdict B``: ``hidden_brake_verdict`` for the README's road users over the first B brake starts and over all of them (§5.10
+"Fail-safe verdict") -- the device pose preparation, the clearances and ONE launch, with and without the poses handed over -- next to
+``hidden_brake_users`` on the same device tensors with its host heading pass.  In every run the tie is asserted (exact integers):
+``commit`` is ``hidden_brake_users``' where it is below B, ``first`` is its ``first``, ``fail_safe`` and ``user`` are their fold.  Also
+the poses the walks scanned.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -98,6 +104,8 @@ def main():
                     help="time hidden_brake_ladder at K decelerations up to the one of --brake next to K hidden_brake calls")
     ap.add_argument("--brake-ladder-users", action="store_true",
                     help="time hidden_brake_ladder_users for the README's three road users next to one hidden_brake_ladder call per user")
+    ap.add_argument("--brake-verdict", type=int, default=None, metavar="B",
+                    help="time hidden_brake_verdict over the first B brake starts (and over all) next to hidden_brake_users")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -232,6 +240,43 @@ def main():
         res["commit_never_per_user"] = [int(v) for v in (u_out.commit < 0).sum(dim=1).cpu()]
         cu = u_out.critical_user()
         res["candidates_by_critical_user"] = {str(c): int((cu == c).sum()) for c in range(-1, len(users))}
+    if a.brake_verdict:
+        users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
+        a_brake = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        if not 1 <= a.brake_verdict <= T:
+            ap.error(f"--brake-verdict B: 1 <= B <= {T}")
+        hbv = lambda B, **kw: sm.hidden_brake_verdict(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake, starts=B,
+                                                      commit_min=B, **kw)
+        # hidden_brake_users on the same tensors, with its host heading pass -- and, for the tie, on the verdict's own headings and on
+        # host x, y, whose arc numpy sums as the device does (torch's scan of device tensors may round otherwise)
+        hbu = lambda: sm.hidden_brake_users(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake)
+        first_out = hbv(a.brake_verdict)
+        u_out = sm.hidden_brake_users(traj["x"], traj["y"], None, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake,
+                                      heading=first_out.poses.heading)
+        assert torch.equal(u_out.arc, first_out.poses.arc)
+        bf, st = u_out.brake_first.cpu().numpy().astype(np.int64), u_out.stop.cpu().numpy().astype(np.int64)
+        b = np.arange(T)[None, :]
+        i0 = np.maximum(st, b + 1)
+        moving = np.minimum(i0, T) - (b + 1)
+        walk = np.where((bf >= 0) & (bf < i0[None]), bf - b[None], (moving + (i0 < T))[None]).max(axis=0)      # [M, T], as --brake-users
+        res["brake_verdict_users"] = [list(u) for u in users]
+        res["users_walk_poses_scanned"] = int(walk.sum())
+        for B in sorted({a.brake_verdict, T}):
+            v_out = hbv(B, poses=first_out.poses)
+            commit = torch.where((u_out.commit >= 0) & (u_out.commit < B), u_out.commit, -1)          # the tie of step 1, in every run
+            assert torch.equal(v_out.commit, commit) and torch.equal(v_out.first, u_out.first), B
+            fail_safe = torch.where(commit >= 0, commit, B).amin(dim=0)
+            assert torch.equal(v_out.fail_safe, fail_safe.to(torch.int32)), B
+            user = torch.where(fail_safe < B, (torch.where(commit >= 0, commit, B) == fail_safe[None]).to(torch.int8).argmax(dim=0), -1)
+            assert torch.equal(v_out.user.to(torch.int64), torch.where(v_out.poses.finite != 0, user, -2)), B
+            res[f"brake_verdict_call_B{B}_ms"] = _median_ms(lambda: hbv(B), a.calls)
+            res[f"brake_verdict_call_B{B}_reused_poses_ms"] = _median_ms(lambda: hbv(B, poses=first_out.poses), a.calls)
+            res[f"verdict_walk_poses_scanned_B{B}"] = int(walk[:, :B].sum())
+            res[f"candidates_by_fail_safe_B{B}"] = {str(k): int((v_out.fail_safe == k).sum()) for k in range(B + 1)}
+            res[f"candidates_by_user_B{B}"] = {str(c): int((v_out.user == c).sum()) for c in range(-2, len(users))}
+        res["hidden_poses_call_ms"] = _median_ms(lambda: sm.hidden_poses(tx, ty, tth, tv), a.calls)
+        res["brake_users_call_ms"] = _median_ms(hbu, a.calls)
     if a.brake_ladder:
         a_top = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
         levels = np.linspace(0.5, a_top, a.brake_ladder) if a.brake_ladder > 1 else np.array([a_top])
