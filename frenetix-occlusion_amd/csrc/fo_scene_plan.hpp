@@ -160,6 +160,40 @@ inline size_t brake_verdict_lds_bytes(int T, int K, int C, int B) {
          (size_t)C * (size_t)T * sizeof(int32_t);
 }
 inline size_t brake_verdict_lds_bound() { return (size_t)BRAKE_LADDER_ROWS_BYTES + BRAKE_USERS_MAX_TABLE * sizeof(int32_t); }
+// the ladder verdict: the lanes of the brake ladder by road users over the first B brake starts -- a lane per (m, b, l), l fastest,
+// padded to Lp = brake_ladder_width(L); G = the power of two >= min(B * Lp, HB_THREADS) lanes per trajectory (min(256, Lp *
+// pow2ceil(B))), ceil(B * Lp / G) rounds over b.  A workgroup serves HB_THREADS / G trajectories, or fewer where their rows (T * (48
+// + 4 K) bytes each) would exceed BRAKE_LADDER_ROWS_BYTES, as in the fail-safe verdict: at small B * Lp the lanes' rule alone would
+// stage far more rows than LDS holds; the lanes beyond per_block * G take part in the staging and then have no trajectory.  Behind
+// the rows stand the table (4 C T bytes) and the exchange through which the waves of a trajectory (G > 64) meet: one key and one
+// rank per class for each of the workgroup's HB_THREADS / 64 waves.  brake_ladder_verdict_lds_bound: no call needs more -- a single
+// trajectory takes at most 254 * 60 bytes, under the rows' bound; the table is part of the argument
+constexpr int BRAKE_LADDER_VERDICT_WAVES = HB_THREADS / 64;
+inline int brake_ladder_verdict_group(int L, int B) {
+  const int Lp = brake_ladder_users_width(L);
+  int G = Lp;
+  while (G < HB_THREADS && (int64_t)G < (int64_t)B * Lp) G <<= 1;
+  return G;
+}
+inline int brake_ladder_verdict_per_block(int T, int K, int L, int B) {
+  const size_t per_traj = (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t));
+  const int by_lanes = HB_THREADS / brake_ladder_verdict_group(L, B);
+  const int by_rows = (int)((size_t)BRAKE_LADDER_ROWS_BYTES / per_traj);
+  const int p = by_lanes < by_rows ? by_lanes : by_rows;
+  return p < 1 ? 1 : p;
+}
+inline int brake_ladder_verdict_blocks(int M, int T, int K, int L, int B) {
+  const int p = brake_ladder_verdict_per_block(T, K, L, B);
+  return (int)(((int64_t)M + p - 1) / p);
+}
+inline size_t brake_ladder_verdict_lds_bytes(int T, int K, int C, int L, int B) {
+  return (size_t)brake_ladder_verdict_per_block(T, K, L, B) * (size_t)T * (6 * sizeof(double) + (size_t)K * sizeof(int32_t)) +
+         (size_t)C * (size_t)T * sizeof(int32_t) + (size_t)(C + 1) * BRAKE_LADDER_VERDICT_WAVES * sizeof(int32_t);
+}
+inline size_t brake_ladder_verdict_lds_bound() {
+  return (size_t)BRAKE_LADDER_ROWS_BYTES + BRAKE_LADDER_USERS_MAX_ARG_BYTES +
+         (size_t)(BRAKE_LADDER_USERS_MAX_CLASSES + 1) * BRAKE_LADDER_VERDICT_WAVES * sizeof(int32_t);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

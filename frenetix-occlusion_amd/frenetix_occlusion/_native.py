@@ -55,6 +55,7 @@ EXPORTS = [
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
     "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
     "fo_scene_hidden_brake_ladder_users", "fo_scene_hidden_poses", "fo_scene_hidden_brake_verdict",
+    "fo_scene_hidden_brake_ladder_verdict",
 ]
 
 
@@ -208,6 +209,20 @@ class HiddenBrakeVerdict(C.Structure):  # fo_hidden_brake_verdict_t
                 ("d_first", C.c_void_p)]
 
 
+class HiddenBrakeLadderVerdict(C.Structure):    # fo_hidden_brake_ladder_verdict_t
+    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
+                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
+                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
+                ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
+                ("h_thr", C.POINTER(C.c_int32)), ("a_limit", C.c_double), ("d_finite_or_null", C.c_void_p),
+                ("d_cost_or_null", C.c_void_p), ("d_safe_or_null", C.c_void_p), ("d_need", C.c_void_p), ("d_at", C.c_void_p),
+                ("d_blocking", C.c_void_p), ("d_user", C.c_void_p), ("d_decel", C.c_void_p), ("d_need_of", C.c_void_p),
+                ("d_first", C.c_void_p)]
+
+
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
 HIDDEN_CLEARANCE_METRIC = {"euclid": 0, "road": 1}   # FO_HIDDEN_CLEARANCE_EUCLID / _ROAD
 
@@ -324,6 +339,7 @@ def load():
     lib.fo_scene_hidden_brake_ladder_users.argtypes = [vp, C.POINTER(HiddenBrakeLadderUsers), vp]
     lib.fo_scene_hidden_poses.argtypes = [vp, C.POINTER(HiddenPoses), vp]
     lib.fo_scene_hidden_brake_verdict.argtypes = [vp, C.POINTER(HiddenBrakeVerdict), vp]
+    lib.fo_scene_hidden_brake_ladder_verdict.argtypes = [vp, C.POINTER(HiddenBrakeLadderVerdict), vp]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -566,6 +566,18 @@ def _ladder_levels(decelerations, fn):
     return levels
 
 
+def default_brake_ladder(a_max, fn):
+    """the default ladder of ``fn`` (hidden_brake_ladder and hidden_brake_ladder_users): 0.5, 1.0, ... up to ``a_max``, with ``a_max``
+    itself appended if it is not on that grid"""
+    a_max = float(a_max)
+    n = int(a_max // 0.5) if 0.5 <= a_max < float("inf") else 0      # levels on the 0.5 grid
+    on_grid = n > 0 and 0.5 * n == a_max
+    if n + (not on_grid) > N.HIDDEN_BRAKE_MAX_LEVELS:
+        raise ValueError(f"{fn}: the default ladder 0.5, 1.0, ... up to a_max = {a_max} m/s^2 has more than "
+                         f"{N.HIDDEN_BRAKE_MAX_LEVELS} levels (hand decelerations over)")
+    return [0.5 * (k + 1) for k in range(n)] + ([] if on_grid else [a_max])
+
+
 def _ladder_starts(starts, T, fn):
     """the number of brake starts of ``fn``: ``starts``, an integer in ``[1, T]``, None = T"""
     if starts is None:
@@ -1108,3 +1120,131 @@ def hidden_brake_verdict(self, x, y, theta, v, *, vehicle, users, dt, a_brake, s
     # (stay referenced until the next call, as in hidden_brake_users)
     self._hbv_inputs = (tv, poses, tuple(clearances), cost, safe)
     return HiddenBrakeVerdict(fail_safe, user, commit, first, poses, B, commit_min, users, map_of, thr, tuple(clearances))
+
+
+@dataclass
+class HiddenBrakeLadderVerdict:
+    """what :meth:`SensorModel.hidden_brake_ladder_verdict` returns (DESIGN.md §5.10 "Ladder verdict"; device tensors): with ``ra``,
+    ``blk``, ``req`` for ``required_all``, ``blocking``, ``required`` of :class:`HiddenBrakeLadderUsers` on the same inputs and
+    ``ends = min(starts, lengths[m])`` -- ``need [M]`` int32, the largest ``ra[m, b]`` over ``b < ends`` with -1 ("no level") counted
+    as ``L = len(levels)``: the level the worst brake start needs, -1 where ``ends`` is 0; ``at [M]`` the first such start, -1 =
+    none; ``blocking [M]`` = ``blk[m, at[m]]``, the users that keep that start from the next gentler level; ``user [M]`` its lowest
+    set bit, -1 = none, -2 = the candidate has a non-finite pose and fails closed (``need`` L, ``decel`` inf); ``decel [M]`` float64
+    = ``levels[need]``, ``+inf`` for ``need == L``, 0.0 for ``need == -1``; per user ``need_of [C, M]`` -- the same maximum over
+    ``req[c]`` -- and ``first [C, M]``.  ``poses`` the :class:`HiddenPoses` it walked on, ``levels`` (host float64 ``[L]``, strictly
+    ascending), ``starts``, ``a_limit`` (above it a candidate lost its safety flag), ``users``, ``map_of``, ``thr``, ``clearances``
+    as in :class:`HiddenBrakeUsers`.
+
+    Not claimed: what :class:`HiddenBrakeLadderUsers` does not claim; the answer is only as fine as the ladder."""
+    need: torch.Tensor
+    at: torch.Tensor
+    blocking: torch.Tensor
+    user: torch.Tensor
+    decel: torch.Tensor
+    need_of: torch.Tensor
+    first: torch.Tensor
+    levels: np.ndarray
+    starts: int
+    a_limit: float
+    users: tuple = ()
+    poses: Optional[HiddenPoses] = None
+    map_of: tuple = ()
+    thr: Optional[np.ndarray] = None
+    clearances: tuple = ()
+
+    def required_deceleration(self):
+        """``[M]`` float64 (m/s^2): ``decel`` -- what the cost row holds in its first reserved column"""
+        return self.decel
+
+    def brake_threat_number(self, a_max):
+        """``[M]`` float64: ``decel / a_max`` -- the reference's ``break_threat_number`` (metrics/be.py:56) against the hidden road
+        users, from the worst of the brake starts walked.  Nothing is read back."""
+        return self.decel / float(a_max)
+
+    def critical_user(self):
+        """``[M]`` int64: the lowest user that keeps the worst brake start from the next gentler level, -1 = none, -2 where the
+        candidate has a non-finite pose.  Nothing is read back."""
+        return self.user.to(torch.int64)
+
+
+def hidden_brake_ladder_verdict(self, x, y, theta, v, *, vehicle, users, dt, levels=None, starts, a_limit, cost=None, safe=None,
+                                margin=None, inflate=0.0, lengths=None, poses=None):
+    """Hidden-traffic ladder verdict (``fo_scene_hidden_brake_ladder_verdict``; DESIGN.md §5.10 "Ladder verdict"): for the hidden
+    road ``users`` of :meth:`hidden_brake_users` and the ladder ``levels`` of :meth:`hidden_brake_ladder_users` (None: 0.5, 1.0, ...
+    up to ``a_limit``, which must then be finite), over the first ``starts`` brake starts alone (an integer in ``[1, T]``, None = T:
+    what a planner executes before it replans), the gentlest deceleration of the ladder that keeps the moving ego clear of every user
+    from the WORST of those starts -- and, with ``cost [M, 16]`` float64 / ``safe [M]`` uint8 of a sweep or planning step over the
+    SAME candidates (both or neither), that deceleration and the blocking user in the two reserved cost columns, and ``safe = 0``
+    where no level suffices or the deceleration exceeds ``a_limit`` (``>= 0``, ``inf`` allowed).  The stage only ever takes safety
+    away.  It owns the same two columns as :meth:`hidden_brake_verdict`: fold one or the other into a row.
+
+    Everything runs on the device and on the current stream: the pose preparation (:meth:`hidden_poses`; ``poses=`` an earlier
+    :class:`HiddenPoses` of the same candidates skips it, ``theta`` may then be None), one ``hidden_clearance`` per distinct
+    ``(metric, flow)`` on the device headings, and ONE launch for the walk, the reduction over the brake starts and the fold.
+    Nothing is read back and nobody waits; returns a :class:`HiddenBrakeLadderVerdict`."""
+    fn = "hidden_brake_ladder_verdict"
+    users = _road_users(users, x, fn)
+    try:
+        a_limit = float(a_limit)
+    except (TypeError, ValueError):
+        a_limit = float("nan")
+    if not a_limit >= 0.0:
+        raise ValueError(f"{fn}: a_limit >= 0 (inf is possible, nan is not)")
+    if levels is None:
+        if not math.isfinite(a_limit):
+            raise ValueError(f"{fn}: the default levels run up to a_limit, which is not finite: hand levels over")
+        levels = default_brake_ladder(a_limit, fn)
+    levels = _ladder_levels(levels, fn)
+    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
+    if 4 * len(users) * T + 8 * len(levels) > N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES:
+        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds of 4 bytes and {len(levels)} levels "
+                         f"of 8 bytes are {4 * len(users) * T + 8 * len(levels)} bytes, at most "
+                         f"{N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES} are possible (they travel as a kernel argument)")
+    if poses is None:
+        poses = hidden_poses(self, x, y, theta, v, lengths)
+    maps, map_of, clearances = _users_clearances(self, users, x, y, None, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
+                                                 lengths=lengths, heading=poses.heading)
+    tx, ty, thead, tlen = self._hc_inputs
+    M, T = (int(a) for a in tx.shape)
+    if tuple(v.shape) != (M, T) or tuple(poses.arc.shape) != (M, T) or tuple(poses.finite.shape) != (M,):
+        raise ValueError(f"{fn}: v and poses.arc must be [M, T], poses.finite [M]")
+    B = _ladder_starts(starts, T, fn)
+    dev = self.device
+    if (cost is None) != (safe is None):
+        raise ValueError(f"{fn}: cost and safe go together: give both or neither")
+    if cost is not None:
+        ok = (torch.is_tensor(cost) and torch.is_tensor(safe) and cost.device == tx.device == safe.device and cost.dtype == torch.float64
+              and safe.dtype == torch.uint8 and tuple(cost.shape) == (M, N.NC) and tuple(safe.shape) == (M,) and cost.is_contiguous()
+              and safe.is_contiguous())
+        if not ok:
+            raise ValueError(f"{fn}: cost must be a contiguous float64 [M, {N.NC}] and safe a uint8 [M] tensor on the model's device "
+                             "(they are written in place)")
+    first_c = clearances[0]
+    w, C_, K_, L_ = first_c.window, len(users), len(maps), len(levels)
+    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    tv = N.on_device(v, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    need, at, blocking, user, need_of, first = new(M), new(M), new(M), new(M), new(C_, M), new(C_, M)
+    decel = torch.empty((M,), dtype=torch.float64, device=dev)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
+    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
+    args = N.HiddenBrakeLadderVerdict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
+                                      hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0,
+                                      win_nx=w.nx, win_ny=w.ny, K=K_, C=C_,
+                                      d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                      d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
+                                      r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
+                                      map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(poses.arc),
+                                      h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B, dt=float(dt),
+                                      h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), a_limit=a_limit,
+                                      d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe),
+                                      d_need=N.ptr(need), d_at=N.ptr(at), d_blocking=N.ptr(blocking), d_user=N.ptr(user),
+                                      d_decel=N.ptr(decel), d_need_of=N.ptr(need_of), d_first=N.ptr(first))
+    self.ctx.call("fo_scene_hidden_brake_ladder_verdict", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_users)
+    self._hblv_inputs = (tv, poses, tuple(clearances), cost, safe)
+    self._hblv_args = args                                  # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
+    return HiddenBrakeLadderVerdict(need, at, blocking, user, decel, need_of, first, levels, B, a_limit, users, poses, map_of, thr,
+                                    tuple(clearances))

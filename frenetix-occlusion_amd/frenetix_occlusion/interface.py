@@ -28,6 +28,7 @@ import yaml
 from . import _native as N
 from .agent import FOAgentManager
 from .metrics.metric import Metric
+from .hidden_traffic import default_brake_ladder as _default_brake_ladder
 from .sensor_model import SensorModel
 from .spawn_locator import SpawnLocator
 from .utils.fo_obstacle import FOObstacles
@@ -64,18 +65,6 @@ def occlusion_memory_vehicles(acc):
     if vehicles not in ("off", "lanes"):
         raise ValueError(f"accelerator.occlusion_memory_vehicles: 'off' or 'lanes', not {vehicles!r}")
     return vehicles
-
-
-def _default_brake_ladder(a_max, fn):
-    """the default ladder of ``fn`` (hidden_brake_ladder and hidden_brake_ladder_users): 0.5, 1.0, ... up to ``a_max``, with ``a_max``
-    itself appended if it is not on that grid"""
-    a_max = float(a_max)
-    n = int(a_max // 0.5) if 0.5 <= a_max < float("inf") else 0      # levels on the 0.5 grid
-    on_grid = n > 0 and 0.5 * n == a_max
-    if n + (not on_grid) > N.HIDDEN_BRAKE_MAX_LEVELS:
-        raise ValueError(f"{fn}: the default ladder 0.5, 1.0, ... up to a_max = {a_max} m/s^2 has more than "
-                         f"{N.HIDDEN_BRAKE_MAX_LEVELS} levels (hand decelerations over)")
-    return [0.5 * (k + 1) for k in range(n)] + ([] if on_grid else [a_max])
 
 
 class FOInterface:
@@ -530,6 +519,31 @@ class FOInterface:
                                                       margin=om["margin"] if margin is None else margin, dt=self.dt,
                                                       a_brake=vt[4] if a_brake is None else a_brake, starts=starts,
                                                       commit_min=commit_min, cost=cost, safe=safe, inflate=inflate)
+
+    def hidden_brake_ladder_verdict(self, trajectories, users, a_limit=None, starts=None, levels=None, cost=None, safe=None, margin=None,
+                                    inflate=0.0):
+        """EXTENSION, not part of the reference: the LADDER VERDICT against the hidden road users of :meth:`hidden_brake_users` -- the
+        gentlest deceleration of the ladder ``levels`` (None: 0.5, 1.0, ... up to the vehicle's ``a_max``) that keeps each candidate
+        clear of every user from the WORST of its first ``starts`` brake starts (None: all), and the user that blocks the level below
+        (:meth:`SensorModel.hidden_brake_ladder_verdict`; returns its
+        :class:`~frenetix_occlusion.sensor_model.HiddenBrakeLadderVerdict`: ``need``, ``at``, ``blocking``, ``user [M]``,
+        ``decel [M]``, ``need_of``, ``first [C, M]``; ``.required_deceleration()``, ``.brake_threat_number(a_max)``,
+        ``.critical_user()``).  With ``cost [M, 16]`` / ``safe [M]`` of a sweep over the same candidates the deceleration and the
+        user are folded into the two reserved columns, and candidates that need more than ``a_limit`` (None: the vehicle's
+        ``a_max``) or more than the ladder holds lose their safety flag.  The other defaults as for :meth:`hidden_brake_users`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_ladder_verdict needs a previous evaluate_scenario")
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        if levels is None:
+            levels = _default_brake_ladder(vt[4], "hidden_brake_ladder_verdict")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        return self.sensor_model.hidden_brake_ladder_verdict(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], users=users,
+                                                             margin=om["margin"] if margin is None else margin, dt=self.dt,
+                                                             levels=levels, starts=starts, a_limit=vt[4] if a_limit is None else a_limit,
+                                                             cost=cost, safe=safe, inflate=inflate)
 
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the

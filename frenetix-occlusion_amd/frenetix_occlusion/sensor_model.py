@@ -22,7 +22,7 @@ from .fan_geometry import ROAD, VISIBLE, OCCLUDED, HoleIndex, footprint_polygon,
 from .cell_window import CellWindow, VisibleArea  # noqa: F401
 from .occlusion_memory import OCCLUSION_MEMORY_METRICS, OCCLUSION_MEMORY_VEHICLES, OcclusionMemory, OcclusionMemoryPlan, occlusion_memory_r2  # noqa: F401
 from .future_visibility import FutureVisibility  # noqa: F401
-from .hidden_traffic import HIDDEN_REACH_FLOWS, HIDDEN_REACH_METRICS, HiddenBrake, HiddenBrakeClasses, HiddenBrakeLadder, HiddenBrakeLadderUsers, HiddenBrakeUsers, HiddenBrakeVerdict, HiddenClearance, HiddenPoses, HiddenReach, HiddenWitness, hidden_brake_thresholds, hidden_reach_r2, hidden_reach_road_units, reference_deceleration_ladder, travelled_arc, unit_headings  # noqa: F401
+from .hidden_traffic import HIDDEN_REACH_FLOWS, HIDDEN_REACH_METRICS, HiddenBrake, HiddenBrakeClasses, HiddenBrakeLadder, HiddenBrakeLadderUsers, HiddenBrakeLadderVerdict, HiddenBrakeUsers, HiddenBrakeVerdict, HiddenClearance, HiddenPoses, HiddenReach, HiddenWitness, hidden_brake_thresholds, hidden_reach_r2, hidden_reach_road_units, reference_deceleration_ladder, travelled_arc, unit_headings  # noqa: F401
 
 
 class SensorModel:
@@ -378,7 +378,7 @@ class SensorModel:
 
     # ---- extensions, not part of the reference: each body and its docstring live in the module named
     from .future_visibility import future_visibility, future_visibility_ex
-    from .hidden_traffic import hidden_brake, hidden_brake_classes, hidden_brake_ladder, hidden_brake_ladder_users, hidden_brake_users, hidden_brake_verdict, hidden_clearance, hidden_poses, hidden_reach, hidden_witness
+    from .hidden_traffic import hidden_brake, hidden_brake_classes, hidden_brake_ladder, hidden_brake_ladder_users, hidden_brake_ladder_verdict, hidden_brake_users, hidden_brake_verdict, hidden_clearance, hidden_poses, hidden_reach, hidden_witness
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

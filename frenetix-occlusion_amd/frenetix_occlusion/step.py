@@ -17,15 +17,41 @@ from . import _native as N
 from .sweep import SweepResult
 
 
+def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict):
+    """the ``hidden_ladder_verdict=`` of :class:`PlanningStep` as a dict of its own, or its refusal; None stays None"""
+    if hidden_ladder_verdict is None:
+        return None
+    if hidden_verdict is not None:
+        raise ValueError("PlanningStep: hidden_verdict and hidden_ladder_verdict own the same two reserved cost columns: "
+                         "a step runs one or the other")
+    try:
+        lv = dict(hidden_ladder_verdict)
+    except (TypeError, ValueError):
+        raise ValueError(f"PlanningStep: hidden_ladder_verdict = {hidden_ladder_verdict!r} is no dict of keyword arguments") from None
+    unknown = set(lv) - {"vehicle", "users", "dt", "levels", "starts", "a_limit", "margin", "inflate", "lengths"}
+    missing = {"vehicle", "users", "dt", "levels", "starts", "a_limit"} - set(lv)
+    if unknown or missing:
+        raise ValueError(f"PlanningStep: hidden_ladder_verdict takes vehicle, users, dt, levels, starts, a_limit and optionally "
+                         f"margin, inflate, lengths (unknown: {sorted(map(str, unknown))}, missing: {sorted(missing)})")
+    return lv
+
+
 class PlanningStep:
     def __init__(self, sensor_model, spawn_locator, sweep, x, y, theta, v, a=None, mode="reduced", lists="f64", shard=None,
-                 mirror=False, hidden_verdict=None):
+                 mirror=False, hidden_verdict=None, hidden_ladder_verdict=None):
         """``hidden_verdict`` (an extension, DESIGN.md §5.10 "Fail-safe verdict"): a dict of the keyword arguments of
         :meth:`SensorModel.hidden_brake_verdict` -- ``vehicle``, ``users``, ``dt``, ``a_brake``, ``starts``, ``commit_min`` and
         optionally ``margin``, ``inflate``, ``lengths`` -- :meth:`run` then queues the pose preparation, the clearances and the
         verdict behind the step on the same stream, folded into this step's ``cost`` and ``safe`` (with ``shard``: into this
         rank's rows, before the all-gather); ``out.hidden_verdict`` is its
         :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeVerdict`.  None: the step queues exactly what it queues without.
+
+        ``hidden_ladder_verdict`` (an extension, DESIGN.md §5.10 "Ladder verdict"): a dict of the keyword arguments of
+        :meth:`SensorModel.hidden_brake_ladder_verdict` -- ``vehicle``, ``users``, ``dt``, ``levels``, ``starts``, ``a_limit`` and
+        optionally ``margin``, ``inflate``, ``lengths`` -- queued where ``hidden_verdict`` is: behind the step on the same stream,
+        with ``shard`` on this rank's rows before the all-gather; ``out.hidden_ladder_verdict`` is its
+        :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeLadderVerdict`.  The two stages own the same two reserved cost
+        columns: giving both is a ValueError.  None: the step queues and allocates exactly what it does without.
 
         ``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
         :class:`~frenetix_occlusion.distributed.CostGather` for the batch size -- this rank's step covers its contiguous
@@ -40,6 +66,7 @@ class PlanningStep:
             raise ValueError("PlanningStep: the three stages must share one context (one ego, one GPU)")
         if mode not in ("reduced", "pair", "full"):
             raise ValueError(f"unknown output mode '{mode}'")
+        ladder = hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict)    # (refused before anything is allocated)
         self.sm, self.sl, self.sw = sensor_model, spawn_locator, sweep
         self.ctx = sweep.ctx
         self.mode, self.lists, self.mirror = mode, lists, bool(mirror)
@@ -90,6 +117,9 @@ class PlanningStep:
             if self.gather is not None and hv.get("lengths") is not None:
                 hv["lengths"] = hv["lengths"][self.gather.lo:self.gather.hi]
             self._hidden_verdict = hv
+        self._hidden_ladder_verdict = ladder
+        if ladder is not None and self.gather is not None and ladder.get("lengths") is not None:
+            ladder["lengths"] = ladder["lengths"][self.gather.lo:self.gather.hi]
 
     def _fill(self, w, O):
         """everything that does not change from step to step"""
@@ -191,6 +221,11 @@ class PlanningStep:
             tx, ty, tth, tv = self.traj[:4]
             self.out.hidden_verdict = sm.hidden_brake_verdict(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
                                                               **self._hidden_verdict)
+        if self._hidden_ladder_verdict is not None:
+            # the same place: one stage or the other owns the two columns
+            tx, ty, tth, tv = self.traj[:4]
+            self.out.hidden_ladder_verdict = sm.hidden_brake_ladder_verdict(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
+                                                                            **self._hidden_ladder_verdict)
         if self.gather is not None:
             # the one collective of the path, queued behind the step
             self.out.cost_all = self.gather.gather(None if self._direct or self.M == 0 else self.out.cost)

@@ -43,6 +43,8 @@ class SweepResult:
     rows: Optional[tuple] = None
     # PlanningStep(hidden_verdict=...): the HiddenBrakeVerdict whose fold stands in cost[:, RES0], cost[:, RES1] and safe
     hidden_verdict: Optional[object] = None
+    # PlanningStep(hidden_ladder_verdict=...): the HiddenBrakeLadderVerdict whose fold stands in the same two columns and safe
+    hidden_ladder_verdict: Optional[object] = None
 
     def list_views(self):
         """five strided [A, T-1, M] views (no copy), order of ``_native.LST``"""

@@ -916,6 +916,78 @@ typedef struct {
 } fo_hidden_brake_verdict_t;
 int fo_scene_hidden_brake_verdict(fo_ctx *ctx, const fo_hidden_brake_verdict_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic LADDER VERDICT (DESIGN.md §5.10 "Ladder verdict") -- "how hard would the ego
+ * have to brake, from the worst of the brake starts it executes before it replans, to stay clear of every hidden road user?", as a
+ * graded term in what a planner acts on: the two reserved columns of the cost row and the safety flag that fo_step_run leaves in
+ * HBM.  The walk of fo_scene_hidden_brake_ladder_users over the first B brake starts, reduced over them on the device: no [M][B]
+ * or [M][B][L] buffer exists here.  Opt-in and additive: one launch on the caller's stream, behind the step whose cost rows it folds
+ * into; nothing is read back.  It writes the SAME two reserved columns as fo_scene_hidden_brake_verdict: a step runs one stage or
+ * the other, never both.
+ *  Inputs: those of fo_scene_hidden_brake_ladder_users word for word -- K maps with d_key[k], d_qmin[k], r2_cap[k]; C classes,
+ *   map_of[c], h_thr [C][T]; trajectories, d_heading, d_len_or_null, extents and window; d_v, d_arc, dt; h_levels [L]; B -- with the
+ *   levels STRICTLY ASCENDING (the answer is a maximum over brake starts and means "the gentlest sufficient deceleration"), and:
+ *   a_limit, float64, >= 0, +inf allowed, not NaN; d_finite_or_null [M] uint8 (of fo_scene_hidden_poses; null: every candidate counts
+ *   as finite); d_cost_or_null [M][FO_NC] and d_safe_or_null [M], the outputs of a sweep / step over the SAME M trajectories: both or
+ *   neither.
+ *  Write ra[m][b], blk[m][b], req[c][m][b] and first[c][m] for what fo_scene_hidden_brake_ladder_users writes as required_all,
+ *   blocking, required and first on the same inputs, and ends = min(B, Lm).
+ *  1. rank(m, b) = ra[m][b] if ra[m][b] >= 0, else L ("no level of this ladder"); need[m] = the maximum of rank(m, b) over b < ends,
+ *   -1 when ends = 0 ("nothing asked").
+ *  2. at[m] = the smallest b < ends with rank(m, b) == need[m], -1 when need[m] = -1.
+ *  3. blocking[m] = blk[m][at[m]], 0 when at[m] = -1; user[m] = the lowest set bit of blocking[m], -1 if none.
+ *  4. Per class need_of[c][m] = the same maximum over b < ends formed from req[c][m][b] (-1 -> L), -1 when ends = 0; first[c][m] is
+ *   the ladder-users entry's.
+ *  5. decel[m] (float64) = levels[need[m]] for 0 <= need[m] < L, +inf for need[m] == L, 0.0 for need[m] == -1.
+ *  6. finite[m] == 0: need[m] = L, at[m] = 0, blocking[m] = 0, user[m] = FO_HIDDEN_VERDICT_NOT_FINITE and decel[m] = +inf, whatever
+ *   the walk found (a NaN pose fails every footprint comparison and would read as "no hit": this case fails CLOSED); need_of and first
+ *   stay the walk's.
+ *  7. With d_cost / d_safe: cost[m][FO_C_RES0] = decel[m], cost[m][FO_C_RES1] = (double)user[m]; if need[m] == L or
+ *   decel[m] > a_limit: safe[m] = 0 and cost[m][FO_C_SAFE] = 0.0, otherwise both are left as found -- the stage only ever takes
+ *   safety away; with a_limit = +inf only "no level" and non-finite candidates lose it; a row that a refused rule list or an
+ *   unusable covariance poisoned keeps its NaNs and safe = 0 and gets the two columns.  No other column is touched.
+ *  Outputs, every byte written by every call: d_need, d_at, d_blocking, d_user [M] int32; d_decel [M] float64; d_need_of, d_first
+ *   [C][M] int32.
+ *  Safety of the data: as fo_scene_hidden_brake_ladder_users; finite may hold anything, no index depends on it.
+ *  Not claimed: what fo_scene_hidden_brake_ladder_users does not claim; brake starts b >= B are not looked at; the answer is only as
+ *   fine as the ladder; that cost / safe belong to the same candidates is the caller's word.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_ladder_verdict:"), in this order: K outside [1, 3]; C outside [1, 8]; no h_thr; a window outside
+ * [1, 32768]^2; an r2_cap[k], k < K, negative or beyond FO_HIDDEN_REACH_MAX_HALO; map_of[c], c < C, outside [0, K); M < 0; L outside
+ * [1, 64]; no h_levels; a level negative or not finite; levels that are not strictly ascending; dt not positive and finite; a_limit
+ * negative or NaN; with M > 0: T outside [1, 254]; B outside [1, T]; C * T > FO_HIDDEN_BRAKE_MAX_TABLE;
+ * 4 * C * T + 8 * L > FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES; a row that is negative, decreases or ends beyond
+ * 169 * r2_cap[map_of[c]]; no d_x / d_y / d_heading; no d_key[k] or d_qmin[k], k < K; no d_v or d_arc; a missing output; only one of
+ * d_cost_or_null / d_safe_or_null; extents refused as by fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  const double *h_levels;                   /* HOST [L] decelerations, m/s^2, strictly ascending */
+  int32_t L;                                /* levels */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  double dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  double a_limit;                           /* decel above it takes safety away; +inf: only "no level" does */
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC] of the step: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  int32_t *d_need, *d_at, *d_blocking, *d_user;     /* [M] */
+  double *d_decel;                          /* [M] */
+  int32_t *d_need_of, *d_first;             /* [C][M] */
+} fo_hidden_brake_ladder_verdict_t;
+int fo_scene_hidden_brake_ladder_verdict(fo_ctx *ctx, const fo_hidden_brake_ladder_verdict_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

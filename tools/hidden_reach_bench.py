@@ -5,7 +5,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
     python tools/hidden_reach_bench.py [M] [--scene city_grid|scenario1] [--memory] [--calls 25] [--metric euclid|road]
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
                                        [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...] [--brake-ladder K]
-                                       [--brake-ladder-users] [--brake-verdict B]
+                                       [--brake-ladder-users] [--brake-verdict B] [--brake-ladder-verdict B]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -50,8 +50,16 @@ and how ``blocking`` is spread over the users.
 ``commit`` is ``hidden_brake_users``' where it is below B, ``first`` is its ``first``, ``fail_safe`` and ``user`` are their fold.  Also
 the poses the walks scanned.
 
+``--brake-ladder-verdict B``: ``hidden_brake_ladder_verdict`` for the README's road users at the interface's default ladder 0.5, 1.0, ...
+11.5 over the first B brake starts (§5.10 "Ladder verdict") -- the whole call, the call with the poses handed over, and the ONE launch
+alone (the structure a call left, fold included, handed to the C entry again) -- next to what the launch replaces: ``hidden_brake_ladder_users``
+at the same B followed by the torch reduction over b, and ``hidden_brake_verdict`` at the single level ``a_max``.  In every run the tie
+is asserted (exact integers, ``decel`` bit for bit): the outputs are that reduction of the ladder-users entry's.  Also the distribution
+of ``need``.
+
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
+import ctypes as C
 import json
 import math
 import os
@@ -64,6 +72,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "frenetix-occlusion_amd")]
 from frenetix_occlusion import _native as N  # noqa: E402
 from frenetix_occlusion import scenario as SC, synthetic as SY  # noqa: E402
+from frenetix_occlusion.hidden_traffic import default_brake_ladder  # noqa: E402
 from frenetix_occlusion.sensor_model import SensorModel  # noqa: E402
 from frenetix_occlusion.utils.fo_obstacle import FOObstacles  # noqa: E402
 
@@ -106,6 +115,9 @@ def main():
                     help="time hidden_brake_ladder_users for the README's three road users next to one hidden_brake_ladder call per user")
     ap.add_argument("--brake-verdict", type=int, default=None, metavar="B",
                     help="time hidden_brake_verdict over the first B brake starts (and over all) next to hidden_brake_users")
+    ap.add_argument("--brake-ladder-verdict", type=int, default=None, metavar="B",
+                    help="time hidden_brake_ladder_verdict over the first B brake starts next to hidden_brake_ladder_users + its reduction "
+                         "and to hidden_brake_verdict at one level")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -277,6 +289,65 @@ def main():
             res[f"candidates_by_user_B{B}"] = {str(c): int((v_out.user == c).sum()) for c in range(-2, len(users))}
         res["hidden_poses_call_ms"] = _median_ms(lambda: sm.hidden_poses(tx, ty, tth, tv), a.calls)
         res["brake_users_call_ms"] = _median_ms(hbu, a.calls)
+    if a.brake_ladder_verdict:
+        users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
+        a_max = SY.VEHICLE_BMW320I[4]
+        B = a.brake_ladder_verdict
+        if not 1 <= B <= T:
+            ap.error(f"--brake-ladder-verdict B: 1 <= B <= {T}")
+        levels = np.array(default_brake_ladder(a_max, "hidden_brake_ladder_verdict"))
+        L = len(levels)
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hblv = lambda **kw: sm.hidden_brake_ladder_verdict(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, levels=levels, starts=B,
+                                                           a_limit=a_max, **kw)
+        hblu = lambda **kw: sm.hidden_brake_ladder_users(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, decelerations=levels, starts=B, **kw)
+        hbv = lambda **kw: sm.hidden_brake_verdict(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_max, starts=B, commit_min=B, **kw)
+        levels_inf = torch.as_tensor(np.append(levels, np.inf), device=dev)
+
+        def reduce_over_b(lu, finite=None):         # steps 1 - 6 as torch ops on the ladder-users outputs (no lengths here: ends = B)
+            rank = torch.where(lu.required_all >= 0, lu.required_all, L)
+            need = rank.amax(dim=1)
+            at = (rank == need[:, None]).to(torch.int8).argmax(dim=1)
+            blocking = lu.blocking.gather(1, at[:, None])[:, 0]
+            low = blocking & -blocking
+            user = torch.where(blocking != 0, torch.log2(low.clamp(min=1).to(torch.float64)).to(torch.int64), -1)
+            need_of = torch.where(lu.required >= 0, lu.required, L).amax(dim=2)
+            if finite is not None:
+                bad = finite == 0
+                need, at, blocking, user = need.masked_fill(bad, L), at.masked_fill(bad, 0), blocking.masked_fill(bad, 0), user.masked_fill(bad, -2)
+            return need, at, blocking, user, levels_inf[need.to(torch.int64)], need_of
+
+        v_out = hblv()
+        # the tie, in every run: the ladder-users entry on the verdict's own headings and on host x, y, whose arc numpy sums as the device does
+        lu = sm.hidden_brake_ladder_users(traj["x"], traj["y"], None, tv, vehicle=veh, users=users, dt=0.1, decelerations=levels, starts=B,
+                                          heading=v_out.poses.heading)
+        assert torch.equal(lu.arc, v_out.poses.arc)
+        need, at, blocking, user, decel, need_of = reduce_over_b(lu, v_out.poses.finite)
+        for name, want in (("need", need), ("at", at), ("blocking", blocking), ("user", user), ("need_of", need_of), ("first", lu.first)):
+            assert torch.equal(getattr(v_out, name).to(torch.int64), want.to(torch.int64)), name
+        assert torch.equal(v_out.decel.view(torch.int64), decel.view(torch.int64))
+        # the launch alone: one more call that folds into a scratch cost / safe pair, then the structure it left handed to the C entry again
+        # (its tensors stay referenced by sm and by keep while it is timed); the fold's stores are part of the figure
+        scratch = (torch.zeros((M, N.NC), dtype=torch.float64, device=dev), torch.ones((M,), dtype=torch.uint8, device=dev))
+        keep = hblv(poses=v_out.poses, cost=scratch[0], safe=scratch[1])
+        launch = (C.byref(sm._hblv_args), N.current_stream(sm._dev_index))
+        assert torch.equal(scratch[0][:, 14].view(torch.int64), v_out.decel.view(torch.int64)) and int(scratch[1].sum()) == int((v_out.decel <= a_max).sum())
+        res["brake_ladder_verdict_users"] = [list(u) for u in users]
+        res["brake_ladder_verdict_levels"] = [float(v) for v in levels]
+        res["brake_ladder_verdict_B"] = B
+        res["brake_ladder_verdict_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_ladder_verdict", *launch), a.calls)
+        assert all(torch.equal(getattr(keep, n), getattr(v_out, n)) for n in ("need", "at", "blocking", "user", "decel", "need_of", "first"))
+        res["brake_ladder_verdict_call_ms"] = _median_ms(hblv, a.calls)
+        res["brake_ladder_verdict_call_reused_poses_ms"] = _median_ms(lambda: hblv(poses=v_out.poses), a.calls)
+        res["brake_ladder_users_call_ms"] = _median_ms(hblu, a.calls)
+        res["brake_ladder_users_call_plus_reduction_ms"] = _median_ms(lambda: reduce_over_b(hblu()), a.calls)
+        res["brake_ladder_users_call_reused_heading_plus_reduction_ms"] = _median_ms(lambda: reduce_over_b(hblu(heading=v_out.poses.heading)), a.calls)
+        res["brake_verdict_call_ms"] = _median_ms(hbv, a.calls)
+        res["brake_verdict_call_reused_poses_ms"] = _median_ms(lambda: hbv(poses=v_out.poses), a.calls)
+        res["candidates_by_need"] = {str(k): int((v_out.need == k).sum()) for k in range(-1, L + 1)}
+        res["candidates_by_ladder_user"] = {str(c): int((v_out.user == c).sum()) for c in range(-2, len(users))}
+        res["candidates_above_a_limit"] = int((v_out.decel > a_max).sum())
+        res["candidates_by_at"] = {str(k): int((v_out.at == k).sum()) for k in range(-1, B)}
     if a.brake_ladder:
         a_top = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
         levels = np.linspace(0.5, a_top, a.brake_ladder) if a.brake_ladder > 1 else np.array([a_top])
