@@ -149,16 +149,19 @@ class HiddenBrakeClasses(C.Structure):  # fo_hidden_brake_classes_t
 
 HIDDEN_BRAKE_MAX_MAPS = 3       # FO_HIDDEN_BRAKE_MAX_MAPS: key maps (forecasts) one fo_scene_hidden_brake_users call walks over
 
+# the members the four structures of the users family (brake_users, ladder_users, verdict, ladder_verdict) begin with, up to d_arc
+_HIDDEN_USERS_HEAD = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
+                      ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
+                      ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
+                      ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
+                      ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
+                      ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p)]
+
 
 class HiddenBrakeUsers(C.Structure):    # fo_hidden_brake_users_t
-    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
-                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
-                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
-                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
-                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
-                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
-                ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
-                ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
+    _fields_ = _HIDDEN_USERS_HEAD + [
+        ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)),
+        ("d_brake_first", C.c_void_p), ("d_stop", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
 
 
 HIDDEN_BRAKE_MAX_LEVELS = 64    # FO_HIDDEN_BRAKE_MAX_LEVELS: decelerations one fo_scene_hidden_brake_ladder call evaluates
@@ -175,16 +178,11 @@ HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES = 3584
 
 
 class HiddenBrakeLadderUsers(C.Structure):      # fo_hidden_brake_ladder_users_t
-    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
-                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
-                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
-                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
-                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
-                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
-                ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
-                ("h_thr", C.POINTER(C.c_int32)), ("d_required", C.c_void_p), ("d_last_unclear", C.c_void_p), ("d_commit", C.c_void_p),
-                ("d_first", C.c_void_p), ("d_required_all", C.c_void_p), ("d_last_unclear_all", C.c_void_p), ("d_blocking", C.c_void_p),
-                ("d_brake_first_or_null", C.c_void_p), ("d_stop_or_null", C.c_void_p)]
+    _fields_ = _HIDDEN_USERS_HEAD + [
+        ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
+        ("h_thr", C.POINTER(C.c_int32)), ("d_required", C.c_void_p), ("d_last_unclear", C.c_void_p), ("d_commit", C.c_void_p),
+        ("d_first", C.c_void_p), ("d_required_all", C.c_void_p), ("d_last_unclear_all", C.c_void_p), ("d_blocking", C.c_void_p),
+        ("d_brake_first_or_null", C.c_void_p), ("d_stop_or_null", C.c_void_p)]
 
 
 class HiddenPoses(C.Structure):         # fo_hidden_poses_t
@@ -197,30 +195,20 @@ HIDDEN_VERDICT_NOT_FINITE = -2  # FO_HIDDEN_VERDICT_NOT_FINITE: user[m] of a can
 
 
 class HiddenBrakeVerdict(C.Structure):  # fo_hidden_brake_verdict_t
-    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
-                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
-                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
-                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
-                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
-                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
-                ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)), ("B", C.c_int32),
-                ("commit_min", C.c_int32), ("d_finite_or_null", C.c_void_p), ("d_cost_or_null", C.c_void_p),
-                ("d_safe_or_null", C.c_void_p), ("d_fail_safe", C.c_void_p), ("d_user", C.c_void_p), ("d_commit", C.c_void_p),
-                ("d_first", C.c_void_p)]
+    _fields_ = _HIDDEN_USERS_HEAD + [
+        ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)), ("B", C.c_int32),
+        ("commit_min", C.c_int32), ("d_finite_or_null", C.c_void_p), ("d_cost_or_null", C.c_void_p),
+        ("d_safe_or_null", C.c_void_p), ("d_fail_safe", C.c_void_p), ("d_user", C.c_void_p), ("d_commit", C.c_void_p),
+        ("d_first", C.c_void_p)]
 
 
 class HiddenBrakeLadderVerdict(C.Structure):    # fo_hidden_brake_ladder_verdict_t
-    _fields_ = [("M", C.c_int32), ("T", C.c_int32), ("d_x", C.c_void_p), ("d_y", C.c_void_p), ("d_heading", C.c_void_p),
-                ("d_len_or_null", C.c_void_p), ("hl", C.c_double), ("hw", C.c_double), ("wb", C.c_double),
-                ("win_ix0", C.c_int32), ("win_iy0", C.c_int32), ("win_nx", C.c_int32), ("win_ny", C.c_int32),
-                ("K", C.c_int32), ("C", C.c_int32), ("d_key", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS),
-                ("d_qmin", C.c_void_p * HIDDEN_BRAKE_MAX_MAPS), ("r2_cap", C.c_int32 * HIDDEN_BRAKE_MAX_MAPS),
-                ("map_of", C.c_int32 * HIDDEN_BRAKE_MAX_CLASSES), ("d_v", C.c_void_p), ("d_arc", C.c_void_p),
-                ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
-                ("h_thr", C.POINTER(C.c_int32)), ("a_limit", C.c_double), ("d_finite_or_null", C.c_void_p),
-                ("d_cost_or_null", C.c_void_p), ("d_safe_or_null", C.c_void_p), ("d_need", C.c_void_p), ("d_at", C.c_void_p),
-                ("d_blocking", C.c_void_p), ("d_user", C.c_void_p), ("d_decel", C.c_void_p), ("d_need_of", C.c_void_p),
-                ("d_first", C.c_void_p)]
+    _fields_ = _HIDDEN_USERS_HEAD + [
+        ("h_levels", C.POINTER(C.c_double)), ("L", C.c_int32), ("B", C.c_int32), ("dt", C.c_double),
+        ("h_thr", C.POINTER(C.c_int32)), ("a_limit", C.c_double), ("d_finite_or_null", C.c_void_p),
+        ("d_cost_or_null", C.c_void_p), ("d_safe_or_null", C.c_void_p), ("d_need", C.c_void_p), ("d_at", C.c_void_p),
+        ("d_blocking", C.c_void_p), ("d_user", C.c_void_p), ("d_decel", C.c_void_p), ("d_need_of", C.c_void_p),
+        ("d_first", C.c_void_p)]
 
 
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches

@@ -410,6 +410,20 @@ def travelled_arc(x, y):
     return np.insert(np.cumsum(seg, axis=-1), 0, 0.0, axis=-1)
 
 
+def _device_arc(x, y, dev):
+    """:func:`travelled_arc` of a brake entry's candidates on ``dev``: made where ``x`` and ``y`` both live, host arrays' uploaded"""
+    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
+    return N.on_device(arc, dev)
+
+
+def _a_brake(a_brake, fn):
+    """the deceleration of ``fn``'s manoeuvre as a float, or its refusal"""
+    a_brake = float(a_brake)
+    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
+        raise ValueError(f"{fn}: a_brake >= 0 and finite")
+    return a_brake
+
+
 def _decided_until(stop, lengths):
     """``decided_until`` of :class:`HiddenBrake` and :class:`HiddenBrakeClasses`: ``stop [M, T]`` does not depend on the hidden road
     user"""
@@ -471,13 +485,10 @@ def hidden_brake(self, x, y, theta, v, *, vehicle, v_max, dt, a_brake, margin=No
     M, T = (int(a) for a in tx.shape)
     if tuple(v.shape) != (M, T):
         raise ValueError("hidden_brake: v must be [M, T]")
-    a_brake = float(a_brake)
-    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
-        raise ValueError("hidden_brake: a_brake >= 0 and finite")
+    a_brake = _a_brake(a_brake, "hidden_brake")
     dev, w = self.device, reach.window
     tv = N.on_device(v, dev)
-    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
-    arc = N.on_device(arc, dev)
+    arc = _device_arc(x, y, dev)
     brake_first = torch.empty((M, T), dtype=torch.int32, device=dev)
     stop = torch.empty((M, T), dtype=torch.int32, device=dev)
     commit = torch.empty(M, dtype=torch.int32, device=dev)
@@ -605,8 +616,7 @@ def hidden_brake_ladder(self, x, y, theta, v, *, vehicle, v_max, dt, deceleratio
     B, K = _ladder_starts(starts, T, "hidden_brake_ladder"), len(levels)
     dev, w = self.device, reach.window
     tv = N.on_device(v, dev)
-    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
-    arc = N.on_device(arc, dev)
+    arc = _device_arc(x, y, dev)
     brake_first = torch.empty((M, B, K), dtype=torch.int32, device=dev)
     stop = torch.empty((M, B, K), dtype=torch.int32, device=dev)
     required = torch.empty((M, B), dtype=torch.int32, device=dev)
@@ -693,14 +703,11 @@ def hidden_brake_classes(self, x, y, theta, v, *, vehicle, speeds, dt, a_brake, 
     M, T = (int(a) for a in tx.shape)
     if tuple(v.shape) != (M, T):
         raise ValueError("hidden_brake_classes: v must be [M, T]")
-    a_brake = float(a_brake)
-    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
-        raise ValueError("hidden_brake_classes: a_brake >= 0 and finite")
+    a_brake = _a_brake(a_brake, "hidden_brake_classes")
     dev, w, C_ = self.device, clearance.window, len(speeds)
     thr = hidden_brake_thresholds(speeds, clearance.dt, clearance.margin, clearance.cell_size, T)
     tv = N.on_device(v, dev)
-    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
-    arc = N.on_device(arc, dev)
+    arc = _device_arc(x, y, dev)
     brake_first = torch.empty((C_, M, T), dtype=torch.int32, device=dev)
     stop = torch.empty((M, T), dtype=torch.int32, device=dev)
     commit = torch.empty((C_, M), dtype=torch.int32, device=dev)
@@ -812,6 +819,81 @@ def _users_clearances(self, users, x, y, theta, *, vehicle, dt, margin, inflate,
     return maps, map_of, clearances
 
 
+@dataclass
+class _UsersCall:
+    """what the callers of the users family (hidden_brake_users, its ladder and the two verdicts) prepare alike: the ``clearances``
+    and ``map_of`` of :func:`_users_clearances`, the device inputs ``x, y, heading, lengths`` of the first of them, ``M, T``,
+    the threshold table ``thr`` of the users' speeds, and the half extents ``hl, hw`` and ``wb`` of the ego rectangle"""
+    clearances: tuple
+    map_of: tuple
+    x: torch.Tensor
+    y: torch.Tensor
+    heading: torch.Tensor
+    lengths: Optional[torch.Tensor]
+    M: int
+    T: int
+    thr: np.ndarray
+    hl: float
+    hw: float
+    wb: float
+
+    def fields(self, tv, arc, dt):
+        """the members every structure of the family begins with (``M`` .. ``d_arc``; _native._HIDDEN_USERS_HEAD), ``dt`` and
+        ``h_thr``, as keyword arguments"""
+        cl, w = self.clearances, self.clearances[0].window
+        maps_t, caps_t, classes_t = (C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS,
+                                     C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES)
+        pad = lambda vals: list(vals) + [None] * (N.HIDDEN_BRAKE_MAX_MAPS - len(vals))
+        return dict(M=self.M, T=self.T, d_x=N.ptr(self.x), d_y=N.ptr(self.y), d_heading=N.ptr(self.heading),
+                    d_len_or_null=N.ptr(self.lengths), hl=self.hl, hw=self.hw, wb=self.wb, win_ix0=w.ix0, win_iy0=w.iy0,
+                    win_nx=w.nx, win_ny=w.ny, K=len(cl), C=len(self.map_of),
+                    d_key=maps_t(*pad([c.key.data_ptr() for c in cl])), d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in cl])),
+                    r2_cap=caps_t(*[int(c.r2_cap) for c in cl]), map_of=classes_t(*self.map_of), d_v=N.ptr(tv), d_arc=N.ptr(arc),
+                    dt=float(dt), h_thr=self.thr.ctypes.data_as(C.POINTER(C.c_int32)))
+
+
+def _users_call(self, fn, users, x, y, theta, v, *, vehicle, dt, margin, inflate, lengths, heading=None, poses=None):
+    """the :class:`_UsersCall` of ``fn`` for the ``users`` that :func:`_road_users` let through: runs the clearances, then refuses a
+    ``v`` of another shape.  ``poses``: the :class:`HiddenPoses` a verdict walks on -- the clearances take its heading (no ``theta``),
+    and its arc and finite flag are held to the shape too"""
+    if poses is not None:
+        theta, heading = None, poses.heading
+    _, map_of, clearances = _users_clearances(self, users, x, y, theta, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
+                                              lengths=lengths, heading=heading)
+    M, T = (int(a) for a in self._hc_inputs[0].shape)
+    if poses is None and tuple(v.shape) != (M, T):
+        raise ValueError(f"{fn}: v must be [M, T]")
+    if poses is not None and (tuple(v.shape) != (M, T) or tuple(poses.arc.shape) != (M, T) or tuple(poses.finite.shape) != (M,)):
+        raise ValueError(f"{fn}: v and poses.arc must be [M, T], poses.finite [M]")
+    first_c = clearances[0]
+    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
+    inflate = float(inflate)
+    return _UsersCall(tuple(clearances), map_of, *self._hc_inputs, M, T, thr, 0.5 * length + inflate, 0.5 * width + inflate, wb)
+
+
+def _arg_bytes(users, x, levels, noun, fn):
+    """refuses thresholds and ``levels`` (``noun``: what ``fn`` calls them) that together overflow the kernel argument they travel as"""
+    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
+    if 4 * len(users) * T + 8 * len(levels) > N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES:
+        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds of 4 bytes and {len(levels)} {noun} "
+                         f"of 8 bytes are {4 * len(users) * T + 8 * len(levels)} bytes, at most "
+                         f"{N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES} are possible (they travel as a kernel argument)")
+
+
+def _cost_safe(cost, safe, M, device, fn):
+    """refuses a verdict's ``cost`` / ``safe`` that do not come as a pair or are not the ``M`` rows of a sweep on ``device``"""
+    if (cost is None) != (safe is None):
+        raise ValueError(f"{fn}: cost and safe go together: give both or neither")
+    if cost is not None:
+        ok = (torch.is_tensor(cost) and torch.is_tensor(safe) and cost.device == device == safe.device and cost.dtype == torch.float64
+              and safe.dtype == torch.uint8 and tuple(cost.shape) == (M, N.NC) and tuple(safe.shape) == (M,) and cost.is_contiguous()
+              and safe.is_contiguous())
+        if not ok:
+            raise ValueError(f"{fn}: cost must be a contiguous float64 [M, {N.NC}] and safe a uint8 [M] tensor on the model's device "
+                             "(they are written in place)")
+
+
 def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, margin=None, inflate=0.0, lengths=None, heading=None):
     """Hidden-traffic brake clearance for mixed road users in one walk (``fo_scene_hidden_brake_users``; DESIGN.md §5.10 "Brake
     clearance by road users"): ``users`` is a sequence of 1 .. 8 ``(speed, metric, flow)`` -- say ``(2.0, "road", "any")`` for a
@@ -821,42 +903,22 @@ def hidden_brake_users(self, x, y, theta, v, *, vehicle, users, dt, a_brake, mar
     (candidate, b) once and decides it for every user on that user's key map; returns a :class:`HiddenBrakeUsers`.
     ``len(users) * T`` may not exceed ``_native.HIDDEN_BRAKE_MAX_TABLE``.  The other arguments as for :meth:`hidden_brake_classes`.
     Nothing is read back and nobody waits for the kernels."""
-    users = _road_users(users, x, "hidden_brake_users")
-    maps, map_of, clearances = _users_clearances(self, users, x, y, theta, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
-                                                 lengths=lengths, heading=heading)
-    tx, ty, thead, tlen = self._hc_inputs
-    M, T = (int(a) for a in tx.shape)
-    if tuple(v.shape) != (M, T):
-        raise ValueError("hidden_brake_users: v must be [M, T]")
-    a_brake = float(a_brake)
-    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
-        raise ValueError("hidden_brake_users: a_brake >= 0 and finite")
-    first_c = clearances[0]
-    dev, w, C_, K_ = self.device, first_c.window, len(users), len(maps)
-    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    fn = "hidden_brake_users"
+    users = _road_users(users, x, fn)
+    p = _users_call(self, fn, users, x, y, theta, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths,
+                    heading=heading)
+    a_brake = _a_brake(a_brake, fn)
+    dev, M, T, C_ = self.device, p.M, p.T, len(users)
     tv = N.on_device(v, dev)
-    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
-    arc = N.on_device(arc, dev)
-    brake_first = torch.empty((C_, M, T), dtype=torch.int32, device=dev)
-    stop = torch.empty((M, T), dtype=torch.int32, device=dev)
-    commit = torch.empty((C_, M), dtype=torch.int32, device=dev)
-    first = torch.empty((C_, M), dtype=torch.int32, device=dev)
-    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
-    inflate = float(inflate)
-    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
-    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
-    args = N.HiddenBrakeUsers(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
-                              hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
-                              win_ny=w.ny, K=K_, C=C_, d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                              d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                              r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
-                              map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(arc), a_brake=a_brake, dt=float(dt),
-                              h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), d_brake_first=N.ptr(brake_first), d_stop=N.ptr(stop),
+    arc = _device_arc(x, y, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    brake_first, stop, commit, first = new(C_, M, T), new(M, T), new(C_, M), new(C_, M)
+    args = N.HiddenBrakeUsers(**p.fields(tv, arc, dt), a_brake=a_brake, d_brake_first=N.ptr(brake_first), d_stop=N.ptr(stop),
                               d_commit=N.ptr(commit), d_first=N.ptr(first))
     self.ctx.call("fo_scene_hidden_brake_users", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_classes -- the clearances' maps too: the caller may drop the result)
-    self._hbu_inputs = (tv, arc, tuple(clearances))
-    return HiddenBrakeUsers(tuple(clearances), users, map_of, thr, brake_first, stop, commit, first, arc, a_brake, float(dt), tlen)
+    self._hbu_inputs = (tv, arc, p.clearances)
+    return HiddenBrakeUsers(p.clearances, users, p.map_of, p.thr, brake_first, stop, commit, first, arc, a_brake, float(dt), p.lengths)
 
 
 @dataclass
@@ -947,49 +1009,26 @@ def hidden_brake_ladder_users(self, x, y, theta, v, *, vehicle, users, dt, decel
     fn = "hidden_brake_ladder_users"
     users = _road_users(users, x, fn)
     levels = _ladder_levels(decelerations, fn)
-    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
-    if 4 * len(users) * T + 8 * len(levels) > N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES:
-        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds of 4 bytes and {len(levels)} decelerations "
-                         f"of 8 bytes are {4 * len(users) * T + 8 * len(levels)} bytes, at most "
-                         f"{N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES} are possible (they travel as a kernel argument)")
-    maps, map_of, clearances = _users_clearances(self, users, x, y, theta, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
-                                                 lengths=lengths, heading=heading)
-    tx, ty, thead, tlen = self._hc_inputs
-    M, T = (int(a) for a in tx.shape)
-    if tuple(v.shape) != (M, T):
-        raise ValueError(f"{fn}: v must be [M, T]")
-    B = _ladder_starts(starts, T, fn)
-    first_c = clearances[0]
-    dev, w, C_, K_, L_ = self.device, first_c.window, len(users), len(maps), len(levels)
-    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    _arg_bytes(users, x, levels, "decelerations", fn)
+    p = _users_call(self, fn, users, x, y, theta, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths,
+                    heading=heading)
+    B = _ladder_starts(starts, p.T, fn)
+    dev, M, C_, L_ = self.device, p.M, len(users), len(levels)
     tv = N.on_device(v, dev)
-    arc = travelled_arc(x, y) if torch.is_tensor(x) and torch.is_tensor(y) else travelled_arc(np.asarray(x), np.asarray(y))
-    arc = N.on_device(arc, dev)
+    arc = _device_arc(x, y, dev)
     new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     required, last_unclear, commit, first = new(C_, M, B), new(C_, M, B), new(C_, M, L_), new(C_, M)
     required_all, last_unclear_all, blocking = new(M, B), new(M, B), new(M, B)
     brake_first, stop = (new(C_, M, B, L_), new(M, B, L_)) if detail else (None, None)
-    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
-    inflate = float(inflate)
-    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
-    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
-    args = N.HiddenBrakeLadderUsers(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
-                                    hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0,
-                                    win_nx=w.nx, win_ny=w.ny, K=K_, C=C_,
-                                    d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                    d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                    r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
-                                    map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(arc),
-                                    h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B, dt=float(dt),
-                                    h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), d_required=N.ptr(required),
-                                    d_last_unclear=N.ptr(last_unclear), d_commit=N.ptr(commit), d_first=N.ptr(first),
-                                    d_required_all=N.ptr(required_all), d_last_unclear_all=N.ptr(last_unclear_all),
+    args = N.HiddenBrakeLadderUsers(**p.fields(tv, arc, dt), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B,
+                                    d_required=N.ptr(required), d_last_unclear=N.ptr(last_unclear), d_commit=N.ptr(commit),
+                                    d_first=N.ptr(first), d_required_all=N.ptr(required_all), d_last_unclear_all=N.ptr(last_unclear_all),
                                     d_blocking=N.ptr(blocking), d_brake_first_or_null=N.ptr(brake_first), d_stop_or_null=N.ptr(stop))
     self.ctx.call("fo_scene_hidden_brake_ladder_users", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
-    self._hblu_inputs = (tv, arc, tuple(clearances))
-    return HiddenBrakeLadderUsers(tuple(clearances), users, map_of, thr, levels, required, last_unclear, commit, first, required_all,
-                                  last_unclear_all, blocking, brake_first, stop, arc, float(dt), tlen)
+    self._hblu_inputs = (tv, arc, p.clearances)
+    return HiddenBrakeLadderUsers(p.clearances, users, p.map_of, p.thr, levels, required, last_unclear, commit, first, required_all,
+                                  last_unclear_all, blocking, brake_first, stop, arc, float(dt), p.lengths)
 
 
 @dataclass
@@ -1074,52 +1113,24 @@ def hidden_brake_verdict(self, x, y, theta, v, *, vehicle, users, dt, a_brake, s
     users = _road_users(users, x, fn)
     if poses is None:
         poses = hidden_poses(self, x, y, theta, v, lengths)
-    maps, map_of, clearances = _users_clearances(self, users, x, y, None, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
-                                                 lengths=lengths, heading=poses.heading)
-    tx, ty, thead, tlen = self._hc_inputs
-    M, T = (int(a) for a in tx.shape)
-    if tuple(v.shape) != (M, T) or tuple(poses.arc.shape) != (M, T) or tuple(poses.finite.shape) != (M,):
-        raise ValueError(f"{fn}: v and poses.arc must be [M, T], poses.finite [M]")
-    a_brake = float(a_brake)
-    if not (a_brake >= 0.0 and math.isfinite(a_brake)):
-        raise ValueError(f"{fn}: a_brake >= 0 and finite")
-    B = _ladder_starts(starts, T, fn)
+    p = _users_call(self, fn, users, x, y, None, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+    a_brake = _a_brake(a_brake, fn)
+    B = _ladder_starts(starts, p.T, fn)
     if isinstance(commit_min, bool) or not isinstance(commit_min, (int, np.integer)) or not 0 <= int(commit_min) <= B:
         raise ValueError(f"{fn}: commit_min = {commit_min!r}, an integer in [0, starts = {B}]")
     commit_min = int(commit_min)
-    dev = self.device
-    if (cost is None) != (safe is None):
-        raise ValueError(f"{fn}: cost and safe go together: give both or neither")
-    if cost is not None:
-        ok = (torch.is_tensor(cost) and torch.is_tensor(safe) and cost.device == tx.device == safe.device and cost.dtype == torch.float64
-              and safe.dtype == torch.uint8 and tuple(cost.shape) == (M, N.NC) and tuple(safe.shape) == (M,) and cost.is_contiguous()
-              and safe.is_contiguous())
-        if not ok:
-            raise ValueError(f"{fn}: cost must be a contiguous float64 [M, {N.NC}] and safe a uint8 [M] tensor on the model's device "
-                             "(they are written in place)")
-    first_c = clearances[0]
-    w, C_, K_ = first_c.window, len(users), len(maps)
-    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    dev, M, C_ = self.device, p.M, len(users)
+    _cost_safe(cost, safe, M, p.x.device, fn)
     tv = N.on_device(v, dev)
     new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     fail_safe, user, commit, first = new(M), new(M), new(C_, M), new(C_, M)
-    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
-    inflate = float(inflate)
-    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
-    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
-    args = N.HiddenBrakeVerdict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
-                                hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0, win_nx=w.nx,
-                                win_ny=w.ny, K=K_, C=C_, d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
-                                map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(poses.arc), a_brake=a_brake, dt=float(dt),
-                                h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), B=B, commit_min=commit_min,
+    args = N.HiddenBrakeVerdict(**p.fields(tv, poses.arc, dt), a_brake=a_brake, B=B, commit_min=commit_min,
                                 d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe),
                                 d_fail_safe=N.ptr(fail_safe), d_user=N.ptr(user), d_commit=N.ptr(commit), d_first=N.ptr(first))
     self.ctx.call("fo_scene_hidden_brake_verdict", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
-    self._hbv_inputs = (tv, poses, tuple(clearances), cost, safe)
-    return HiddenBrakeVerdict(fail_safe, user, commit, first, poses, B, commit_min, users, map_of, thr, tuple(clearances))
+    self._hbv_inputs = (tv, poses, p.clearances, cost, safe)
+    return HiddenBrakeVerdict(fail_safe, user, commit, first, poses, B, commit_min, users, p.map_of, p.thr, p.clearances)
 
 
 @dataclass
@@ -1195,56 +1206,24 @@ def hidden_brake_ladder_verdict(self, x, y, theta, v, *, vehicle, users, dt, lev
             raise ValueError(f"{fn}: the default levels run up to a_limit, which is not finite: hand levels over")
         levels = default_brake_ladder(a_limit, fn)
     levels = _ladder_levels(levels, fn)
-    T = int(x.shape[1]) if len(getattr(x, "shape", ())) == 2 else 0
-    if 4 * len(users) * T + 8 * len(levels) > N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES:
-        raise ValueError(f"{fn}: {len(users)} users x {T} samples = {len(users) * T} thresholds of 4 bytes and {len(levels)} levels "
-                         f"of 8 bytes are {4 * len(users) * T + 8 * len(levels)} bytes, at most "
-                         f"{N.HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES} are possible (they travel as a kernel argument)")
+    _arg_bytes(users, x, levels, "levels", fn)
     if poses is None:
         poses = hidden_poses(self, x, y, theta, v, lengths)
-    maps, map_of, clearances = _users_clearances(self, users, x, y, None, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate,
-                                                 lengths=lengths, heading=poses.heading)
-    tx, ty, thead, tlen = self._hc_inputs
-    M, T = (int(a) for a in tx.shape)
-    if tuple(v.shape) != (M, T) or tuple(poses.arc.shape) != (M, T) or tuple(poses.finite.shape) != (M,):
-        raise ValueError(f"{fn}: v and poses.arc must be [M, T], poses.finite [M]")
-    B = _ladder_starts(starts, T, fn)
-    dev = self.device
-    if (cost is None) != (safe is None):
-        raise ValueError(f"{fn}: cost and safe go together: give both or neither")
-    if cost is not None:
-        ok = (torch.is_tensor(cost) and torch.is_tensor(safe) and cost.device == tx.device == safe.device and cost.dtype == torch.float64
-              and safe.dtype == torch.uint8 and tuple(cost.shape) == (M, N.NC) and tuple(safe.shape) == (M,) and cost.is_contiguous()
-              and safe.is_contiguous())
-        if not ok:
-            raise ValueError(f"{fn}: cost must be a contiguous float64 [M, {N.NC}] and safe a uint8 [M] tensor on the model's device "
-                             "(they are written in place)")
-    first_c = clearances[0]
-    w, C_, K_, L_ = first_c.window, len(users), len(maps), len(levels)
-    thr = hidden_brake_thresholds([s for s, _, _ in users], first_c.dt, first_c.margin, first_c.cell_size, T)
+    p = _users_call(self, fn, users, x, y, None, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+    B = _ladder_starts(starts, p.T, fn)
+    dev, M, C_, L_ = self.device, p.M, len(users), len(levels)
+    _cost_safe(cost, safe, M, p.x.device, fn)
     tv = N.on_device(v, dev)
     new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
     need, at, blocking, user, need_of, first = new(M), new(M), new(M), new(M), new(C_, M), new(C_, M)
     decel = torch.empty((M,), dtype=torch.float64, device=dev)
-    length, width, wb = (float(a) for a in tuple(vehicle)[:3])
-    inflate = float(inflate)
-    pad = lambda vals, n: list(vals) + [None] * (n - len(vals))
-    maps_t, classes_t = C.c_void_p * N.HIDDEN_BRAKE_MAX_MAPS, C.c_int32 * N.HIDDEN_BRAKE_MAX_CLASSES
-    args = N.HiddenBrakeLadderVerdict(M=M, T=T, d_x=N.ptr(tx), d_y=N.ptr(ty), d_heading=N.ptr(thead), d_len_or_null=N.ptr(tlen),
-                                      hl=0.5 * length + inflate, hw=0.5 * width + inflate, wb=wb, win_ix0=w.ix0, win_iy0=w.iy0,
-                                      win_nx=w.nx, win_ny=w.ny, K=K_, C=C_,
-                                      d_key=maps_t(*pad([c.key.data_ptr() for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                      d_qmin=maps_t(*pad([N.ptr(c.qmin) for c in clearances], N.HIDDEN_BRAKE_MAX_MAPS)),
-                                      r2_cap=(C.c_int32 * N.HIDDEN_BRAKE_MAX_MAPS)(*[int(c.r2_cap) for c in clearances]),
-                                      map_of=classes_t(*map_of), d_v=N.ptr(tv), d_arc=N.ptr(poses.arc),
-                                      h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B, dt=float(dt),
-                                      h_thr=thr.ctypes.data_as(C.POINTER(C.c_int32)), a_limit=a_limit,
-                                      d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe),
-                                      d_need=N.ptr(need), d_at=N.ptr(at), d_blocking=N.ptr(blocking), d_user=N.ptr(user),
-                                      d_decel=N.ptr(decel), d_need_of=N.ptr(need_of), d_first=N.ptr(first))
+    args = N.HiddenBrakeLadderVerdict(**p.fields(tv, poses.arc, dt), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B,
+                                      a_limit=a_limit, d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost),
+                                      d_safe_or_null=N.ptr(safe), d_need=N.ptr(need), d_at=N.ptr(at), d_blocking=N.ptr(blocking),
+                                      d_user=N.ptr(user), d_decel=N.ptr(decel), d_need_of=N.ptr(need_of), d_first=N.ptr(first))
     self.ctx.call("fo_scene_hidden_brake_ladder_verdict", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
-    self._hblv_inputs = (tv, poses, tuple(clearances), cost, safe)
+    self._hblv_inputs = (tv, poses, p.clearances, cost, safe)
     self._hblv_args = args                                  # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
-    return HiddenBrakeLadderVerdict(need, at, blocking, user, decel, need_of, first, levels, B, a_limit, users, poses, map_of, thr,
-                                    tuple(clearances))
+    return HiddenBrakeLadderVerdict(need, at, blocking, user, decel, need_of, first, levels, B, a_limit, users, poses, p.map_of, p.thr,
+                                    p.clearances)
