@@ -11,8 +11,10 @@ namespace {
 // stop below 0.1) and the brake threat number decel / a_max.  For one candidate deceleration the ego keeps its path,
 // the speed profile becomes [v0, max(v1 - decel j dt, 0) ...], poses are re-sampled by linear interpolation over the
 // travelled chord length (scipy interp1d semantics: searchsorted-left segment, clipped), rectangles are tested for
-// intersection (SAT, touching counts) at every step the agent exists.  Where the re-sampled arc length exceeds the
-// path length the reference raises ValueError; here it is clamped to the end of the path.
+// intersection (SAT, touching counts) at every step the agent exists.  Two deviations from the reference: where the
+// re-sampled arc length exceeds the path length the reference raises ValueError; here it is clamped to the end of the
+// path.  On a path segment of zero length (two samples at one place: an ego that stands) scipy divides by zero and returns
+// NaN; here the segment gives its left knot -- the pose, heading included, of the earlier of the two samples.
 __global__ void fo_be_prep_kernel(int M, int Mp, int T, const double *__restrict__ x, const double *__restrict__ y,
                                   const double *__restrict__ acc, double *__restrict__ dist, double *__restrict__ mina) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
