@@ -1,7 +1,15 @@
 // fo_hidden_brake.hpp -- hidden-traffic brake clearance (fo_scene_hidden_brake; DESIGN.md §5.10 "Brake clearance"): from which
 // sample on "follow the candidate until here, then brake" no longer keeps the moving ego out of road hidden traffic may have
 // reached.  An EXTENSION, not part of the reference.  Included by fo_scene.hip after fo_hidden_reach.hpp (same translation unit,
-// same flags: -ffp-contract=off, which the pose arithmetic and the footprint test need); it scans with fo_hr_scan_pose_rows.
+// same flags: -ffp-contract=off, which the pose arithmetic and the footprint test need).
+//
+// The home of what all seven brake kernels (this one and fo_hidden_brake_{classes,ladder,users,verdict,ladder_users,ladder_verdict}
+// .hpp) share, each piece stated once: the staging of a workgroup's rows (hb_stage_rows), the length clamp (hb_length), the speed
+// profile, the stop sample and the pose step of a manoeuvre (hb_speed, hb_stop_sample, hb_pose_step), the commit rule (hb_unclear)
+// and the shuffle minimum (hb_shfl_min); the box of the scan is fo_hidden_reach.hpp's (fo_hr_scan_box), like the scan itself.
+// What keeps every one of them in range: every LDS index is clamped to [0, Lm) before it is used (hb_pose_step), Lm <= T, the rows
+// are staged under m < M, and fo_hr_scan_pose_rows tests every cell against the window and the raster first: no content of v, arc
+// or a map can make a lane read out of range.  No atomics, no scratch, plain vector stores.
 //
 // Inputs are the arrival map A and d_first of one forecast call (any of the three entries) and, next to its trajectories, the
 // speed v and the travelled chord length arc per sample, handed over as data.  The definition stands in include/fo_hip.h.
@@ -12,9 +20,7 @@
 //                        with arc[j] >= sc is non-decreasing in sc, whatever arc holds).  The walk ends at the first hit, and
 //                        once the ego stands (i >= stop) the pose no longer changes: ONE scan that keeps the smallest arrival
 //                        step of the footprint answers every remaining sample.  commit is a shuffle minimum over the G lanes.
-// The arrival map is read through the caches (the access pattern of fo_hr_traj_kernel).  Every LDS index is clamped to [0, Lm)
-// before it is used and the scan tests every cell against the window and the raster first: no content of v, arc, A or first can
-// make a lane read out of range.  No atomics, no scratch, plain vector stores; every byte of every output is written.
+// The arrival map is read through the caches (the access pattern of fo_hr_traj_kernel).  Every byte of every output is written.
 #pragma once
 #include "fo_hidden_reach.hpp"
 
@@ -39,18 +45,69 @@ struct HrBrakeArgs {
   int32_t *commit;                      // [M]
 };
 
+// The rows x, y, cos, sin, arc, v (T float64 each, in this order) of the per_block trajectories from m0 on, into `rows`; the
+// workgroup's lanes split the elements.  each(t, i) runs once per staged element, t its index in [per_block][T], i in [M][T]: a
+// caller stages its qmin rows in the same pass.  The caller's __syncthreads() follows.
+template <class Args, class F>
+__device__ __forceinline__ void hb_stage_rows(const Args &a, double *rows, long long m0, int per_block, F &&each) {
+  const int T = a.T;
+  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
+    const int su = t / T, k = t - su * T;
+    if (m0 + su < a.M) {
+      const size_t i = (size_t)(m0 + su) * T + k;
+      double *row = rows + (size_t)su * 6 * T + k;
+      row[0] = a.x[i];
+      row[T] = a.y[i];
+      row[2 * T] = a.heading[2 * i];
+      row[3 * T] = a.heading[2 * i + 1];
+      row[4 * T] = a.arc[i];
+      row[5 * T] = a.v[i];
+      each(t, i);
+    }
+  }
+}
+
+// Lm, the samples of trajectory m < M that count: len[m] clamped to [0, T].  (Lanes without a trajectory take Lm = 0 and walk nothing.)
+template <class Args>
+__device__ __forceinline__ int hb_length(const Args &a, long long m) {
+  int Lm = a.T;
+  if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < a.T ? l : a.T); }
+  return Lm;
+}
+
 // vn(i) of a manoeuvre that brakes from sample b at speed vb: be.py's profile, the speed held over a step
 __device__ __forceinline__ double hb_speed(double vb, double a_brake, double dt, int i, int b) {
   return fmax(vb - a_brake * ((double)(i - b) * dt), 0.0);
 }
 
-// The pose step of a manoeuvre, the ONE statement of step 3's arithmetic on the device (fo_hr_brake_kernel and
-// fo_hr_brake_classes_kernel, fo_hidden_brake_classes.hpp, both walk with it): the running length s gains vn(i - 1) dt, the segment
-// index j moves forward to the first sample with arc >= the clamped length, the position is interpolated between the segment's
-// ends and the heading is the nearer end's.  X .. ARC: the trajectory's rows (LDS), Lm >= 2 its length (i = b + 1 < Lm), last =
-// Lm - 1 and arc_end = ARC[last] from the caller; every index is clamped to [0, Lm) before it is used.  (`last` is the caller's
-// value on purpose: with Lm - 1 formed in here as well, fo_hr_brake_kernel's address of ARC[Lm - 1] was selected differently and the
-// kernel, an instruction longer, took 1.4 % more time; written so, its gfx950 assembly is what it was before the step was shared.)
+// the stop sample of the manoeuvre: the first i in [b, Lm) with vn(i) == 0, Lm if the ego never stands
+__device__ __forceinline__ int hb_stop_sample(double vb, double a_brake, double dt, int b, int Lm) {
+  int st = Lm;
+  for (int i = b; i < Lm; ++i)
+    if (hb_speed(vb, a_brake, dt, i, b) == 0.0) { st = i; break; }
+  return st;
+}
+
+// The commit rule: brake start b is unclear when the candidate itself is hit no later than b (fm = first) or the manoeuvre is hit
+// while the ego still moves (bf = its first hit, st = its stop sample)
+__device__ __forceinline__ bool hb_unclear(int fm, int b, int bf, int st) { return (fm >= 0 && fm <= b) || (bf >= 0 && bf < st); }
+
+// v becomes the minimum over the lanes whose index differs in the bits [lo, hi) alone (powers of two, hi <= 64: lanes of one wave).
+// In place on purpose: taking v by value and returning it, the loop over b of fo_hr_brake_kernel kept one more induction variable,
+// the kernel took 66 registers instead of 64 and lost its eighth wave per SIMD (two classes instantiations lost one as well).
+__device__ __forceinline__ void hb_shfl_min(int &v, int lo, int hi) {
+  for (int o = hi >> 1; o >= lo; o >>= 1) {
+    const int w = __shfl_xor(v, o);
+    v = v < w ? v : w;
+  }
+}
+
+// The pose step of a manoeuvre, the ONE statement of step 3's arithmetic on the device: the running length s gains vn(i - 1) dt, the
+// segment index j moves forward to the first sample with arc >= the clamped length, the position is interpolated between the
+// segment's ends and the heading is the nearer end's.  X .. ARC: the trajectory's rows (LDS), Lm >= 2 its length (i = b + 1 < Lm),
+// last = Lm - 1 and arc_end = ARC[last] from the caller; every index is clamped to [0, Lm) before it is used.  (`last` is the
+// caller's value on purpose: with Lm - 1 formed in here as well, fo_hr_brake_kernel's address of ARC[Lm - 1] was selected
+// differently and the kernel, an instruction longer, took 1.4 % more time.)
 struct HbPose { double x, y, c, s; };
 __device__ __forceinline__ HbPose hb_pose_step(const double *X, const double *Y, const double *C, const double *S, const double *ARC,
                                                int Lm, int last, double arc_end, double vb, double a_brake, double dt, int i, int b, double &s,
@@ -80,39 +137,22 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeAr
   const int sub = threadIdx.x / G, kl = threadIdx.x & (G - 1);
   const long long m0 = (long long)blockIdx.x * per_block, m = m0 + sub;
   const bool live = m < a.M;
-  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
-    const int su = t / T, k = t - su * T;
-    if (m0 + su < a.M) {
-      const size_t i = (size_t)(m0 + su) * T + k;
-      double *row = hb_rows + (size_t)su * 6 * T + k;
-      row[0] = a.x[i];
-      row[T] = a.y[i];
-      row[2 * T] = a.heading[2 * i];
-      row[3 * T] = a.heading[2 * i + 1];
-      row[4 * T] = a.arc[i];
-      row[5 * T] = a.v[i];
-    }
-  }
+  hb_stage_rows(a, hb_rows, m0, per_block, [](int, size_t) {});
   __syncthreads();
   const double *X = hb_rows + (size_t)sub * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
   int Lm = 0, fm = -1;
   if (live) {
-    Lm = T;
-    if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < T ? l : T); }
+    Lm = hb_length(a, m);
     fm = a.first[m];
   }
-  // cells beyond the raster and the window have no arrival step: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  const HrBox sb = fo_hr_scan_box(a);
   int commit = 0x7fffffff;
   for (int b = kl; b < T; b += G) {
     int bf = -1, st = -1;
     if (b < Lm) {                       // (Lm = 0 on lanes without a trajectory)
       const int last = Lm - 1;
       const double vb = V[b], arc_end = ARC[last];
-      st = Lm;
-      for (int i = b; i < Lm; ++i)
-        if (hb_speed(vb, a.a_brake, a.dt, i, b) == 0.0) { st = i; break; }
+      st = hb_stop_sample(vb, a.a_brake, a.dt, b, Lm);
       double s = ARC[b];
       int j = 0;
       for (int i = b + 1; i < Lm; ++i) {
@@ -120,7 +160,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeAr
         // the ego stands from sample st on (vn = 0 adds nothing to s): this pose is the manoeuvre's last one
         const bool stands = i >= st;
         int amin = 255;
-        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, A, 255, lox, loy, hix, hiy, 0, 1,
+        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, A, 255, sb.lox, sb.loy, sb.hix, sb.hiy, 0, 1,
                              [&](int av, int, int) { amin = amin < av ? amin : av; });
         if (stands) {                   // hit(i') for i' >= i iff amin <= i'
           const int at = amin > i ? amin : i;
@@ -129,17 +169,14 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_kernel(const HrBrakeAr
         }
         if (amin <= i) { bf = i; break; }
       }
-      if ((fm >= 0 && fm <= b) || (bf >= 0 && bf < st)) commit = commit < b ? commit : b;
+      if (hb_unclear(fm, b, bf, st)) commit = commit < b ? commit : b;
     }
     if (live) {
       a.brake_first[(size_t)m * T + b] = bf;
       a.stop[(size_t)m * T + b] = st;
     }
   }
-  for (int o = G >> 1; o > 0; o >>= 1) {            // lanes of a trajectory are G consecutive lanes of one wave
-    const int c = __shfl_xor(commit, o);
-    commit = commit < c ? commit : c;
-  }
+  hb_shfl_min(commit, 1, G);   // lanes of a trajectory are G consecutive lanes of one wave
   if (live && kl == 0) a.commit[m] = commit == 0x7fffffff ? -1 : commit;
 }
 

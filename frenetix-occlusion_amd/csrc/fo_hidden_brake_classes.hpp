@@ -1,13 +1,13 @@
 // fo_hidden_brake_classes.hpp -- hidden-traffic brake clearance for several road-user speeds in one pass
 // (fo_scene_hidden_brake_classes; DESIGN.md §5.10 "Brake clearance by classes").  An EXTENSION, not part of the reference.
 // Included by fo_scene.hip after fo_hidden_brake.hpp and fo_hidden_clearance.hpp (same translation unit, same flags:
-// -ffp-contract=off); it walks with hb_pose_step and scans with fo_hr_scan_pose_rows.
+// -ffp-contract=off); staging, length, stop sample, pose step, commit rule and shuffle minimum are fo_hidden_brake.hpp's, where the
+// bounds reasoning of all of them stands.
 //
 // Inputs are the key map and qmin of ONE clearance call and a threshold table thr [C][T] = 169 R2_c[j], one row per class of hidden
 // road user.  Per cell A_c(g) <= j iff key(g) <= thr[c][j], so the minimum key under a braking pose decides every class at once:
 // the manoeuvre of (m, b) is walked once, not once per class.  The definition stands in include/fo_hip.h.
-//   fo_hr_brake_classes_kernel<NC>  the shape of fo_hr_brake_kernel: a lane per brake start (m, b), G = brake_group(T) lanes per
-//                        trajectory, the six rows x, y, cos, sin, arc, v in LDS; next to them the trajectory's qmin row and the
+//   fo_hr_brake_classes_kernel<NC>  the lanes of fo_hr_brake_kernel; next to the six rows the trajectory's qmin row and the
 //                        threshold table, staged from the kernel argument once per workgroup (brake_classes_lds_bytes).  Per pose the
 //                        lane keeps the minimum key of the footprint and tests it against the classes still open; the walk ends
 //                        when every class has its first hit, or at the standing pose, where ONE scan settles every open class by
@@ -15,9 +15,7 @@
 //                        minima over the G lanes.  NC = brake_classes_width(C) >= C is the compile-time class count: the
 //                        per-class state (first hit, first, commit) is indexed by unrolled loops alone and stays in registers;
 //                        classes c >= C are never open, read no threshold and are not stored.
-// The key map is read through the caches.  Every LDS index is clamped to [0, Lm) or bounded by c < C before it is used and the scan
-// tests every cell against the window and the raster first: no content of v, arc, key, qmin or thr can make a lane read out of
-// range.  No atomics, no scratch, plain vector stores; every byte of every output is written.
+// The key map is read through the caches.  Class indices into the table are bounded by c < C.  Every byte of every output is written.
 #pragma once
 #include "fo_hidden_brake.hpp"
 #include "fo_hidden_clearance.hpp"
@@ -57,29 +55,12 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_classes_kernel(const H
   const bool live = m < a.M;
   int32_t *QM = (int32_t *)(hbc_rows + (size_t)per_block * 6 * T);   // [per_block][T]
   int32_t *TH = QM + (size_t)per_block * T;                          // [C][T]
-  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
-    const int su = t / T, k = t - su * T;
-    if (m0 + su < a.M) {
-      const size_t i = (size_t)(m0 + su) * T + k;
-      double *row = hbc_rows + (size_t)su * 6 * T + k;
-      row[0] = a.x[i];
-      row[T] = a.y[i];
-      row[2 * T] = a.heading[2 * i];
-      row[3 * T] = a.heading[2 * i + 1];
-      row[4 * T] = a.arc[i];
-      row[5 * T] = a.v[i];
-      QM[t] = a.qmin[i];
-    }
-  }
+  hb_stage_rows(a, hbc_rows, m0, per_block, [&](int t, size_t i) { QM[t] = a.qmin[i]; });
   for (int t = threadIdx.x; t < nc * T; t += HB_THREADS) TH[t] = thr.v[t];     // (C * T <= FO_HIDDEN_BRAKE_MAX_TABLE: the host's refusal)
   __syncthreads();
   const double *X = hbc_rows + (size_t)sub * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
   const int32_t *Q = QM + (size_t)sub * T;
-  int Lm = 0;
-  if (live) {
-    Lm = T;
-    if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < T ? l : T); }
-  }
+  const int Lm = live ? hb_length(a, m) : 0;
   // first[c] = min { k < Lm : qmin[m][k] <= thr[c][k] }: the lanes of the trajectory split its samples
   int fm[NC];
 #pragma unroll
@@ -92,15 +73,10 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_classes_kernel(const H
   }
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    for (int o = G >> 1; o > 0; o >>= 1) {          // lanes of a trajectory are G consecutive lanes of one wave
-      const int f = __shfl_xor(fm[c], o);
-      fm[c] = fm[c] < f ? fm[c] : f;
-    }
+    hb_shfl_min(fm[c], 1, G);               // lanes of a trajectory are G consecutive lanes of one wave
     if (fm[c] == 0x7fffffff) fm[c] = -1;
   }
-  // cells beyond the raster and the window have no key: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  const HrBox sb = fo_hr_scan_box(a);
   const unsigned every = (1u << nc) - 1u;           // bit c: class c has no first hit yet
   int commit[NC];
 #pragma unroll
@@ -112,16 +88,14 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_classes_kernel(const H
     if (b < Lm) {                       // (Lm = 0 on lanes without a trajectory)
       const int last = Lm - 1;
       const double vb = V[b], arc_end = ARC[last];
-      st = Lm;
-      for (int i = b; i < Lm; ++i)
-        if (hb_speed(vb, a.a_brake, a.dt, i, b) == 0.0) { st = i; break; }
+      st = hb_stop_sample(vb, a.a_brake, a.dt, b, Lm);
       double s = ARC[b];
       int j = 0;
       unsigned open = every;
       for (int i = b + 1; i < Lm; ++i) {
         const HbPose p = hb_pose_step(X, Y, C, S, ARC, Lm, last, arc_end, vb, a.a_brake, a.dt, i, b, s, j);
         int q = HC_NONE;
-        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, K, HC_NONE, lox, loy, hix, hiy, 0, 1,
+        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, K, HC_NONE, sb.lox, sb.loy, sb.hix, sb.hiy, 0, 1,
                              [&](int kv, int, int) { q = q < kv ? q : kv; });
         if (i >= st) {                  // the ego stands: this pose is the manoeuvre's last one, hit_c(i') for i' >= i iff q <= thr[c][i']
 #pragma unroll
@@ -140,7 +114,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_classes_kernel(const H
       }
 #pragma unroll
       for (int c = 0; c < NC; ++c)
-        if ((fm[c] >= 0 && fm[c] <= b) || (bf[c] >= 0 && bf[c] < st)) commit[c] = commit[c] < b ? commit[c] : b;
+        if (hb_unclear(fm[c], b, bf[c], st)) commit[c] = commit[c] < b ? commit[c] : b;
     }
     if (live) {
 #pragma unroll
@@ -151,10 +125,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_classes_kernel(const H
   }
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
-    for (int o = G >> 1; o > 0; o >>= 1) {
-      const int f = __shfl_xor(commit[c], o);
-      commit[c] = commit[c] < f ? commit[c] : f;
-    }
+    hb_shfl_min(commit[c], 1, G);
     if (live && kl == 0 && c < nc) {
       a.commit[(size_t)c * a.M + (size_t)m] = commit[c] == 0x7fffffff ? -1 : commit[c];
       a.first[(size_t)c * a.M + (size_t)m] = fm[c];

@@ -1,8 +1,8 @@
 // fo_hidden_brake_ladder.hpp -- hidden-traffic brake ladder (fo_scene_hidden_brake_ladder; DESIGN.md §5.10 "Brake ladder"): per
 // candidate and brake start the gentlest deceleration of a ladder of K levels that still keeps the moving ego out of road hidden
 // traffic may have reached -- the brake clearance at K decelerations from ONE launch.  An EXTENSION, not part of the reference.
-// Included by fo_scene.hip after fo_hidden_brake.hpp (same translation unit, same flags: -ffp-contract=off); it walks with hb_speed
-// and hb_pose_step and scans with fo_hr_scan_pose_rows, unchanged: the arithmetic of a manoeuvre exists once.
+// Included by fo_scene.hip after fo_hidden_brake.hpp (same translation unit, same flags: -ffp-contract=off); staging, length, stop
+// sample, pose step, commit rule and shuffle minimum are fo_hidden_brake.hpp's, where the bounds reasoning of all of them stands.
 //
 // Inputs are those of fo_hr_brake_kernel with the K levels in place of a_brake (they travel as a kernel argument: 512 bytes, no
 // transfer, no device buffer) and B, the number of brake starts.  The definition stands in include/fo_hip.h.
@@ -11,14 +11,12 @@
 //                        decelerations (their LDS reads of the trajectory's rows are mostly broadcasts, their footprints lie
 //                        next to each other).  G = brake_ladder_group(T, K, B) lanes per trajectory (a power of two in
 //                        [Kp, 256]), 256 / G trajectories per workgroup, whose rows x, y, cos, sin, arc, v are staged in LDS once
-//                        as in fo_hr_brake_kernel; a lane takes the brake starts b = l / Kp, l / Kp + G / Kp, ...  Every lane of
+//                        by hb_stage_rows; a lane takes the brake starts b = l / Kp, l / Kp + G / Kp, ...  Every lane of
 //                        the workgroup runs the same number of rounds, so the shuffles stand outside divergent code.
 //                        required and last_unclear are a __shfl_xor minimum and maximum over the Kp lanes of a round; commit[k]
 //                        is a minimum over the lanes with the same k: by __shfl_xor within a wave and, where a trajectory has
 //                        more than a wave (G = 128, 256), through 1 KB of LDS behind the rows.
-// The arrival map is read through the caches.  Every LDS index is clamped to [0, Lm) before it is used (hb_pose_step), the level
-// index is < K, and the scan tests every cell against the window and the raster first: no content of v, arc, A, first or the
-// levels can make a lane read out of range.  No atomics, no scratch, plain vector stores; every byte of every output is written.
+// The arrival map is read through the caches.  The level index is < K.  Every byte of every output is written.
 #pragma once
 #include "fo_hidden_brake.hpp"
 
@@ -57,31 +55,16 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_kernel(const Hr
   const int k = l & (Kp - 1), bq = l / Kp, nb = G / Kp;
   const long long m0 = (long long)blockIdx.x * per_block, m = m0 + sub;
   const bool live = m < a.M, level = k < K;
-  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
-    const int su = t / T, ks = t - su * T;
-    if (m0 + su < a.M) {
-      const size_t i = (size_t)(m0 + su) * T + ks;
-      double *row = hbl_rows + (size_t)su * 6 * T + ks;
-      row[0] = a.x[i];
-      row[T] = a.y[i];
-      row[2 * T] = a.heading[2 * i];
-      row[3 * T] = a.heading[2 * i + 1];
-      row[4 * T] = a.arc[i];
-      row[5 * T] = a.v[i];
-    }
-  }
+  hb_stage_rows(a, hbl_rows, m0, per_block, [](int, size_t) {});
   __syncthreads();
   const double *X = hbl_rows + (size_t)sub * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
   int Lm = 0, fm = -1;
   if (live) {
-    Lm = T;
-    if (a.len) { const int ln = a.len[m]; Lm = ln < 0 ? 0 : (ln < T ? ln : T); }
+    Lm = hb_length(a, m);
     fm = a.first[m];
   }
   const double a_brake = level ? lv.v[k] : 0.0;
-  // cells beyond the raster and the window have no arrival step: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  const HrBox sb = fo_hr_scan_box(a);
   int commit = 0x7fffffff;
   for (int b0 = 0; b0 < B; b0 += nb) {  // the same rounds on every lane of the workgroup
     const int b = b0 + bq;
@@ -90,9 +73,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_kernel(const Hr
     if (mine && b < Lm) {               // (Lm = 0 on lanes without a trajectory)
       const int last = Lm - 1;
       const double vb = V[b], arc_end = ARC[last];
-      st = Lm;
-      for (int i = b; i < Lm; ++i)
-        if (hb_speed(vb, a_brake, a.dt, i, b) == 0.0) { st = i; break; }
+      st = hb_stop_sample(vb, a_brake, a.dt, b, Lm);
       double s = ARC[b];
       int j = 0;
       for (int i = b + 1; i < Lm; ++i) {
@@ -100,7 +81,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_kernel(const Hr
         // the ego stands from sample st on (vn = 0 adds nothing to s): this pose is the manoeuvre's last one
         const bool stands = i >= st;
         int amin = 255;
-        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, A, 255, lox, loy, hix, hiy, 0, 1,
+        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, A, 255, sb.lox, sb.loy, sb.hix, sb.hiy, 0, 1,
                              [&](int av, int, int) { amin = amin < av ? amin : av; });
         if (stands) {                   // hit(i') for i' >= i iff amin <= i'
           const int at = amin > i ? amin : i;
@@ -109,7 +90,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_kernel(const Hr
         }
         if (amin <= i) { bf = i; break; }
       }
-      if ((fm >= 0 && fm <= b) || (bf >= 0 && bf < st)) {
+      if (hb_unclear(fm, b, bf, st)) {
         commit = commit < b ? commit : b;
         unclear_k = k;
       } else {
@@ -133,10 +114,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_kernel(const Hr
   }
   // commit[m][k]: the minimum over the lanes of the trajectory with this k -- within the wave ...
   const int in_wave = G < 64 ? G : 64;
-  for (int o = in_wave >> 1; o >= Kp; o >>= 1) {
-    const int c = __shfl_xor(commit, o);
-    commit = commit < c ? commit : c;
-  }
+  hb_shfl_min(commit, Kp, in_wave);
   if (G > 64) {                         // ... and over the G / 64 waves of the trajectory (G is the workgroup's: no lane diverges)
     int32_t *CM = (int32_t *)(hbl_rows + (size_t)per_block * 6 * T);       // [HB_THREADS / 64][64]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;

@@ -2,8 +2,10 @@
 // (fo_scene_hidden_brake_ladder_users; DESIGN.md §5.10 "Brake ladder by road users"): per candidate and brake start the gentlest
 // deceleration of a ladder of L levels that keeps the moving ego clear of EVERY class of hidden road user, each class held against
 // the key map it names.  An EXTENSION, not part of the reference.  Included by fo_scene.hip after fo_hidden_brake_users.hpp and
-// fo_hidden_brake_ladder.hpp (same translation unit, same flags: -ffp-contract=off); it walks with hb_speed and hb_pose_step, scans
-// with fo_hr_scan_pose_rows and decides with HbuKeys / hbu_hits, all unchanged: the arithmetic of a manoeuvre exists once.
+// fo_hidden_brake_ladder.hpp (same translation unit, same flags: -ffp-contract=off); it stages with hbu_stage, forms first[c] with
+// hbu_first and walks with hbu_walk (fo_hidden_brake_users.hpp, where the bounds reasoning stands).  The home of what the two ladder
+// users kernels (this one and fo_hidden_brake_ladder_verdict.hpp) share: the ballot of a round (hblu_ballot) and what a group of
+// levels requires (hblu_required).
 //
 // Inputs are those of fo_hr_brake_users_kernel with the L levels in place of a_brake, and B, the number of brake starts.  The levels
 // and the threshold table travel together as ONE kernel argument of FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES (HbluPack: the levels'
@@ -11,10 +13,9 @@
 //   fo_hr_brake_ladder_users_kernel<NC, NK>  the lanes of fo_hr_brake_ladder_kernel: a lane per (m, b, l), lanes along (b, l) with l
 //                        fastest, padded to Lp = the power of two >= L; G = brake_ladder_users_group lanes per trajectory (a power
 //                        of two in [Lp, 256]), 256 / G trajectories per workgroup, the same rounds on every lane of the workgroup.
-//                        Per lane the state of fo_hr_brake_users_kernel: one scan per braking pose over map 0 whose callback reads the
-//                        other maps that still have an open class, the walk ends when every class has its hit or at the standing
-//                        pose.  LDS: the six rows and the K qmin rows of each trajectory, the table, and behind them the commit
-//                        exchange, one int32 per class and lane of the workgroup (used where a trajectory has more than a wave).
+//                        Per lane the walk of fo_hr_brake_users_kernel.  LDS: the six rows and the K qmin rows of each trajectory,
+//                        the table, and behind them the commit exchange, one int32 per class and lane of the workgroup (used
+//                        where a trajectory has more than a wave).
 //                        first[c] is formed by every wave for itself (its lanes split the samples), so that no wave waits for it.
 //                        After a round every lane holds its unclear mask (bit c: class c is unclear at this lane's level).  The Lp
 //                        lanes of one (m, b) are consecutive lanes of one wave, so ONE wave ballot per class holds the unclear bits of
@@ -24,10 +25,7 @@
 //                        (A __shfl_xor minimum / maximum per class costs 2 log2(Lp) shuffles per class and round; a ballot costs one
 //                        compare.)  commit[c][l] is a minimum over the lanes with the same l: __shfl_xor within the wave and, where
 //                        G = 128, 256, through the exchange.
-// The key maps are read through the caches and never written, so two of them may be the same buffer.  Every LDS index is clamped to
-// [0, Lm) or bounded by c < C, the level index is < L, and a map is read only at a window index that was tested against the window:
-// no content of v, arc, the keys, qmin, thr, map_of or the levels can make a lane read out of range.  No atomics, no scratch, plain
-// vector stores; every byte of every output handed over is written.
+// The level index is < L.  Every byte of every output handed over is written.
 #pragma once
 #include "fo_hidden_brake_users.hpp"
 #include "fo_hidden_brake_ladder.hpp"
@@ -66,6 +64,42 @@ static_assert(4 * FO_HIDDEN_BRAKE_MAX_TABLE <= FO_HIDDEN_BRAKE_LADDER_USERS_MAX_
 static_assert(BRAKE_LADDER_USERS_MAX_ARG_BYTES == FO_HIDDEN_BRAKE_LADDER_USERS_MAX_ARG_BYTES && BRAKE_LADDER_USERS_MAX_CLASSES == FO_HIDDEN_BRAKE_MAX_CLASSES,
               "brake_ladder_users_lds_bound speaks of the header's limits");
 
+// This lane's group of Lp lanes within the ballots of its wave, and the levels that exist
+struct HbluGroup { int shift; unsigned long long seg_mask, lv_mask; };
+__device__ __forceinline__ HbluGroup hblu_group(int lane, int Lp, int L) {
+  return HbluGroup{lane & ~(Lp - 1), Lp == 64 ? ~0ull : (1ull << Lp) - 1ull, L == 64 ? ~0ull : (1ull << L) - 1ull};
+}
+
+// The ballot of a round, reached by every lane of the wave: um has bit c set where class c is unclear at this lane's (m, b, level).
+// ONE wave ballot per class holds the unclear bits of every level of every (m, b) of the wave; segs[c] becomes the Lp bits of this
+// lane's group (bit l: class c is unclear at level l), the return value their OR over the classes.
+template <int NC>
+__device__ __forceinline__ unsigned long long hblu_ballot(unsigned um, const HbluGroup &g, unsigned long long (&segs)[NC]) {
+  unsigned long long any = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c) {
+    segs[c] = (__builtin_amdgcn_ballot_w64((um >> c & 1u) != 0) >> g.shift) & g.seg_mask;
+    any |= segs[c];
+  }
+  return any;
+}
+
+// What the group's levels require against all classes: req, the lowest clear level below L (-1: none, or no manoeuvre), and
+// at_level, bit c: class c is unclear at the level below the required one (the last one where req < 0; req = 0: nothing blocks)
+struct HbluReq { int req; unsigned at_level; };
+template <int NC>
+__device__ __forceinline__ HbluReq hblu_required(const unsigned long long (&segs)[NC], unsigned long long any, const HbluGroup &g, int L,
+                                                 bool man) {
+  const unsigned long long clear = ~any & g.lv_mask;
+  const int req = man ? __builtin_ffsll((long long)clear) - 1 : -1;
+  const int lvl = req < 0 ? L - 1 : req - 1;
+  unsigned at_level = 0;
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+    if (lvl >= 0 && (segs[c] >> lvl & 1ull)) at_level |= 1u << c;
+  return HbluReq{req, at_level};
+}
+
 // dynamic LDS: brake_ladder_users_lds_bytes(T, K, C, L, B)
 template <int NC, int NK>
 __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(const HrBrakeLadderUsersArgs a, const HbluPack pk) {
@@ -79,68 +113,17 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(co
   int32_t *QM = (int32_t *)(hblu_rows + (size_t)per_block * 6 * T);  // [NK][per_block][T]
   int32_t *TH = QM + (size_t)NK * per_block * T;                     // [C][T]
   int32_t *CM = TH + (size_t)nc * T;                                 // [C][HB_THREADS]
-  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
-    const int su = t / T, ks = t - su * T;
-    if (m0 + su < a.M) {
-      const size_t i = (size_t)(m0 + su) * T + ks;
-      double *row = hblu_rows + (size_t)su * 6 * T + ks;
-      row[0] = a.x[i];
-      row[T] = a.y[i];
-      row[2 * T] = a.heading[2 * i];
-      row[3 * T] = a.heading[2 * i + 1];
-      row[4 * T] = a.arc[i];
-      row[5 * T] = a.v[i];
-      QM[t] = a.qmin0[i];
-      if constexpr (NK > 1) QM[(size_t)per_block * T + t] = a.qmin1[i];
-      if constexpr (NK > 2) QM[(size_t)2 * per_block * T + t] = a.qmin2[i];
-    }
-  }
-  for (int t = threadIdx.x; t < nc * T; t += HB_THREADS) TH[t] = pk.w[2 * L + t];   // (4 C T + 8 L <= the argument's bytes: the host's refusal)
+  hbu_stage<NK>(a, hblu_rows, QM, TH, m0, per_block, [&](int t) { return pk.w[2 * L + t]; });
   __syncthreads();
-  const double *X = hblu_rows + (size_t)sub * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
-  const int32_t *Q = QM + (size_t)sub * T;          // map k2: Q[k2 * per_block * T + j]
-  int Lm = 0;
-  if (live) {
-    Lm = T;
-    if (a.len) { const int ln = a.len[m]; Lm = ln < 0 ? 0 : (ln < T ? ln : T); }
-  }
+  const double *X = hblu_rows + (size_t)sub * 6 * T, *V = X + 5 * T;
+  const int Lm = live ? hb_length(a, m) : 0;
   const double a_brake = level ? __hiloint2double(pk.w[2 * k + 1], pk.w[2 * k]) : 0.0;
-  const unsigned every = (1u << nc) - 1u;           // bit c: class c is there (c < C); in the walk: it has no first hit yet
-  unsigned cm1 = 0, cm2 = 0;                        // bit c: class c is held against map 1 / map 2
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int mo = hbu_map_of(a.map_of, c);
-    if (c < nc && mo == 1) cm1 |= 1u << c;
-    if (c < nc && mo == 2) cm2 |= 1u << c;
-  }
-  // first[c] = min { j < Lm : qmin_map_of[c][m][j] <= thr[c][j] }: the lanes a trajectory has in THIS wave split its samples
+  const HbuMasks mk = hbu_masks<NC>(a.map_of, nc);
   const int in_wave = G < 64 ? G : 64;
-  int fm[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) fm[c] = 0x7fffffff;
-  for (int j = l & (in_wave - 1); j < Lm; j += in_wave) {
-    HbuKeys q{Q[j], 0, 0};
-    if constexpr (NK > 1) q.q1 = Q[(size_t)per_block * T + j];
-    if constexpr (NK > 2) q.q2 = Q[(size_t)2 * per_block * T + j];
-    const unsigned h = hbu_hits<NC, NK>(q, TH, T, j, every, cm1, cm2);
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (h >> c & 1u) fm[c] = fm[c] < j ? fm[c] : j;
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    for (int o = in_wave >> 1; o > 0; o >>= 1) {
-      const int f = __shfl_xor(fm[c], o);
-      fm[c] = fm[c] < f ? fm[c] : f;
-    }
-    if (fm[c] == 0x7fffffff) fm[c] = -1;
-  }
-  // cells beyond the raster and the window have no key: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
-  // this lane's group of Lp lanes within the ballot of its wave, and the levels that exist
-  const int seg_shift = lane & ~(Lp - 1);
-  const unsigned long long seg_mask = Lp == 64 ? ~0ull : (1ull << Lp) - 1ull, lv_mask = L == 64 ? ~0ull : (1ull << L) - 1ull;
+  int fm[NC];                           // formed by every wave for itself: the lanes a trajectory has in THIS wave split its samples
+  hbu_first<NC, NK>(QM + (size_t)sub * T, (size_t)per_block * T, TH, T, Lm, l & (in_wave - 1), in_wave, mk, fm);
+  const HrBox sb = fo_hr_scan_box(a);
+  const HbluGroup grp = hblu_group(lane, Lp, L);
   int commit[NC];
 #pragma unroll
   for (int c = 0; c < NC; ++c) commit[c] = 0x7fffffff;
@@ -152,68 +135,18 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(co
 #pragma unroll
     for (int c = 0; c < NC; ++c) bf[c] = -1;
     if (walk) {
-      const int last = Lm - 1;
-      const double vb = V[b], arc_end = ARC[last];
-      st = Lm;
-      for (int i = b; i < Lm; ++i)
-        if (hb_speed(vb, a_brake, a.dt, i, b) == 0.0) { st = i; break; }
-      double s = ARC[b];
-      int j = 0;
-      unsigned open = every;
-      for (int i = b + 1; i < Lm; ++i) {
-        const HbPose p = hb_pose_step(X, Y, C, S, ARC, Lm, last, arc_end, vb, a_brake, a.dt, i, b, s, j);
-        const bool open1 = (open & cm1) != 0, open2 = (open & cm2) != 0;   // maps 1, 2 still have an open class (map 0 is the scan's own)
-        HbuKeys q{HC_NONE, HC_NONE, HC_NONE};
-        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, a.key0, HC_NONE, lox, loy, hix, hiy, 0, 1, [&](int kv, int gx, int gy) {
-          q.q0 = q.q0 < kv ? q.q0 : kv;
-          if constexpr (NK > 1) {
-            const int wx = gx - a.ix0, wy = gy - a.iy0;
-            const bool in = wx >= 0 && wx < a.nx && wy >= 0 && wy < a.ny;
-            if (open1) {
-              const int vk = in ? a.key1[wy * a.nx + wx] : kv;      // outside the window: 0 or NONE, the same for every map
-              q.q1 = q.q1 < vk ? q.q1 : vk;
-            }
-            if constexpr (NK > 2) {
-              if (open2) {
-                const int vk = in ? a.key2[wy * a.nx + wx] : kv;
-                q.q2 = q.q2 < vk ? q.q2 : vk;
-              }
-            }
-          }
-        });
-        if (i >= st) {                  // the ego stands: this pose is the manoeuvre's last one, hit_c(i') for i' >= i iff q <= thr[c][i']
-          for (int at = i; at <= last && open; ++at) {
-            const unsigned h = hbu_hits<NC, NK>(q, TH, T, at, open, cm1, cm2);
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-              if (h >> c & 1u) bf[c] = at;
-            open &= ~h;
-          }
-          break;
-        }
-        const unsigned h = hbu_hits<NC, NK>(q, TH, T, i, open, cm1, cm2);
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-          if (h >> c & 1u) bf[c] = i;
-        open &= ~h;
-        if (!open) break;
-      }
+      const double vb = V[b];
+      st = hb_stop_sample(vb, a_brake, a.dt, b, Lm);
+      hbu_walk<NC, NK>(a, X, TH, Lm, b, vb, a_brake, st, mk, sb, bf);
 #pragma unroll
       for (int c = 0; c < NC; ++c)
-        if (c < nc && ((fm[c] >= 0 && fm[c] <= b) || (bf[c] >= 0 && bf[c] < st))) {
+        if (c < nc && hb_unclear(fm[c], b, bf[c], st)) {
           commit[c] = commit[c] < b ? commit[c] : b;
           um |= 1u << c;
         }
     }
-    // every lane of the wave is here: one ballot per class holds the unclear bits of all its (m, b) groups
-    unsigned long long any = 0;
-    unsigned at_level = 0;              // bit c: class c is unclear at the level asked of it below (required_all - 1)
     unsigned long long segs[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      segs[c] = (__builtin_amdgcn_ballot_w64((um >> c & 1u) != 0) >> seg_shift) & seg_mask;
-      any |= segs[c];
-    }
+    const unsigned long long any = hblu_ballot<NC>(um, grp, segs);
     const bool row = live && b < B;     // (the Lp lanes of (m, b) agree on it)
     const bool man = b < Lm;            // ... and on whether there is a manoeuvre
     if (row) {
@@ -221,21 +154,16 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(co
 #pragma unroll
       for (int c = 0; c < NC; ++c)
         if (c < nc && k == (c & (Lp - 1))) {        // the classes' rows are dealt to the lanes of the group
-          const unsigned long long clear = ~segs[c] & lv_mask;
+          const unsigned long long clear = ~segs[c] & grp.lv_mask;
           const size_t o = ((size_t)c * a.M + (size_t)m) * B + b;
           a.required[o] = man ? __builtin_ffsll((long long)clear) - 1 : -1;
           a.last_unclear[o] = segs[c] ? 63 - __builtin_clzll(segs[c]) : -1;
         }
-      const unsigned long long clear = ~any & lv_mask;
-      const int req = man ? __builtin_ffsll((long long)clear) - 1 : -1;
-      const int lvl = req < 0 ? L - 1 : req - 1;    // (req = 0: -1, nothing blocks)
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        if (lvl >= 0 && (segs[c] >> lvl & 1ull)) at_level |= 1u << c;
+      const HbluReq rq = hblu_required<NC>(segs, any, grp, L, man);
       if (k == 0) {
-        a.required_all[mb] = req;
+        a.required_all[mb] = rq.req;
         a.last_unclear_all[mb] = any ? 63 - __builtin_clzll(any) : -1;
-        a.blocking[mb] = (int32_t)at_level;
+        a.blocking[mb] = (int32_t)rq.at_level;
       }
       if (a.stop && level) {            // the detail (uniform: both buffers or neither)
         const size_t o = mb * L + k;
@@ -248,11 +176,7 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(co
   }
   // commit[c][m][l]: the minimum over the lanes of the trajectory with this l -- within the wave ...
 #pragma unroll
-  for (int c = 0; c < NC; ++c)
-    for (int o = in_wave >> 1; o >= Lp; o >>= 1) {
-      const int f = __shfl_xor(commit[c], o);
-      commit[c] = commit[c] < f ? commit[c] : f;
-    }
+  for (int c = 0; c < NC; ++c) hb_shfl_min(commit[c], Lp, in_wave);
   if (G > 64) {                         // ... and over the G / 64 waves of the trajectory (G is the workgroup's: no lane diverges)
     const int wave = threadIdx.x >> 6;
 #pragma unroll
@@ -278,14 +202,10 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_users_kernel(co
   }
 }
 
-// the instantiation of K maps at the class width NC
 template <int NC>
 void hblu_launch(int K, dim3 grid, dim3 block, size_t lds, hipStream_t s, const HrBrakeLadderUsersArgs &a, const HbluPack &pk) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((fo_hr_brake_ladder_users_kernel<NC, 1>), grid, block, lds, s, a, pk); break;
-    case 2: hipLaunchKernelGGL((fo_hr_brake_ladder_users_kernel<NC, 2>), grid, block, lds, s, a, pk); break;
-    default: hipLaunchKernelGGL((fo_hr_brake_ladder_users_kernel<NC, 3>), grid, block, lds, s, a, pk); break;
-  }
+  hbu_launch_maps(K, fo_hr_brake_ladder_users_kernel<NC, 1>, fo_hr_brake_ladder_users_kernel<NC, 2>, fo_hr_brake_ladder_users_kernel<NC, 3>,
+                  grid, block, lds, s, a, pk);
 }
 
 }  // namespace

@@ -2,9 +2,10 @@
 // "Ladder verdict"): the deceleration each candidate needs, from the worst of the brake starts up to the replanning interval, to stay
 // clear of every class of hidden road user -- folded into the two reserved columns of the planning step's cost row and its safety
 // flag.  An EXTENSION, not part of the reference.  Included by fo_scene.hip after fo_hidden_brake_ladder_users.hpp and
-// fo_hidden_brake_verdict.hpp (same translation unit, same flags: -ffp-contract=off); it walks with hb_speed and hb_pose_step, scans
-// with fo_hr_scan_pose_rows, decides with HbuKeys / hbu_hits and takes the levels and the table as the HbluPack argument, all
-// unchanged: the arithmetic of a manoeuvre exists once.  What the groups' answers mean per trajectory is fo_hidden_ladder_verdict.hpp's.
+// fo_hidden_brake_verdict.hpp (same translation unit, same flags: -ffp-contract=off); it stages with hbu_stage, forms first[c] with
+// hbu_first and walks with hbu_walk (fo_hidden_brake_users.hpp, where the bounds reasoning stands), forms a round's answers with
+// hblu_ballot and hblu_required (fo_hidden_brake_ladder_users.hpp) and takes the levels and the table as the HbluPack argument.
+// What the groups' answers mean per trajectory is fo_hidden_ladder_verdict.hpp's.
 //
 // Inputs are those of fo_hr_brake_ladder_users_kernel, a_limit, finite [M] and the cost / safe pair.  The definition stands in
 // include/fo_hip.h.
@@ -20,11 +21,8 @@
 //                        Across the rounds a lane keeps the maximum of its groups' keys and per-class ranks; at the end the
 //                        maximum over the lanes of the trajectory: __shfl_xor within the wave and, where G = 128, 256, one int32
 //                        per wave through the exchange.  Lane 0 of each trajectory writes the outputs and folds the row.
-// No [M][B] or [M][B][L] buffer exists.  The key maps are read through the caches and never written, so two of them may be the same
-// buffer.  Every LDS index is clamped to [0, Lm) or bounded by c < C, the level index is < L, and a map is read only at a window index
-// that was tested against the window: no content of v, arc, the keys, qmin, thr, map_of, the levels or finite can make a lane read out
-// of range.  No atomics, no scratch, plain vector stores; every byte of every output is written; of cost and safe only what the
-// definition names.
+// No [M][B] or [M][B][L] buffer exists.  The level index is < L, finite is read at m < M alone.  Every byte of every output is
+// written; of cost and safe only what the definition names.
 #pragma once
 #include "fo_hidden_brake_ladder_users.hpp"
 #include "fo_hidden_ladder_verdict.hpp"
@@ -69,69 +67,18 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_verdict_kernel(
   int32_t *QM = (int32_t *)(hblv_rows + (size_t)per_block * 6 * T);  // [NK][per_block][T]
   int32_t *TH = QM + (size_t)NK * per_block * T;                     // [C][T]
   int32_t *EX = TH + (size_t)nc * T;                                 // [C + 1][BRAKE_LADDER_VERDICT_WAVES]
-  for (int t = threadIdx.x; t < per_block * T; t += HB_THREADS) {
-    const int su = t / T, ks = t - su * T;
-    if (m0 + su < a.M) {
-      const size_t i = (size_t)(m0 + su) * T + ks;
-      double *row = hblv_rows + (size_t)su * 6 * T + ks;
-      row[0] = a.x[i];
-      row[T] = a.y[i];
-      row[2 * T] = a.heading[2 * i];
-      row[3 * T] = a.heading[2 * i + 1];
-      row[4 * T] = a.arc[i];
-      row[5 * T] = a.v[i];
-      QM[t] = a.qmin0[i];
-      if constexpr (NK > 1) QM[(size_t)per_block * T + t] = a.qmin1[i];
-      if constexpr (NK > 2) QM[(size_t)2 * per_block * T + t] = a.qmin2[i];
-    }
-  }
-  for (int t = threadIdx.x; t < nc * T; t += HB_THREADS) TH[t] = pk.w[2 * L + t];   // (4 C T + 8 L <= the argument's bytes: the host's refusal)
+  hbu_stage<NK>(a, hblv_rows, QM, TH, m0, per_block, [&](int t) { return pk.w[2 * L + t]; });
   __syncthreads();
   const int row_of = live ? sub : 0;    // (lanes without a trajectory read nothing: Lm = 0; their pointers stay inside the rows)
-  const double *X = hblv_rows + (size_t)row_of * 6 * T, *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T, *V = ARC + T;
-  const int32_t *Q = QM + (size_t)row_of * T;       // map k2: Q[k2 * per_block * T + j]
-  int Lm = 0;
-  if (live) {
-    Lm = T;
-    if (a.len) { const int ln = a.len[m]; Lm = ln < 0 ? 0 : (ln < T ? ln : T); }
-  }
+  const double *X = hblv_rows + (size_t)row_of * 6 * T, *V = X + 5 * T;
+  const int Lm = live ? hb_length(a, m) : 0;
   const double a_brake = level ? __hiloint2double(pk.w[2 * k + 1], pk.w[2 * k]) : 0.0;
-  const unsigned every = (1u << nc) - 1u;           // bit c: class c is there (c < C); in the walk: it has no first hit yet
-  unsigned cm1 = 0, cm2 = 0;                        // bit c: class c is held against map 1 / map 2
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    const int mo = hbu_map_of(a.map_of, c);
-    if (c < nc && mo == 1) cm1 |= 1u << c;
-    if (c < nc && mo == 2) cm2 |= 1u << c;
-  }
-  // first[c] = min { j < Lm : qmin_map_of[c][m][j] <= thr[c][j] }: the lanes a trajectory has in THIS wave split its samples
+  const HbuMasks mk = hbu_masks<NC>(a.map_of, nc);
   const int in_wave = G < 64 ? G : 64;
-  int fm[NC];
-#pragma unroll
-  for (int c = 0; c < NC; ++c) fm[c] = 0x7fffffff;
-  for (int j = l & (in_wave - 1); j < Lm; j += in_wave) {
-    HbuKeys q{Q[j], 0, 0};
-    if constexpr (NK > 1) q.q1 = Q[(size_t)per_block * T + j];
-    if constexpr (NK > 2) q.q2 = Q[(size_t)2 * per_block * T + j];
-    const unsigned h = hbu_hits<NC, NK>(q, TH, T, j, every, cm1, cm2);
-#pragma unroll
-    for (int c = 0; c < NC; ++c)
-      if (h >> c & 1u) fm[c] = fm[c] < j ? fm[c] : j;
-  }
-#pragma unroll
-  for (int c = 0; c < NC; ++c) {
-    for (int o = in_wave >> 1; o > 0; o >>= 1) {
-      const int f = __shfl_xor(fm[c], o);
-      fm[c] = fm[c] < f ? fm[c] : f;
-    }
-    if (fm[c] == 0x7fffffff) fm[c] = -1;
-  }
-  // cells beyond the raster and the window have no key: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
-  // this lane's group of Lp lanes within the ballot of its wave, and the levels that exist
-  const int seg_shift = lane & ~(Lp - 1);
-  const unsigned long long seg_mask = Lp == 64 ? ~0ull : (1ull << Lp) - 1ull, lv_mask = L == 64 ? ~0ull : (1ull << L) - 1ull;
+  int fm[NC];                           // formed by every wave for itself, as in the ladder-users kernel
+  hbu_first<NC, NK>(QM + (size_t)row_of * T, (size_t)per_block * T, TH, T, Lm, l & (in_wave - 1), in_wave, mk, fm);
+  const HrBox sb = fo_hr_scan_box(a);
+  const HbluGroup grp = hblu_group(lane, Lp, L);
   const int ends = B < Lm ? B : Lm;     // brake starts with a manoeuvre (Lm = 0 on lanes without a trajectory)
   int32_t key = FO_HIDDEN_LADDER_NO_KEY, need_of[NC];
 #pragma unroll
@@ -142,80 +89,24 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_verdict_kernel(
     unsigned um = 0;                    // bit c: class c is unclear at (m, b, this level)
     if (walk) {
       int bf[NC];
-#pragma unroll
-      for (int c = 0; c < NC; ++c) bf[c] = -1;
-      const int last = Lm - 1;
-      const double vb = V[b], arc_end = ARC[last];
-      int st = Lm;
-      for (int i = b; i < Lm; ++i)
-        if (hb_speed(vb, a_brake, a.dt, i, b) == 0.0) { st = i; break; }
-      double s = ARC[b];
-      int j = 0;
-      unsigned open = every;
-      for (int i = b + 1; i < Lm; ++i) {
-        const HbPose p = hb_pose_step(X, Y, C, S, ARC, Lm, last, arc_end, vb, a_brake, a.dt, i, b, s, j);
-        const bool open1 = (open & cm1) != 0, open2 = (open & cm2) != 0;   // maps 1, 2 still have an open class (map 0 is the scan's own)
-        HbuKeys q{HC_NONE, HC_NONE, HC_NONE};
-        fo_hr_scan_pose_rows(a, p.x, p.y, p.c, p.s, a.key0, HC_NONE, lox, loy, hix, hiy, 0, 1, [&](int kv, int gx, int gy) {
-          q.q0 = q.q0 < kv ? q.q0 : kv;
-          if constexpr (NK > 1) {
-            const int wx = gx - a.ix0, wy = gy - a.iy0;
-            const bool in = wx >= 0 && wx < a.nx && wy >= 0 && wy < a.ny;
-            if (open1) {
-              const int vk = in ? a.key1[wy * a.nx + wx] : kv;      // outside the window: 0 or NONE, the same for every map
-              q.q1 = q.q1 < vk ? q.q1 : vk;
-            }
-            if constexpr (NK > 2) {
-              if (open2) {
-                const int vk = in ? a.key2[wy * a.nx + wx] : kv;
-                q.q2 = q.q2 < vk ? q.q2 : vk;
-              }
-            }
-          }
-        });
-        if (i >= st) {                  // the ego stands: this pose is the manoeuvre's last one, hit_c(i') for i' >= i iff q <= thr[c][i']
-          for (int at = i; at <= last && open; ++at) {
-            const unsigned h = hbu_hits<NC, NK>(q, TH, T, at, open, cm1, cm2);
-#pragma unroll
-            for (int c = 0; c < NC; ++c)
-              if (h >> c & 1u) bf[c] = at;
-            open &= ~h;
-          }
-          break;
-        }
-        const unsigned h = hbu_hits<NC, NK>(q, TH, T, i, open, cm1, cm2);
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-          if (h >> c & 1u) bf[c] = i;
-        open &= ~h;
-        if (!open) break;
-      }
+      const double vb = V[b];
+      const int st = hb_stop_sample(vb, a_brake, a.dt, b, Lm);
+      hbu_walk<NC, NK>(a, X, TH, Lm, b, vb, a_brake, st, mk, sb, bf);
 #pragma unroll
       for (int c = 0; c < NC; ++c)
-        if (c < nc && ((fm[c] >= 0 && fm[c] <= b) || (bf[c] >= 0 && bf[c] < st))) um |= 1u << c;
+        if (c < nc && hb_unclear(fm[c], b, bf[c], st)) um |= 1u << c;
     }
-    // every lane of the wave is here: one ballot per class holds the unclear bits of all its (m, b) groups
-    unsigned long long any = 0, segs[NC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-      segs[c] = (__builtin_amdgcn_ballot_w64((um >> c & 1u) != 0) >> seg_shift) & seg_mask;
-      any |= segs[c];
-    }
+    unsigned long long segs[NC];
+    const unsigned long long any = hblu_ballot<NC>(um, grp, segs);
     if (b < ends) {                     // (the Lp lanes of (m, b) agree on it, and on everything below)
 #pragma unroll
       for (int c = 0; c < NC; ++c)
         if (c < nc) {
-          const unsigned long long clear = ~segs[c] & lv_mask;
+          const unsigned long long clear = ~segs[c] & grp.lv_mask;
           need_of[c] = fo_hidden_ladder_max(need_of[c], fo_hidden_ladder_rank(__builtin_ffsll((long long)clear) - 1, L));
         }
-      const unsigned long long clear = ~any & lv_mask;
-      const int req = __builtin_ffsll((long long)clear) - 1;
-      const int lvl = req < 0 ? L - 1 : req - 1;    // (req = 0: -1, nothing blocks)
-      unsigned at_level = 0;            // bit c: class c is unclear at the level below the required one
-#pragma unroll
-      for (int c = 0; c < NC; ++c)
-        if (lvl >= 0 && (segs[c] >> lvl & 1ull)) at_level |= 1u << c;
-      key = fo_hidden_ladder_max(key, fo_hidden_ladder_key(fo_hidden_ladder_rank(req, L), b, (int32_t)at_level));
+      const HbluReq rq = hblu_required<NC>(segs, any, grp, L, true);
+      key = fo_hidden_ladder_max(key, fo_hidden_ladder_key(fo_hidden_ladder_rank(rq.req, L), b, (int32_t)rq.at_level));
     }
   }
   // the maximum over the lanes of the trajectory -- within the wave ...
@@ -260,14 +151,10 @@ __global__ __launch_bounds__(HB_THREADS) void fo_hr_brake_ladder_verdict_kernel(
   }
 }
 
-// the instantiation of K maps at the class width NC
 template <int NC>
 void hblv_launch(int K, dim3 grid, dim3 block, size_t lds, hipStream_t s, const HrBrakeLadderVerdictArgs &a, const HbluPack &pk) {
-  switch (K) {
-    case 1: hipLaunchKernelGGL((fo_hr_brake_ladder_verdict_kernel<NC, 1>), grid, block, lds, s, a, pk); break;
-    case 2: hipLaunchKernelGGL((fo_hr_brake_ladder_verdict_kernel<NC, 2>), grid, block, lds, s, a, pk); break;
-    default: hipLaunchKernelGGL((fo_hr_brake_ladder_verdict_kernel<NC, 3>), grid, block, lds, s, a, pk); break;
-  }
+  hbu_launch_maps(K, fo_hr_brake_ladder_verdict_kernel<NC, 1>, fo_hr_brake_ladder_verdict_kernel<NC, 2>, fo_hr_brake_ladder_verdict_kernel<NC, 3>,
+                  grid, block, lds, s, a, pk);
 }
 
 }  // namespace

@@ -63,10 +63,8 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hc_traj_kernel(const HcTrajArgs
   if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < a.T ? l : a.T); }
   int q = HC_NONE;
   if (k < Lm) {
-    // cells beyond the raster and the window have no key: the scan never leaves their union
-    const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-    const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
-    fo_hr_scan_footprint(a, i, K, HC_NONE, lox, loy, hix, hiy, [&](int v) { q = q < v ? q : v; });
+    const HrBox sb = fo_hr_scan_box(a);
+    fo_hr_scan_footprint(a, i, K, HC_NONE, sb.lox, sb.loy, sb.hix, sb.hiy, [&](int v) { q = q < v ? q : v; });
   }
   a.qmin[i] = q;
 }

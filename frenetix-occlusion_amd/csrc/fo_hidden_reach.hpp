@@ -172,6 +172,16 @@ struct HrTrajArgs {
   int32_t *cells, *first, *slack;       // [M][T], [M], [M]
 };
 
+// The box every footprint scan is clipped to: cells beyond the raster and the window have no arrival step and no key, so a scan
+// never leaves their union.  The ONE statement of it: every kernel that scans footprints takes its box from here.
+struct HrBox { int lox, loy, hix, hiy; };
+template <class Args>
+__device__ __forceinline__ HrBox fo_hr_scan_box(const Args &a) {
+  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
+  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  return HrBox{lox, loy, hix, hiy};
+}
+
 // The footprint of pose i of the trajectory arrays of `a` (HrTrajArgs, or the clearance's / the witness' arguments: the same field
 // names): every world-raster cell of the rectangle's bounding box (one cell of slack, clipped to [lox, hix] x [loy, hiy]) whose
 // centre passes the float64 point-in-rectangle test gets f(v, gx, gy), v = map[cell] inside the window, outside it 0 on raster
@@ -242,14 +252,12 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_traj_kernel(const HrTrajArgs
     Lm = a.T;
     if (a.len) { const int l = a.len[m]; Lm = l < 0 ? 0 : (l < a.T ? l : a.T); }
   }
-  // cells beyond the raster and the window have no arrival step: the scan never leaves their union
-  const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-  const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
+  const HrBox sb = fo_hr_scan_box(a);
   int first = 0x7fffffff, slack = 0x7fffffff;
   for (int k = kl; k < a.T; k += G) {
     int n = 0;
     if (live && k < Lm) {
-      fo_hr_scan_footprint(a, (size_t)m * a.T + k, A, 255, lox, loy, hix, hiy, [&](int av) {
+      fo_hr_scan_footprint(a, (size_t)m * a.T + k, A, 255, sb.lox, sb.loy, sb.hix, sb.hiy, [&](int av) {
         if (av != 255) {
           const int d = av - k;
           slack = slack < d ? slack : d;

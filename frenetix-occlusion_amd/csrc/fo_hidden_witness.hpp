@@ -77,9 +77,8 @@ __global__ __launch_bounds__(HR_THREADS) void fo_hr_witness_kernel(const HrWitne
   }
   int bd = 0x7fffffff, by = 0x7fffffff, bx = 0x7fffffff;          // the smallest (d, gy, gx) of this lane's rows
   if (ks >= 0) {
-    const int lox = a.ix0 < 0 ? a.ix0 : 0, loy = a.iy0 < 0 ? a.iy0 : 0;
-    const int hix = (a.ix0 + a.nx > a.rnx ? a.ix0 + a.nx : a.rnx) - 1, hiy = (a.iy0 + a.ny > a.rny ? a.iy0 + a.ny : a.rny) - 1;
-    fo_hr_scan_footprint_rows(a, (size_t)m * a.T + ks, A, 255, lox, loy, hix, hiy, k, HW_LANES, [&](int av, int gx, int gy) {
+    const HrBox sb = fo_hr_scan_box(a);
+    fo_hr_scan_footprint_rows(a, (size_t)m * a.T + ks, A, 255, sb.lox, sb.loy, sb.hix, sb.hiy, k, HW_LANES, [&](int av, int gx, int gy) {
       if (av <= ks) {
         const int d = hw_dist(a, gx, gy);                         // rows and columns ascend: the first cell of a d stays
         if (d < bd) { bd = d; by = gy; bx = gx; }

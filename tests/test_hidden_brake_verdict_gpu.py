@@ -177,6 +177,27 @@ def test_tie_over_class_and_map_counts(torch_cuda, C_, K):
         _tie(torch, sm, sc, sc.M, 5, same, same_q, sc.thr[:C_], map_of, [cap] * K, (C_, K, "alias"), alias=(1, 0))
 
 
+def test_against_the_checkers_own_walk(torch_cuda):
+    """the ties above hold the verdict against the users ENTRY, whose kernel walks a manoeuvre with the very code this kernel walks
+    with (hbu_walk): a fault in it moves both alike.  Here the checker's walk (tests/ref_hidden_brake_users.py) and fold stand in the
+    entry's place: T = 31, five users on three maps, ragged lengths, B in {1, 5, T}"""
+    torch = torch_cuda
+    sm, road = UG._parked()
+    sc = _scene(TIE_SCENES[31], US.USERS)
+    assert len(sc.keys) == 3
+    _, _, ref_commit, ref_first = UG.BU.brake_users(sc.keys, sc.win, road, sc.qmins, SC.ORIGIN, SC.CS, sc.x, sc.y, sc.head, sc.arc, sc.v, UG.HL,
+                                                   UG.HW, UG.WB, sc.a_brake, sc.dt, sc.thr, sc.map_of, sc.lens)
+    assert (ref_commit >= 0).any() and (ref_commit < 0).any()
+    for B in (1, 5, 31):
+        rc, msg, out = _raw_verdict(torch, sm, sc.win, sc.r2_caps, sc.keys, sc.qmins, sc.x, sc.y, sc.head, sc.v, sc.arc, sc.a_brake, sc.dt,
+                                    sc.thr, sc.map_of, B, lens=sc.lens)
+        assert rc == 0, (B, msg)
+        commit, fail_safe, user = BV.verdict(ref_commit, B)
+        for name, want in (("commit", commit), ("first", ref_first), ("fail_safe", fail_safe), ("user", user)):
+            got = getattr(out, name)
+            assert np.array_equal(got, want), (B, name, np.argwhere(got != want)[:4].tolist())
+
+
 # ------------------------------------------------------------------------------------------------ 2. the pose preparation
 def _poses(torch, sm, x, y, theta, v, lens=None):
     out = sm.hidden_poses(*(torch.as_tensor(a).to(sm.device) for a in (x, y, theta, v)), lengths=lens)
