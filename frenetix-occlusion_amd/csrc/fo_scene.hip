@@ -52,6 +52,9 @@
 //   fo_hidden_brake_verdict.hpp  fo_hr_brake_verdict_kernel  the fail-safe verdict: the users walk over the first B brake starts,
 //                                            folded into the reserved cost columns and the safety flag (fo_hidden_verdict.hpp: the
 //                                            fold as plain functions of values)
+//   fo_hidden_brake_impact.hpp  fo_hr_brake_impact_kernel  the impact verdict: the same walk, keeping the speed the ego has left at
+//                                            the hit; the worst harm over the classes folded likewise (fo_hidden_impact.hpp: the harm
+//                                            rows, the choice and the fold as plain functions of values)
 //   fo_hidden_brake_ladder_verdict.hpp  fo_hr_brake_ladder_verdict_kernel  the ladder verdict: the ladder-users walk over the first B
 //                                            brake starts, reduced to the level the worst start needs and folded likewise
 //                                            (fo_hidden_ladder_verdict.hpp: the reduction and the fold as plain functions of values)
@@ -75,6 +78,7 @@
 #include "fo_hidden_brake_ladder_users.hpp"
 #include "fo_hidden_poses.hpp"
 #include "fo_hidden_brake_verdict.hpp"
+#include "fo_hidden_brake_impact.hpp"
 #include "fo_hidden_brake_ladder_verdict.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"

@@ -673,6 +673,57 @@ int fo_scene_hidden_brake_verdict(fo_ctx *ctx, const fo_hidden_brake_verdict_t *
   return FO_OK;
 }
 
+// the impact verdict of every trajectory over its first B brake starts against every class of road user on the key map it names --
+// the worst harm that remains after braking, folded into the reserved cost columns and the safety flag: one launch
+// (fo_hidden_brake_impact.hpp); map_of and the table travel as kernel arguments, the harm rows and speeds in the caller's device buffer
+int fo_scene_hidden_brake_impact(fo_ctx *ctx, const fo_hidden_brake_impact_t *p, void *stream) {
+  const char *fn = "fo_scene_hidden_brake_impact";
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  if ((rc = hbu_check_head(ctx, *p, fn))) return rc;
+  if ((rc = hb_check_brake(ctx, p->a_brake, p->dt, fn))) return rc;
+  if (!(p->harm_limit >= 0.0))                                   // (NaN fails the comparison; +inf passes)
+    return fo_fail(ctx, FO_E_ARG, "%s: harm_limit = %g, a harm >= 0 (or +inf) is needed", fn, p->harm_limit);
+  if (p->M == 0) return FO_OK;
+  const int T = p->T, B = p->B, K = p->K, C = p->C;
+  if ((rc = hb_check_samples(ctx, T, fn))) return rc;
+  if ((rc = hb_check_starts(ctx, B, T, fn))) return rc;
+  if ((rc = hb_check_table_size(ctx, C, T, fn))) return rc;
+  if ((rc = hbu_check_inputs(ctx, *p, fn))) return rc;
+  if (!p->d_speed_of || !p->d_harm_rows)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_speed_of [C] and d_harm_rows [C][4] are required with M > 0", fn);
+  if (!p->d_harm || !p->d_user || !p->d_speed || !p->d_at || !p->d_commit || !p->d_first)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_harm [M][2], d_user [M], d_speed, d_at, d_commit and d_first [C][M] are required with M > 0", fn);
+  if ((rc = hb_check_cost_pair(ctx, p->d_cost_or_null, p->d_safe_or_null, fn))) return rc;
+  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HbuMaps mp = hbu_maps(*p);
+  const HrBrakeImpactArgs a{p->M, T, brake_verdict_group(B), brake_verdict_per_block(T, K, B), C, B, p->d_x, p->d_y, p->d_heading,
+                            p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster,
+                            sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2],
+                            mp.qmin[0], mp.qmin[1], mp.qmin[2], mp.map_of, p->d_v, p->d_arc, p->a_brake, p->dt, p->d_speed_of,
+                            p->d_harm_rows, p->harm_limit, p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null, p->d_harm,
+                            p->d_user, p->d_speed, p->d_at, p->d_commit, p->d_first};
+  const HbThr thr = hb_thr(p->h_thr, C * T);
+  const dim3 grid((unsigned)brake_verdict_blocks(p->M, T, K, B)), block(HB_THREADS);
+  const size_t lds = brake_verdict_lds_bytes(T, K, C, B);
+  hipStream_t s = (hipStream_t)stream;
+  if (brake_users_width(C) == 4) hbi_launch<4>(K, grid, block, lds, s, a, thr);
+  else hbi_launch<8>(K, grid, block, lds, s, a, thr);
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
+// the harm row of a class of hidden road user (fo_hidden_impact.hpp), for the caller that builds d_harm_rows
+int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_coeff_t *hc, double *row) {
+  if (!hc || !row || !(size > 0.0) || !(size < INFINITY) || !(ego_mass > 0.0) || !(ego_mass < INFINITY)) return FO_E_ARG;
+  double r[4];
+  if (!fo_hidden_impact_row_of(type, size, ego_mass, *hc, r)) return FO_E_ARG;
+  for (int i = 0; i < 4; ++i) row[i] = r[i];
+  return FO_OK;
+}
+
 // the ladder verdict of every trajectory over its first B brake starts against every class of road user on the key map it names --
 // the level the worst start needs, folded into the reserved cost columns and the safety flag: one launch
 // (fo_hidden_brake_ladder_verdict.hpp); the levels, map_of and the table travel as kernel arguments

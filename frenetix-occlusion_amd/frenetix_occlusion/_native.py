@@ -55,7 +55,7 @@ EXPORTS = [
     "fo_scene_set_occlusion_memory_vehicles", "fo_scene_hidden_witness", "fo_scene_hidden_brake",
     "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
     "fo_scene_hidden_brake_ladder_users", "fo_scene_hidden_poses", "fo_scene_hidden_brake_verdict",
-    "fo_scene_hidden_brake_ladder_verdict",
+    "fo_scene_hidden_brake_ladder_verdict", "fo_scene_hidden_brake_impact", "fo_hidden_impact_row",
 ]
 
 
@@ -211,6 +211,14 @@ class HiddenBrakeLadderVerdict(C.Structure):    # fo_hidden_brake_ladder_verdict
         ("d_first", C.c_void_p)]
 
 
+class HiddenBrakeImpact(C.Structure):   # fo_hidden_brake_impact_t
+    _fields_ = _HIDDEN_USERS_HEAD + [
+        ("a_brake", C.c_double), ("dt", C.c_double), ("h_thr", C.POINTER(C.c_int32)), ("B", C.c_int32),
+        ("d_speed_of", C.c_void_p), ("d_harm_rows", C.c_void_p), ("harm_limit", C.c_double), ("d_finite_or_null", C.c_void_p),
+        ("d_cost_or_null", C.c_void_p), ("d_safe_or_null", C.c_void_p), ("d_harm", C.c_void_p), ("d_user", C.c_void_p),
+        ("d_speed", C.c_void_p), ("d_at", C.c_void_p), ("d_commit", C.c_void_p), ("d_first", C.c_void_p)]
+
+
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
 HIDDEN_CLEARANCE_METRIC = {"euclid": 0, "road": 1}   # FO_HIDDEN_CLEARANCE_EUCLID / _ROAD
 
@@ -328,6 +336,8 @@ def load():
     lib.fo_scene_hidden_poses.argtypes = [vp, C.POINTER(HiddenPoses), vp]
     lib.fo_scene_hidden_brake_verdict.argtypes = [vp, C.POINTER(HiddenBrakeVerdict), vp]
     lib.fo_scene_hidden_brake_ladder_verdict.argtypes = [vp, C.POINTER(HiddenBrakeLadderVerdict), vp]
+    lib.fo_scene_hidden_brake_impact.argtypes = [vp, C.POINTER(HiddenBrakeImpact), vp]
+    lib.fo_hidden_impact_row.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(HarmCoeff), C.POINTER(C.c_double)]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])
     lib.fo_scene_candidate_count.argtypes = [vp, ip, vp]

@@ -1130,6 +1130,7 @@ def hidden_brake_verdict(self, x, y, theta, v, *, vehicle, users, dt, a_brake, s
     self.ctx.call("fo_scene_hidden_brake_verdict", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
     self._hbv_inputs = (tv, poses, p.clearances, cost, safe)
+    self._hbv_args = args                                   # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
     return HiddenBrakeVerdict(fail_safe, user, commit, first, poses, B, commit_min, users, p.map_of, p.thr, p.clearances)
 
 
@@ -1227,3 +1228,177 @@ def hidden_brake_ladder_verdict(self, x, y, theta, v, *, vehicle, users, dt, lev
     self._hblv_args = args                                  # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
     return HiddenBrakeLadderVerdict(need, at, blocking, user, decel, need_of, first, levels, B, a_limit, users, poses, p.map_of, p.thr,
                                     p.clearances)
+
+
+def hidden_impact_rows(kinds, ego_mass, coeff=None, fn="hidden_impact_rows"):
+    """The harm rows ``[C, 4]`` (host float64) of the road users ``kinds`` -- one ``(type_name, length, width)`` each -- against an
+    ego of ``ego_mass`` kg, from the library's own ``fo_hidden_impact_row`` (csrc/fo_hidden_impact.hpp, where what a row means
+    stands); ``coeff``: the entries of harm_params.json as :func:`metrics.metric.load_harm_coeff` returns them (None: the package's).
+    A type the reference has no protection entry for is refused."""
+    from .metrics.metric import load_harm_coeff
+    coeff = load_harm_coeff() if coeff is None else dict(coeff)
+    try:
+        if set(coeff) != {n for n, _ in N.HarmCoeff._fields_}:
+            raise TypeError
+        hc = N.HarmCoeff(**{k: float(v) for k, v in coeff.items()})
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: coeff must hold the eight entries of harm_params.json (metrics.metric.load_harm_coeff)") from None
+    try:
+        ego_mass = float(ego_mass)
+    except (TypeError, ValueError):
+        ego_mass = float("nan")
+    if not (ego_mass > 0.0 and math.isfinite(ego_mass)):
+        raise ValueError(f"{fn}: ego_mass must be positive and finite")
+    rows = np.empty((len(kinds), 4), dtype=np.float64)
+    lib = N.load()
+    for c, kind in enumerate(kinds):
+        try:
+            name, length, width = kind
+            code = N.TYPE_CODES.get(str(name).lower(), -1)
+            size = float(length) * float(width)
+        except (TypeError, ValueError):
+            raise ValueError(f"{fn}: kinds[{c}] = {kind!r}, a (type_name, length, width) is needed") from None
+        if code < 0:
+            raise ValueError(f"{fn}: kinds[{c}]: the harm model has no protection entry for the type {name!r}")
+        if not (size > 0.0 and math.isfinite(size)):
+            raise ValueError(f"{fn}: kinds[{c}]: length and width must be positive and finite")
+        row = (C.c_double * 4)()
+        if lib.fo_hidden_impact_row(code, size, ego_mass, C.byref(hc), row) != N.FO_OK:
+            raise ValueError(f"{fn}: kinds[{c}] = {kind!r} has no harm row")
+        rows[c] = row[:]
+    return rows
+
+
+@dataclass
+class HiddenBrakeImpact:
+    """what :meth:`SensorModel.hidden_brake_impact` returns (DESIGN.md §5.10 "Impact verdict"; device tensors): ``harm [M, 2]`` float64
+    -- (obstacle harm, ego harm), the reference's MAIS3+ probabilities head-on and at the worst area of impact, of the user whose
+    obstacle harm is greatest at the speed the ego has left where it is hit; (0, 0) where no user hits a brake start, (1, 1) where the
+    candidate has a non-finite pose and fails closed; ``user [M]`` int32 that user (the lowest on a tie), -1 = none, -2 = fails
+    closed; per user ``speed [C, M]`` float64 -- the greatest ego speed at a hit over the brake starts walked, 0.0 without a hit --,
+    ``at [C, M]`` int32 the first brake start that attains it, -1 = none, and ``commit``, ``first [C, M]`` int32 as in
+    :class:`HiddenBrakeVerdict`.  ``rows`` (host float64 ``[C, 4]``) and ``speed_of`` (host ``[C]``) the harm rows and speeds of the
+    users, ``kinds`` their ``(type_name, length, width)``, ``harm_limit`` the bound above which a candidate lost its safety flag;
+    ``poses``, ``starts``, ``users``, ``map_of``, ``thr``, ``clearances`` as in :class:`HiddenBrakeVerdict`.
+
+    Not claimed: the bound is head-on and worst-area for every user; a standing ego that is reached carries no harm; brake starts
+    beyond ``starts`` are not looked at; this is harm, not risk -- there is no collision probability in it."""
+    harm: torch.Tensor
+    user: torch.Tensor
+    speed: torch.Tensor
+    at: torch.Tensor
+    commit: torch.Tensor
+    first: torch.Tensor
+    rows: np.ndarray
+    speed_of: np.ndarray
+    kinds: tuple
+    harm_limit: float
+    poses: Optional[HiddenPoses] = None
+    starts: int = 0
+    users: tuple = ()
+    map_of: tuple = ()
+    thr: Optional[np.ndarray] = None
+    clearances: tuple = ()
+
+    def obstacle_harm(self):
+        """``[M]`` float64: what the cost row holds in its first reserved column"""
+        return self.harm[:, 0]
+
+    def ego_harm(self):
+        """``[M]`` float64: the ego's harm against the same user at the same speed"""
+        return self.harm[:, 1]
+
+    def critical_user(self):
+        """``[M]`` int64: the user whose obstacle harm is greatest, -1 = no user hits, -2 where the candidate has a non-finite pose"""
+        return self.user.to(torch.int64)
+
+    def impact_speed(self, user=None):
+        """``[M]`` float64 (m/s): the ego speed at the hit against ``user`` -- against the chosen user by default, 0.0 where there is
+        none.  Torch ops on the tensors' device, nothing is read back."""
+        if user is not None:
+            return self.speed[user]
+        u = self.user.to(torch.int64)
+        picked = self.speed.gather(0, u.clamp(min=0).unsqueeze(0))[0]
+        return torch.where(u >= 0, picked, torch.zeros_like(picked))
+
+    def harm_of(self, c):
+        """``[M, 2]`` float64: (obstacle harm, ego harm) of user ``c`` from ``speed[c]`` by the same row, (0, 0) where it has no hit;
+        elementwise torch ops on the device (not a hot path; ``exp`` is torch's, the last bits may differ from ``harm``)"""
+        p = self.rows[c]
+        w = self.speed[c] + float(self.speed_of[c])
+        both = torch.stack((1.0 / (1.0 + torch.exp(p[0] + p[1] * w)), 1.0 / (1.0 + torch.exp(p[2] + p[3] * w))), dim=1)
+        return torch.where((self.at[c] >= 0).unsqueeze(1), both, torch.zeros_like(both))
+
+
+def _harm_limit(harm_limit, fn):
+    try:
+        harm_limit = float(harm_limit)
+    except (TypeError, ValueError):
+        harm_limit = float("nan")
+    if not harm_limit >= 0.0:
+        raise ValueError(f"{fn}: harm_limit >= 0 (inf is possible, nan is not)")
+    return harm_limit
+
+
+def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, a_brake, starts, harm_limit, coeff=None, cost=None,
+                        safe=None, margin=None, inflate=0.0, lengths=None, poses=None):
+    """Hidden-traffic impact verdict (``fo_scene_hidden_brake_impact``; DESIGN.md §5.10 "Impact verdict"): for the hidden road
+    ``users`` of :meth:`hidden_brake_users`, of the ``kinds`` ``(type_name, length, width)`` -- one per user --, over the first
+    ``starts`` brake starts alone (an integer in ``[1, T]``, None = T: what a planner executes before it replans), the worst harm
+    that remains after braking at ``a_brake``: the reference's MAIS3+ probability at the speed the ego of ``ego_mass`` kg has left
+    where a manoeuvre is hit, head-on and at the worst area of impact -- and, with ``cost [M, 16]`` float64 / ``safe [M]`` uint8 of a
+    sweep or planning step over the SAME candidates (both or neither), the obstacle's harm and the user in the two reserved cost
+    columns, and ``safe = 0`` where that harm exceeds ``harm_limit`` (``>= 0``, ``inf`` allowed).  The stage only ever takes safety
+    away.  It owns the same two columns as :meth:`hidden_brake_verdict` and :meth:`hidden_brake_ladder_verdict`: fold one of the
+    three into a row.  ``coeff``: the entries of harm_params.json (None: the package's).
+
+    Everything runs on the device and on the current stream: the pose preparation (:meth:`hidden_poses`; ``poses=`` an earlier
+    :class:`HiddenPoses` of the same candidates skips it, ``theta`` may then be None), one ``hidden_clearance`` per distinct
+    ``(metric, flow)`` on the device headings, and ONE launch for the walk, the harm and the fold.  The harm rows are built once per
+    distinct ``(users, kinds, ego_mass, coeff)`` and kept on the device: after the first call nothing is uploaded.  Nothing is read
+    back and nobody waits; returns a :class:`HiddenBrakeImpact`."""
+    fn = "hidden_brake_impact"
+    users = _road_users(users, x, fn)
+    try:
+        kinds = tuple((str(k[0]), float(k[1]), float(k[2])) for k in kinds)
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{fn}: kinds must hold one (type_name, length, width) per user") from None
+    if len(kinds) != len(users):
+        raise ValueError(f"{fn}: {len(kinds)} kinds for {len(users)} users: one (type_name, length, width) per user")
+    harm_limit = _harm_limit(harm_limit, fn)
+    from .metrics.metric import load_harm_coeff
+    coeff = load_harm_coeff() if coeff is None else dict(coeff)
+    try:
+        key = (tuple(s for s, _, _ in users), kinds, float(ego_mass), tuple(sorted((str(k), float(q)) for k, q in coeff.items())))
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: ego_mass and the entries of coeff must be numbers") from None
+    cache = self.__dict__.setdefault("_hbi_rows", {})
+    if key not in cache:
+        rows = hidden_impact_rows(kinds, ego_mass, coeff, fn)
+        speed_of = np.array(key[0], dtype=np.float64)
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = (rows, speed_of, N.on_device(rows, self.device), N.on_device(speed_of, self.device))
+    rows, speed_of, d_rows, d_speed_of = cache[key]
+    if poses is None:
+        poses = hidden_poses(self, x, y, theta, v, lengths)
+    p = _users_call(self, fn, users, x, y, None, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+    a_brake = _a_brake(a_brake, fn)
+    B = _ladder_starts(starts, p.T, fn)
+    dev, M, C_ = self.device, p.M, len(users)
+    _cost_safe(cost, safe, M, p.x.device, fn)
+    tv = N.on_device(v, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    user, at, commit, first = new(M), new(C_, M), new(C_, M), new(C_, M)
+    harm = torch.empty((M, 2), dtype=torch.float64, device=dev)
+    speed = torch.empty((C_, M), dtype=torch.float64, device=dev)
+    args = N.HiddenBrakeImpact(**p.fields(tv, poses.arc, dt), a_brake=a_brake, B=B, d_speed_of=N.ptr(d_speed_of),
+                               d_harm_rows=N.ptr(d_rows), harm_limit=harm_limit, d_finite_or_null=N.ptr(poses.finite),
+                               d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe), d_harm=N.ptr(harm), d_user=N.ptr(user),
+                               d_speed=N.ptr(speed), d_at=N.ptr(at), d_commit=N.ptr(commit), d_first=N.ptr(first))
+    self.ctx.call("fo_scene_hidden_brake_impact", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_users)
+    self._hbi_inputs = (tv, poses, p.clearances, cost, safe)
+    self._hbi_args = args                                   # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
+    return HiddenBrakeImpact(harm, user, speed, at, commit, first, rows, speed_of, kinds, harm_limit, poses, B, users, p.map_of, p.thr,
+                             p.clearances)

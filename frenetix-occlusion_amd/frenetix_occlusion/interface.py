@@ -545,6 +545,59 @@ class FOInterface:
                                                              levels=levels, starts=starts, a_limit=vt[4] if a_limit is None else a_limit,
                                                              cost=cost, safe=safe, inflate=inflate)
 
+    def phantom_kind(self, type_name):
+        """``(type_name, length, width)`` of the phantom :class:`FOAgentManager` makes of ``type_name``: the configuration's
+        dimensions with the prediction's size factors (agent.py:402-405), so that the harm model's mass by size is the sweep's"""
+        am = self.config["agent_manager"]
+        key = str(type_name).lower()
+        if not isinstance(am.get(key), dict) or "length" not in am[key] or "width" not in am[key]:
+            raise ValueError(f"hidden_brake_impact: the configuration's agent_manager has no dimensions for the type {type_name!r}: "
+                             "hand kinds over as (type_name, length, width)")
+        pr = am["prediction"]
+        big = key == "bicycle"
+        fl = pr["size_factor_length_l"] if big else pr["size_factor_length_s"]
+        fw = pr["size_factor_width_l"] if big else pr["size_factor_width_s"]
+        return (str(type_name), float(am[key]["length"]) * float(fl), float(am[key]["width"]) * float(fw))
+
+    def hidden_brake_impact(self, trajectories, users, kinds=None, harm_limit=None, starts=None, a_brake=None, cost=None, safe=None,
+                            margin=None, inflate=0.0):
+        """EXTENSION, not part of the reference: the IMPACT VERDICT against the hidden road users of :meth:`hidden_brake_users` -- the
+        worst harm that remains after braking at ``a_brake`` (None: the vehicle's ``a_max``) from one of the first ``starts`` brake
+        starts (None: all): the reference's MAIS3+ probability at the speed the ego has left where it is hit, head-on and at the
+        worst area of impact (:meth:`SensorModel.hidden_brake_impact`; returns its
+        :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeImpact`: ``harm [M, 2]``, ``user [M]``, ``speed``, ``at``, ``commit``,
+        ``first [C, M]``; ``.obstacle_harm()``, ``.ego_harm()``, ``.critical_user()``, ``.impact_speed()``, ``.harm_of(c)``).
+        ``kinds``: one ``(type_name, length, width)`` or one type name per user -- a name alone takes the dimensions of the phantom
+        the agent manager makes of that type (:meth:`phantom_kind`), so the numbers sit beside the sweep's ``max_obst_harm``; None:
+        Pedestrian, Bicycle, Car by ascending speed, possible only with exactly three users.  With ``cost [M, 16]`` / ``safe [M]``
+        of a sweep over the same candidates the obstacle's harm and the user are folded into the two reserved columns, and
+        candidates whose harm exceeds ``harm_limit`` (None: the configuration's ``metric_thresholds.harm``; ``null`` there: inf)
+        lose their safety flag.  The other defaults as for :meth:`hidden_brake_users`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_impact needs a previous evaluate_scenario")
+        users = tuple(users)
+        if kinds is None:
+            if len(users) != 3:
+                raise ValueError("hidden_brake_impact: kinds is required unless exactly three users are given "
+                                 "(then: Pedestrian, Bicycle, Car by ascending speed)")
+            order = sorted(range(3), key=lambda c: float(users[c][0]))
+            kinds = [None] * 3
+            for name, c in zip(("Pedestrian", "Bicycle", "Car"), order):
+                kinds[c] = name
+        kinds = [self.phantom_kind(k) if isinstance(k, str) else tuple(k) for k in kinds]
+        if harm_limit is None:
+            harm_limit = ((self.config.get("metrics") or {}).get("metric_thresholds") or {}).get("harm")
+            harm_limit = float("inf") if harm_limit is None else harm_limit
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        return self.sensor_model.hidden_brake_impact(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], ego_mass=vt[3],
+                                                     users=users, kinds=kinds, margin=om["margin"] if margin is None else margin,
+                                                     dt=self.dt, a_brake=vt[4] if a_brake is None else a_brake, starts=starts,
+                                                     harm_limit=harm_limit, cost=cost, safe=safe, inflate=inflate)
+
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the
         metric sweep.  ``witness.select(max_agents, merge_cells)`` picks the candidates whose witnesses differ (one per block of

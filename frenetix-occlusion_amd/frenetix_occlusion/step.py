@@ -17,28 +17,46 @@ from . import _native as N
 from .sweep import SweepResult
 
 
-def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict):
-    """the ``hidden_ladder_verdict=`` of :class:`PlanningStep` as a dict of its own, or its refusal; None stays None"""
-    if hidden_ladder_verdict is None:
+_LADDER_KEYS = ("vehicle", "users", "dt", "levels", "starts", "a_limit")
+_IMPACT_KEYS = ("vehicle", "ego_mass", "users", "kinds", "dt", "a_brake", "starts", "harm_limit")
+
+
+def _stage_options(name, given, required, optional):
+    """the dict ``given`` for the stage ``name=`` of :class:`PlanningStep` as a dict of its own, or its refusal; None stays None"""
+    if given is None:
         return None
-    if hidden_verdict is not None:
-        raise ValueError("PlanningStep: hidden_verdict and hidden_ladder_verdict own the same two reserved cost columns: "
-                         "a step runs one or the other")
     try:
-        lv = dict(hidden_ladder_verdict)
+        opts = dict(given)
     except (TypeError, ValueError):
-        raise ValueError(f"PlanningStep: hidden_ladder_verdict = {hidden_ladder_verdict!r} is no dict of keyword arguments") from None
-    unknown = set(lv) - {"vehicle", "users", "dt", "levels", "starts", "a_limit", "margin", "inflate", "lengths"}
-    missing = {"vehicle", "users", "dt", "levels", "starts", "a_limit"} - set(lv)
+        raise ValueError(f"PlanningStep: {name} = {given!r} is no dict of keyword arguments") from None
+    unknown = set(opts) - set(required) - set(optional)
+    missing = set(required) - set(opts)
     if unknown or missing:
-        raise ValueError(f"PlanningStep: hidden_ladder_verdict takes vehicle, users, dt, levels, starts, a_limit and optionally "
-                         f"margin, inflate, lengths (unknown: {sorted(map(str, unknown))}, missing: {sorted(missing)})")
-    return lv
+        raise ValueError(f"PlanningStep: {name} takes {', '.join(required)} and optionally {', '.join(optional)} "
+                         f"(unknown: {sorted(map(str, unknown))}, missing: {sorted(missing)})")
+    return opts
+
+
+def hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict):
+    """``(ladder, impact)``: the ``hidden_ladder_verdict=`` and ``hidden_impact_verdict=`` of :class:`PlanningStep` as dicts of their
+    own, or the refusal of the three stages together -- they own the same two reserved cost columns, so a step runs one of them;
+    None stays None"""
+    given = [n for n, q in (("hidden_verdict", hidden_verdict), ("hidden_ladder_verdict", hidden_ladder_verdict),
+                            ("hidden_impact_verdict", hidden_impact_verdict)) if q is not None]
+    if len(given) > 1:
+        raise ValueError(f"PlanningStep: {' and '.join(given)} own the same two reserved cost columns: a step runs one of them")
+    return (_stage_options("hidden_ladder_verdict", hidden_ladder_verdict, _LADDER_KEYS, ("margin", "inflate", "lengths")),
+            _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths")))
+
+
+def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict=None):
+    """the ``hidden_ladder_verdict=`` of :class:`PlanningStep` as a dict of its own, or its refusal; None stays None"""
+    return hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict)[0]
 
 
 class PlanningStep:
     def __init__(self, sensor_model, spawn_locator, sweep, x, y, theta, v, a=None, mode="reduced", lists="f64", shard=None,
-                 mirror=False, hidden_verdict=None, hidden_ladder_verdict=None):
+                 mirror=False, hidden_verdict=None, hidden_ladder_verdict=None, hidden_impact_verdict=None):
         """``hidden_verdict`` (an extension, DESIGN.md §5.10 "Fail-safe verdict"): a dict of the keyword arguments of
         :meth:`SensorModel.hidden_brake_verdict` -- ``vehicle``, ``users``, ``dt``, ``a_brake``, ``starts``, ``commit_min`` and
         optionally ``margin``, ``inflate``, ``lengths`` -- :meth:`run` then queues the pose preparation, the clearances and the
@@ -53,6 +71,13 @@ class PlanningStep:
         :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeLadderVerdict`.  The two stages own the same two reserved cost
         columns: giving both is a ValueError.  None: the step queues and allocates exactly what it does without.
 
+        ``hidden_impact_verdict`` (an extension, DESIGN.md §5.10 "Impact verdict"): a dict of the keyword arguments of
+        :meth:`SensorModel.hidden_brake_impact` -- ``vehicle``, ``ego_mass``, ``users``, ``kinds``, ``dt``, ``a_brake``, ``starts``,
+        ``harm_limit`` and optionally ``coeff``, ``margin``, ``inflate``, ``lengths`` -- queued where the other two stages are;
+        ``out.hidden_impact_verdict`` is its :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeImpact`.  It owns the same two
+        columns: giving two of the three stages is a ValueError.  None: nothing is queued or allocated for it, and ``out`` has no
+        such attribute.
+
         ``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
         :class:`~frenetix_occlusion.distributed.CostGather` for the batch size -- this rank's step covers its contiguous
         block of the candidates (scene stage and phantoms replicated), writes the block's cost rows into the collective's
@@ -66,7 +91,7 @@ class PlanningStep:
             raise ValueError("PlanningStep: the three stages must share one context (one ego, one GPU)")
         if mode not in ("reduced", "pair", "full"):
             raise ValueError(f"unknown output mode '{mode}'")
-        ladder = hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict)    # (refused before anything is allocated)
+        ladder, impact = hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict)    # (refused before anything is allocated)
         self.sm, self.sl, self.sw = sensor_model, spawn_locator, sweep
         self.ctx = sweep.ctx
         self.mode, self.lists, self.mirror = mode, lists, bool(mirror)
@@ -120,6 +145,9 @@ class PlanningStep:
         self._hidden_ladder_verdict = ladder
         if ladder is not None and self.gather is not None and ladder.get("lengths") is not None:
             ladder["lengths"] = ladder["lengths"][self.gather.lo:self.gather.hi]
+        self._hidden_impact_verdict = impact
+        if impact is not None and self.gather is not None and impact.get("lengths") is not None:
+            impact["lengths"] = impact["lengths"][self.gather.lo:self.gather.hi]
 
     def _fill(self, w, O):
         """everything that does not change from step to step"""
@@ -226,6 +254,11 @@ class PlanningStep:
             tx, ty, tth, tv = self.traj[:4]
             self.out.hidden_ladder_verdict = sm.hidden_brake_ladder_verdict(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
                                                                             **self._hidden_ladder_verdict)
+        if self._hidden_impact_verdict is not None:
+            # the same place: one of the three stages owns the two columns
+            tx, ty, tth, tv = self.traj[:4]
+            self.out.hidden_impact_verdict = sm.hidden_brake_impact(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
+                                                                    **self._hidden_impact_verdict)
         if self.gather is not None:
             # the one collective of the path, queued behind the step
             self.out.cost_all = self.gather.gather(None if self._direct or self.M == 0 else self.out.cost)

@@ -988,6 +988,90 @@ typedef struct {
 } fo_hidden_brake_ladder_verdict_t;
 int fo_scene_hidden_brake_ladder_verdict(fo_ctx *ctx, const fo_hidden_brake_ladder_verdict_t *p, void *stream);
 
+/* EXTENSION, not part of the reference: hidden-traffic IMPACT VERDICT (DESIGN.md §5.10 "Impact verdict") -- "if hidden traffic is
+ * there, how bad is what braking cannot avoid?": per candidate the worst harm that remains after braking from one of the brake
+ * starts it executes before it replans, in the reference's own unit (the MAIS3+ probability of metrics/utils/harm_model.py), as a
+ * finite, graded term in the two reserved columns of the cost row and the safety flag that fo_step_run leaves in HBM.  It still
+ * orders a fan of candidates where "can it stop clear?" is "no" for every one.  The walk of fo_scene_hidden_brake_verdict, which
+ * keeps the speed the ego has left where a manoeuvre is hit.  Opt-in and additive: one launch on the caller's stream, behind the
+ * step whose cost rows it folds into; nothing is read back.  It writes the SAME two reserved columns as the two verdicts above: a
+ * step runs one of the three stages.
+ *  Inputs: those of fo_scene_hidden_brake_verdict word for word, without commit_min, and: d_speed_of [C] float64, the speed of class
+ *   c in m/s; d_harm_rows [C][4] float64, the rows (p0, p1, p2, p3) of the classes (fo_hidden_impact_row; what a row means stands in
+ *   csrc/fo_hidden_impact.hpp: the reference's harm head-on and at the worst area of impact); harm_limit, float64, >= 0, +inf
+ *   allowed, not NaN.  Both buffers live on the device: the caller builds them once per set of users and keeps them.
+ *  Write Lm for the length as in the verdict entry, ends = min(B, Lm), v for d_v, and fm[c] = first[c][m], bf[c], st for the first
+ *   hit of class c on the manoeuvre that brakes from b and that manoeuvre's stop sample, as fo_scene_hidden_brake_users writes them
+ *   (brake_first[c][m][b], stop[m][b]).
+ *  1. Brake start b < ends is HIT by class c iff (0 <= fm[c] <= b) or (0 <= bf[c] < st): the commit rule of the verdict entry.
+ *  2. The ego speed at the hit u(c, b): if 0 <= fm[c] <= b, u = v[m][fm[c]] (the candidate itself is met at sample fm[c], before
+ *   braking from b changes anything); otherwise u = max(v[m][b] - a_brake * ((bf[c] - b) * dt), 0), the manoeuvre's speed at its
+ *   first hit -- positive, since bf[c] < st.
+ *  3. speed[c][m] = the greatest u(c, b) over the hit starts b (compared by >: a NaN never wins; -inf is the value before the first
+ *   one), at[c][m] = the lowest b that attains it; with no hit start (or none whose u compares): speed = 0.0, at = -1.
+ *   commit[c][m] and first[c][m] are fo_scene_hidden_brake_verdict's, bit for bit.
+ *  4. With w = speed[c][m] + speed_of[c]: obstacle harm of class c = 1 / (1 + exp(p0 + p1 * w)), ego harm = 1 / (1 + exp(p2 + p3 * w));
+ *   float64, plain exp, no contraction.
+ *  5. user[m] = the lowest c with at[c][m] >= 0 whose obstacle harm is greatest (compared by >), -1 where no class has a hit;
+ *   harm[m] = (obstacle harm, ego harm) of that class, (0.0, 0.0) for -1.
+ *  6. finite[m] == 0: harm[m] = (1.0, 1.0) and user[m] = FO_HIDDEN_VERDICT_NOT_FINITE, whatever the walk found (a NaN pose fails
+ *   every footprint comparison and would read as "no hit": this case fails CLOSED); speed, at, commit and first stay the walk's.
+ *  7. With d_cost / d_safe: cost[m][FO_C_RES0] = harm[m][0], cost[m][FO_C_RES1] = (double)user[m]; if harm[m][0] > harm_limit or
+ *   the candidate is not finite: safe[m] = 0 and cost[m][FO_C_SAFE] = 0.0, otherwise both are left as found -- the stage only ever
+ *   takes safety away; a row that a refused rule list or an unusable covariance poisoned keeps its NaNs and safe = 0 and gets the
+ *   two columns.  No other column is touched.
+ *  Outputs, every byte written by every call: d_harm [M][2] float64; d_user [M] int32; d_speed [C][M] float64; d_at, d_commit,
+ *   d_first [C][M] int32.
+ *  Safety of the data: as fo_scene_hidden_brake_users; finite, speed_of and the rows may hold anything, no index depends on them.
+ *  Not claimed: what fo_scene_hidden_brake_users does not claim; the bound is head-on and worst-area for every user (a lane-bound
+ *   vehicle that can only arrive from the side is still priced head-on); a standing ego that is reached carries no harm (the
+ *   family's "moving ego" convention), so the quantity jumps where a manoeuvre just comes to rest; brake starts b >= B are not
+ *   looked at; there is no collision probability -- this is harm, not risk; that cost / safe belong to the same candidates is the
+ *   caller's word.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_impact:"), in this order: K outside [1, 3]; C outside [1, 8]; no h_thr; a window outside [1, 32768]^2; an
+ * r2_cap[k], k < K, negative or beyond FO_HIDDEN_REACH_MAX_HALO; map_of[c], c < C, outside [0, K); M < 0; a_brake negative or not
+ * finite; dt not positive and finite; harm_limit negative or NaN; with M > 0: T outside [1, 254]; B outside [1, T];
+ * C * T > FO_HIDDEN_BRAKE_MAX_TABLE; a row of h_thr that is negative, decreases or ends beyond 169 * r2_cap[map_of[c]]; no d_x /
+ * d_y / d_heading; no d_key[k] or d_qmin[k], k < K; no d_v or d_arc; no d_speed_of or d_harm_rows; a missing output; only one of
+ * d_cost_or_null / d_safe_or_null; extents refused as by fo_scene_hidden_reach.  FO_E_STATE: no scene. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  double a_brake, dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  const double *d_speed_of;                 /* [C] speed of class c, m/s */
+  const double *d_harm_rows;                /* [C][4] (p0, p1, p2, p3) */
+  double harm_limit;                        /* obstacle harm above it takes safety away; +inf: only non-finite candidates lose it */
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC] of the step: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  double *d_harm;                           /* [M][2] (obstacle, ego) */
+  int32_t *d_user;                          /* [M] */
+  double *d_speed;                          /* [C][M] */
+  int32_t *d_at, *d_commit, *d_first;       /* [C][M] */
+} fo_hidden_brake_impact_t;
+int fo_scene_hidden_brake_impact(fo_ctx *ctx, const fo_hidden_brake_impact_t *p, void *stream);
+
+/* The harm row of a class of hidden road user, on the host (needs no context and no device): row = (p0, p1, p2, p3) for a road
+ * user of `type` (FO_TYPE_*) and `size` = length * width in m^2 against an ego of ego_mass kg (csrc/fo_hidden_impact.hpp, where what
+ * a row means stands).  FO_OK, or FO_E_ARG: no hc / row, a type whose protection entry is None (FO_TYPE_STRUCTURE and anything
+ * outside the FO_TYPE_* codes), size or ego_mass not positive and finite. */
+int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_coeff_t *hc, double *row);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

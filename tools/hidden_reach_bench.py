@@ -57,6 +57,13 @@ at the same B followed by the torch reduction over b, and ``hidden_brake_verdict
 is asserted (exact integers, ``decel`` bit for bit): the outputs are that reduction of the ladder-users entry's.  Also the distribution
 of ``need``.
 
+``--brake-impact B``: ``hidden_brake_impact`` for the README's road users -- a pedestrian, a cyclist and a car of the dimensions the
+agent manager gives its phantoms -- over the first B brake starts (§5.10 "Impact verdict"), next to ``hidden_brake_verdict`` at the same
+B: the whole call, the call with the poses handed over, and the ONE launch of either alone (the structure a call left handed to the C
+entry again).  In every run the tie is asserted: ``commit`` and ``first`` are the verdict's, ``speed`` (bit for bit) and ``at`` are steps
+1 - 3 of the definition on ``hidden_brake_users``' ``brake_first`` / ``stop`` / ``first``.  Also the distribution of the obstacle's harm
+over the candidates and how many distinct values it takes.
+
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
 import ctypes as C
@@ -118,6 +125,8 @@ def main():
     ap.add_argument("--brake-ladder-verdict", type=int, default=None, metavar="B",
                     help="time hidden_brake_ladder_verdict over the first B brake starts next to hidden_brake_ladder_users + its reduction "
                          "and to hidden_brake_verdict at one level")
+    ap.add_argument("--brake-impact", type=int, default=None, metavar="B",
+                    help="time hidden_brake_impact over the first B brake starts next to hidden_brake_verdict")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -289,6 +298,59 @@ def main():
             res[f"candidates_by_user_B{B}"] = {str(c): int((v_out.user == c).sum()) for c in range(-2, len(users))}
         res["hidden_poses_call_ms"] = _median_ms(lambda: sm.hidden_poses(tx, ty, tth, tv), a.calls)
         res["brake_users_call_ms"] = _median_ms(hbu, a.calls)
+    if a.brake_impact:
+        users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
+        kinds = (("Pedestrian", 0.3 * 1.2, 0.5 * 1.3), ("Bicycle", 2.0 * 1.4, 0.9 * 2.5), ("Car", 4.8 * 1.2, 2.0 * 1.3))   # length, width x size factors
+        a_brake = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
+        B = a.brake_impact
+        if not 1 <= B <= T:
+            ap.error(f"--brake-impact B: 1 <= B <= {T}")
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbi = lambda **kw: sm.hidden_brake_impact(tx, ty, tth, tv, vehicle=veh, ego_mass=SY.VEHICLE_BMW320I[3], users=users, kinds=kinds, dt=0.1,
+                                                  a_brake=a_brake, starts=B, harm_limit=math.inf, **kw)
+        hbv = lambda **kw: sm.hidden_brake_verdict(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake, starts=B, commit_min=B, **kw)
+        i_out = hbi()
+        v_out = hbv(poses=i_out.poses)
+        # the tie, in every run: the verdict entry, and the users entry on the stage's own headings and on host x, y (whose arc numpy sums
+        # as the device does), then steps 1 - 3 in numpy float64
+        assert torch.equal(i_out.commit, v_out.commit) and torch.equal(i_out.first, v_out.first)
+        u_out = sm.hidden_brake_users(traj["x"], traj["y"], None, tv, vehicle=veh, users=users, dt=0.1, a_brake=a_brake, heading=i_out.poses.heading)
+        assert torch.equal(u_out.arc, i_out.poses.arc)
+        bf, st, fm = (t.cpu().numpy().astype(np.int64) for t in (u_out.brake_first[:, :, :B], u_out.stop[:, :B], u_out.first))
+        vh = np.asarray(traj["v"], dtype=np.float64)
+        b = np.arange(B)[None, None, :]
+        met = (fm[:, :, None] >= 0) & (fm[:, :, None] <= b)
+        hit = met | ((bf >= 0) & (bf < st[None]))
+        left = vh[None, :, :B] - a_brake * ((bf - b) * 0.1)
+        u = np.where(met, np.take_along_axis(vh, np.clip(fm, 0, None).T, axis=1).T[:, :, None], np.where(left > 0.0, left, 0.0))
+        u = np.where(hit, u, -np.inf)
+        speed, at = u.max(axis=2), u.argmax(axis=2)
+        none = ~hit.any(axis=2)
+        speed, at = np.where(none, 0.0, speed), np.where(none, -1, at)
+        assert np.array_equal(i_out.at.cpu().numpy(), at) and i_out.speed.cpu().numpy().tobytes() == speed.tobytes()
+        # the launches alone: a call that folds into a scratch cost / safe pair, then the structure it left handed to the C entry again
+        scratch = (torch.zeros((M, N.NC), dtype=torch.float64, device=dev), torch.ones((M,), dtype=torch.uint8, device=dev))
+        keep_v = hbv(poses=i_out.poses, cost=scratch[0], safe=scratch[1])
+        launch_v = (C.byref(sm._hbv_args), N.current_stream(sm._dev_index))
+        res["brake_verdict_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_verdict", *launch_v), a.calls)
+        keep_i = hbi(poses=i_out.poses, cost=scratch[0], safe=scratch[1])
+        launch_i = (C.byref(sm._hbi_args), N.current_stream(sm._dev_index))
+        res["brake_impact_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_impact", *launch_i), a.calls)
+        assert torch.equal(keep_i.harm, i_out.harm) and torch.equal(keep_v.fail_safe, v_out.fail_safe)
+        assert torch.equal(scratch[0][:, 14].view(torch.int64), i_out.harm[:, 0].contiguous().view(torch.int64))
+        res["brake_impact_users"] = [list(u_) for u_ in users]
+        res["brake_impact_kinds"] = [list(k) for k in kinds]
+        res["brake_impact_B"] = B
+        res["brake_impact_call_ms"] = _median_ms(hbi, a.calls)
+        res["brake_impact_call_reused_poses_ms"] = _median_ms(lambda: hbi(poses=i_out.poses), a.calls)
+        res["brake_verdict_call_ms"] = _median_ms(hbv, a.calls)
+        res["brake_verdict_call_reused_poses_ms"] = _median_ms(lambda: hbv(poses=i_out.poses), a.calls)
+        harm = i_out.harm[:, 0].cpu().numpy()
+        res["obstacle_harm_quantiles"] = {str(q): float(np.quantile(harm, q)) for q in (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0)}
+        res["obstacle_harm_distinct_values"] = int(len(np.unique(harm)))
+        res["obstacle_harm_zero"] = int((harm == 0.0).sum())
+        res["candidates_by_impact_user"] = {str(c): int((i_out.user == c).sum()) for c in range(-2, len(users))}
+        res["candidates_by_fail_safe"] = {str(k): int((v_out.fail_safe == k).sum()) for k in range(B + 1)}
     if a.brake_ladder_verdict:
         users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
         a_max = SY.VEHICLE_BMW320I[4]
