@@ -135,9 +135,13 @@ __device__ __forceinline__ void hbu_first(const int32_t *Q, size_t plane, const 
 // and 2 only while they have an open class; outside the window the value it was handed (0 on raster road, NONE elsewhere) holds
 // for every map.  Class c tests the minimum of map_of[c]; the walk ends when every class has its first hit, or at the standing
 // pose, where one scan settles every open class (the rows of the table do not decrease).
-template <int NC, int NK, class Args>
+// hit(i, p, h): called at a MOVING pose (i < st) with the sample, the pose and the mask h != 0 of the classes first hit at it, before
+// they leave `open` (fo_hidden_brake_impact_lanes.hpp prices them there); hits of a standing ego are not handed over.  The default
+// does nothing and leaves no code.
+struct HbuNoHit { __device__ __forceinline__ void operator()(int, const HbPose &, unsigned) const {} };
+template <int NC, int NK, class Args, class H = HbuNoHit>
 __device__ __forceinline__ void hbu_walk(const Args &a, const double *X, const int32_t *TH, int Lm, int b, double vb, double a_brake, int st,
-                                         const HbuMasks &mk, const HrBox &sb, int (&bf)[NC]) {
+                                         const HbuMasks &mk, const HrBox &sb, int (&bf)[NC], H &&hit = H()) {
   const int T = a.T, last = Lm - 1;
   const double *Y = X + T, *C = Y + T, *S = C + T, *ARC = S + T;
   const double arc_end = ARC[last];
@@ -179,6 +183,7 @@ __device__ __forceinline__ void hbu_walk(const Args &a, const double *X, const i
       break;
     }
     const unsigned h = hbu_hits<NC, NK>(q, TH, T, i, open, cm1, cm2);
+    if (h) hit(i, p, h);
 #pragma unroll
     for (int c = 0; c < NC; ++c)
       if (h >> c & 1u) bf[c] = i;

@@ -118,6 +118,35 @@ FO_HIDDEN_IMPACT_HD fo_hidden_impact_t fo_hidden_impact_classes(const double (&s
   return r;
 }
 
+// the same steps where the caller holds the closing speed w of each class itself (fo_scene_hidden_brake_impact_lanes, whose w is no
+// sum: csrc/fo_hidden_approach.hpp): the two logistics at closing[c], the same choice, the same fail-closed row
+template <int NC>
+FO_HIDDEN_IMPACT_HD fo_hidden_impact_t fo_hidden_impact_classes_closing(const double (&closing)[NC], const int32_t (&at)[NC], int C,
+                                                                        const double *rows, bool finite) {
+  fo_hidden_impact_t r{0.0, 0.0, -1};
+  double best = -1.0;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+  for (int c = 0; c < NC; ++c)
+    if (c < C && at[c] >= 0) {
+      const double ho = fo_hidden_impact_logistic(rows[4 * c], rows[4 * c + 1], closing[c]);
+      const double he = fo_hidden_impact_logistic(rows[4 * c + 2], rows[4 * c + 3], closing[c]);
+      if (ho > best) {
+        best = ho;
+        r.obst_harm = ho;
+        r.ego_harm = he;
+        r.user = c;
+      }
+    }
+  if (!finite) {
+    r.obst_harm = 1.0;
+    r.ego_harm = 1.0;
+    r.user = FO_HIDDEN_VERDICT_NOT_FINITE;
+  }
+  return r;
+}
+
 // step 7: the two reserved columns always; the flag and FO_C_SAFE only ever lose safety; no other column is touched (a row that
 // fo_verdict poisoned keeps its NaNs)
 FO_HIDDEN_IMPACT_HD void fo_hidden_impact_fold(const fo_hidden_impact_t &r, double harm_limit, double *cost_row, uint8_t *safe) {

@@ -79,6 +79,7 @@
 #include "fo_hidden_poses.hpp"
 #include "fo_hidden_brake_verdict.hpp"
 #include "fo_hidden_brake_impact.hpp"
+#include "fo_hidden_brake_impact_lanes.hpp"
 #include "fo_hidden_brake_ladder_verdict.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"

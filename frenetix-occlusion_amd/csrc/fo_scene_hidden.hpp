@@ -370,6 +370,76 @@ static int hidden_clearance_call(fo_ctx *ctx, const fo_hidden_clearance_t *p, bo
   return FO_OK;
 }
 
+// the impact verdict of every trajectory over its first B brake starts against every class of road user on the key map it names --
+// the worst harm that remains after braking, folded into the reserved cost columns and the safety flag: one launch; map_of and the
+// table travel as kernel arguments, the harm rows and speeds in the caller's device buffer.  The ONE host part of both entries:
+// head-on (fo_hidden_brake_impact.hpp) and, LANES, by approach angle (fo_hidden_brake_impact_lanes.hpp), which asks for its mask,
+// its two numbers, its two outputs and the map's move table on top
+template <bool LANES, class P>
+static int hidden_brake_impact_call(fo_ctx *ctx, const P *p, const char *fn, void *stream) {
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  if ((rc = hbu_check_head(ctx, *p, fn))) return rc;
+  if ((rc = hb_check_brake(ctx, p->a_brake, p->dt, fn))) return rc;
+  if (!(p->harm_limit >= 0.0))                                   // (NaN fails the comparison; +inf passes)
+    return fo_fail(ctx, FO_E_ARG, "%s: harm_limit = %g, a harm >= 0 (or +inf) is needed", fn, p->harm_limit);
+  if constexpr (LANES) {
+    if (p->dir_mask >> p->C != 0u)
+      return fo_fail(ctx, FO_E_ARG, "%s: dir_mask = 0x%x has bits at or above C = %d", fn, p->dir_mask, p->C);
+    if (!(fabs(p->cos_h) <= 1.0) || !(fabs(p->sin_h) <= 1.0))    // (NaN fails the comparison)
+      return fo_fail(ctx, FO_E_ARG, "%s: cos_h = %g, sin_h = %g, the cosine and sine of 22.5 deg + heading_slack in [-1, 1] are needed",
+                     fn, p->cos_h, p->sin_h);
+    if (p->dir_mask != 0u && (rc = hr_check_moves(ctx, fn))) return rc;
+  }
+  if (p->M == 0) return FO_OK;
+  const int T = p->T, B = p->B, K = p->K, C = p->C;
+  if ((rc = hb_check_samples(ctx, T, fn))) return rc;
+  if ((rc = hb_check_starts(ctx, B, T, fn))) return rc;
+  if ((rc = hb_check_table_size(ctx, C, T, fn))) return rc;
+  if ((rc = hbu_check_inputs(ctx, *p, fn))) return rc;
+  if (!p->d_speed_of || !p->d_harm_rows)
+    return fo_fail(ctx, FO_E_ARG, "%s: d_speed_of [C] and d_harm_rows [C][4] are required with M > 0", fn);
+  if constexpr (LANES) {
+    if (!p->d_harm || !p->d_user || !p->d_closing || !p->d_cosine || !p->d_at || !p->d_commit || !p->d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_harm [M][2], d_user [M], d_closing, d_cosine, d_at, d_commit and d_first [C][M] are required with M > 0", fn);
+  } else {
+    if (!p->d_harm || !p->d_user || !p->d_speed || !p->d_at || !p->d_commit || !p->d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_harm [M][2], d_user [M], d_speed, d_at, d_commit and d_first [C][M] are required with M > 0", fn);
+  }
+  if ((rc = hb_check_cost_pair(ctx, p->d_cost_or_null, p->d_safe_or_null, fn))) return rc;
+  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HbuMaps mp = hbu_maps(*p);
+  const HbThr thr = hb_thr(p->h_thr, C * T);
+  const dim3 grid((unsigned)brake_verdict_blocks(p->M, T, K, B)), block(HB_THREADS);
+  const size_t lds = brake_verdict_lds_bytes(T, K, C, B);
+  hipStream_t s = (hipStream_t)stream;
+  if constexpr (LANES) {
+    const uint32_t dir = p->cos_h > -1.0 ? p->dir_mask : 0u;     // h >= pi: every class is head-on, the table is not read
+    const HrBrakeImpactLanesArgs a{p->M, T, brake_verdict_group(B), brake_verdict_per_block(T, K, B), C, B, p->d_x, p->d_y, p->d_heading,
+                                   p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster,
+                                   sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1],
+                                   mp.key[2], mp.qmin[0], mp.qmin[1], mp.qmin[2], mp.map_of, p->d_v, p->d_arc, p->a_brake, p->dt,
+                                   p->d_speed_of, p->d_harm_rows, p->harm_limit, sc->map->d_lane_moves, dir, p->cos_h, p->sin_h,
+                                   p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null, p->d_harm, p->d_user, p->d_closing,
+                                   p->d_cosine, p->d_at, p->d_commit, p->d_first};
+    if (brake_users_width(C) == 4) hbil_launch<4>(K, grid, block, lds, s, a, thr);
+    else hbil_launch<8>(K, grid, block, lds, s, a, thr);
+  } else {
+    const HrBrakeImpactArgs a{p->M, T, brake_verdict_group(B), brake_verdict_per_block(T, K, B), C, B, p->d_x, p->d_y, p->d_heading,
+                              p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster,
+                              sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2],
+                              mp.qmin[0], mp.qmin[1], mp.qmin[2], mp.map_of, p->d_v, p->d_arc, p->a_brake, p->dt, p->d_speed_of,
+                              p->d_harm_rows, p->harm_limit, p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null, p->d_harm,
+                              p->d_user, p->d_speed, p->d_at, p->d_commit, p->d_first};
+    if (brake_users_width(C) == 4) hbi_launch<4>(K, grid, block, lds, s, a, thr);
+    else hbi_launch<8>(K, grid, block, lds, s, a, thr);
+  }
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
 extern "C" {
 
 int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
@@ -673,46 +743,13 @@ int fo_scene_hidden_brake_verdict(fo_ctx *ctx, const fo_hidden_brake_verdict_t *
   return FO_OK;
 }
 
-// the impact verdict of every trajectory over its first B brake starts against every class of road user on the key map it names --
-// the worst harm that remains after braking, folded into the reserved cost columns and the safety flag: one launch
-// (fo_hidden_brake_impact.hpp); map_of and the table travel as kernel arguments, the harm rows and speeds in the caller's device buffer
+// the impact verdict, head-on and by approach angle: hidden_brake_impact_call above
 int fo_scene_hidden_brake_impact(fo_ctx *ctx, const fo_hidden_brake_impact_t *p, void *stream) {
-  const char *fn = "fo_scene_hidden_brake_impact";
-  int rc;
-  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
-  Scene *sc = (Scene *)ctx->scene;
-  if ((rc = hbu_check_head(ctx, *p, fn))) return rc;
-  if ((rc = hb_check_brake(ctx, p->a_brake, p->dt, fn))) return rc;
-  if (!(p->harm_limit >= 0.0))                                   // (NaN fails the comparison; +inf passes)
-    return fo_fail(ctx, FO_E_ARG, "%s: harm_limit = %g, a harm >= 0 (or +inf) is needed", fn, p->harm_limit);
-  if (p->M == 0) return FO_OK;
-  const int T = p->T, B = p->B, K = p->K, C = p->C;
-  if ((rc = hb_check_samples(ctx, T, fn))) return rc;
-  if ((rc = hb_check_starts(ctx, B, T, fn))) return rc;
-  if ((rc = hb_check_table_size(ctx, C, T, fn))) return rc;
-  if ((rc = hbu_check_inputs(ctx, *p, fn))) return rc;
-  if (!p->d_speed_of || !p->d_harm_rows)
-    return fo_fail(ctx, FO_E_ARG, "%s: d_speed_of [C] and d_harm_rows [C][4] are required with M > 0", fn);
-  if (!p->d_harm || !p->d_user || !p->d_speed || !p->d_at || !p->d_commit || !p->d_first)
-    return fo_fail(ctx, FO_E_ARG, "%s: d_harm [M][2], d_user [M], d_speed, d_at, d_commit and d_first [C][M] are required with M > 0", fn);
-  if ((rc = hb_check_cost_pair(ctx, p->d_cost_or_null, p->d_safe_or_null, fn))) return rc;
-  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
-  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const HbuMaps mp = hbu_maps(*p);
-  const HrBrakeImpactArgs a{p->M, T, brake_verdict_group(B), brake_verdict_per_block(T, K, B), C, B, p->d_x, p->d_y, p->d_heading,
-                            p->d_len_or_null, p->hl, p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster,
-                            sc->map->rnx, sc->map->rny, p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2],
-                            mp.qmin[0], mp.qmin[1], mp.qmin[2], mp.map_of, p->d_v, p->d_arc, p->a_brake, p->dt, p->d_speed_of,
-                            p->d_harm_rows, p->harm_limit, p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null, p->d_harm,
-                            p->d_user, p->d_speed, p->d_at, p->d_commit, p->d_first};
-  const HbThr thr = hb_thr(p->h_thr, C * T);
-  const dim3 grid((unsigned)brake_verdict_blocks(p->M, T, K, B)), block(HB_THREADS);
-  const size_t lds = brake_verdict_lds_bytes(T, K, C, B);
-  hipStream_t s = (hipStream_t)stream;
-  if (brake_users_width(C) == 4) hbi_launch<4>(K, grid, block, lds, s, a, thr);
-  else hbi_launch<8>(K, grid, block, lds, s, a, thr);
-  FO_HIP_TRY(ctx, hipGetLastError());
-  return FO_OK;
+  return hidden_brake_impact_call<false>(ctx, p, "fo_scene_hidden_brake_impact", stream);
+}
+
+int fo_scene_hidden_brake_impact_lanes(fo_ctx *ctx, const fo_hidden_brake_impact_lanes_t *p, void *stream) {
+  return hidden_brake_impact_call<true>(ctx, p, "fo_scene_hidden_brake_impact_lanes", stream);
 }
 
 // the harm row of a class of hidden road user (fo_hidden_impact.hpp), for the caller that builds d_harm_rows

@@ -1281,8 +1281,15 @@ class HiddenBrakeImpact:
     users, ``kinds`` their ``(type_name, length, width)``, ``harm_limit`` the bound above which a candidate lost its safety flag;
     ``poses``, ``starts``, ``users``, ``map_of``, ``thr``, ``clearances`` as in :class:`HiddenBrakeVerdict`.
 
-    Not claimed: the bound is head-on and worst-area for every user; a standing ego that is reached carries no harm; brake starts
-    beyond ``starts`` are not looked at; this is harm, not risk -- there is no collision probability in it."""
+    With ``approach="lanes"`` (DESIGN.md §5.10 "Impact verdict by approach angle") ``speed`` is None and the per-user pair is
+    ``closing [C, M]`` float64 -- the greatest closing speed over the brake starts walked, every lane-bound user at the worst angle
+    the lanes allow where it meets the ego, 0.0 without a hit -- and ``cosine [C, M]`` float64, the approach cosine at ``at``
+    (1.0 = head-on, and without a hit); ``at`` is then the first start that attains ``closing``.  ``approach`` and
+    ``heading_slack`` are the call's; with ``"head_on"`` ``closing`` and ``cosine`` are None.
+
+    Not claimed: the bound is worst-area for every user and head-on for every user that is not lane-bound (with ``"head_on"``: for
+    every user; ``approach="lanes"`` prices lane-bound users by their approach angle); a standing ego that is reached carries no
+    harm; brake starts beyond ``starts`` are not looked at; this is harm, not risk -- there is no collision probability in it."""
     harm: torch.Tensor
     user: torch.Tensor
     speed: torch.Tensor
@@ -1299,6 +1306,10 @@ class HiddenBrakeImpact:
     map_of: tuple = ()
     thr: Optional[np.ndarray] = None
     clearances: tuple = ()
+    closing: Optional[torch.Tensor] = None
+    cosine: Optional[torch.Tensor] = None
+    approach: str = "head_on"
+    heading_slack: float = 0.0
 
     def obstacle_harm(self):
         """``[M]`` float64: what the cost row holds in its first reserved column"""
@@ -1314,18 +1325,39 @@ class HiddenBrakeImpact:
 
     def impact_speed(self, user=None):
         """``[M]`` float64 (m/s): the ego speed at the hit against ``user`` -- against the chosen user by default, 0.0 where there is
-        none.  Torch ops on the tensors' device, nothing is read back."""
+        none.  Torch ops on the tensors' device, nothing is read back.  With ``approach="lanes"`` the ego speed at the hit is no
+        output: :meth:`closing_speed` is what is priced."""
+        if self.speed is None:
+            raise ValueError("impact_speed: with approach=\"lanes\" the ego speed at the hit is not an output; .closing_speed() is "
+                             "the speed that is priced and .approach_cosine() its angle")
+        return self._picked(self.speed, user, 0.0)
+
+    def _picked(self, per_user, user, none):
         if user is not None:
-            return self.speed[user]
+            return per_user[user]
         u = self.user.to(torch.int64)
-        picked = self.speed.gather(0, u.clamp(min=0).unsqueeze(0))[0]
-        return torch.where(u >= 0, picked, torch.zeros_like(picked))
+        picked = per_user.gather(0, u.clamp(min=0).unsqueeze(0))[0]
+        return torch.where(u >= 0, picked, torch.full_like(picked, none))
+
+    def closing_speed(self, user=None):
+        """``[M]`` float64 (m/s): the closing speed that is priced against ``user`` -- against the chosen user by default, 0.0 where
+        there is none.  With ``approach="head_on"`` it is ``speed + speed_of``."""
+        if self.closing is not None:
+            return self._picked(self.closing, user, 0.0)
+        w = torch.where(self.at >= 0, self.speed + torch.as_tensor(self.speed_of, device=self.speed.device).unsqueeze(1),
+                        torch.zeros_like(self.speed))
+        return self._picked(w, user, 0.0)
+
+    def approach_cosine(self, user=None):
+        """``[M]`` float64: the cosine of the reference's principal direction of force the closing speed was formed with, 1.0 =
+        head-on (and where there is no hit)"""
+        return self._picked(torch.ones_like(self.speed) if self.cosine is None else self.cosine, user, 1.0)
 
     def harm_of(self, c):
         """``[M, 2]`` float64: (obstacle harm, ego harm) of user ``c`` from ``speed[c]`` by the same row, (0, 0) where it has no hit;
         elementwise torch ops on the device (not a hot path; ``exp`` is torch's, the last bits may differ from ``harm``)"""
         p = self.rows[c]
-        w = self.speed[c] + float(self.speed_of[c])
+        w = self.closing[c] if self.closing is not None else self.speed[c] + float(self.speed_of[c])
         both = torch.stack((1.0 / (1.0 + torch.exp(p[0] + p[1] * w)), 1.0 / (1.0 + torch.exp(p[2] + p[3] * w))), dim=1)
         return torch.where((self.at[c] >= 0).unsqueeze(1), both, torch.zeros_like(both))
 
@@ -1341,7 +1373,7 @@ def _harm_limit(harm_limit, fn):
 
 
 def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, a_brake, starts, harm_limit, coeff=None, cost=None,
-                        safe=None, margin=None, inflate=0.0, lengths=None, poses=None):
+                        safe=None, margin=None, inflate=0.0, lengths=None, poses=None, approach="head_on", heading_slack=0.0):
     """Hidden-traffic impact verdict (``fo_scene_hidden_brake_impact``; DESIGN.md §5.10 "Impact verdict"): for the hidden road
     ``users`` of :meth:`hidden_brake_users`, of the ``kinds`` ``(type_name, length, width)`` -- one per user --, over the first
     ``starts`` brake starts alone (an integer in ``[1, T]``, None = T: what a planner executes before it replans), the worst harm
@@ -1352,6 +1384,13 @@ def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds
     away.  It owns the same two columns as :meth:`hidden_brake_verdict` and :meth:`hidden_brake_ladder_verdict`: fold one of the
     three into a row.  ``coeff``: the entries of harm_params.json (None: the package's).
 
+    ``approach="lanes"`` (``fo_scene_hidden_brake_impact_lanes``; DESIGN.md §5.10 "Impact verdict by approach angle") prices every
+    user with ``flow == "lanes"`` at the worst closing speed the lanes' driving directions allow at the cells where it meets the
+    ego -- ``dv = sqrt(v_ego^2 + v_user^2 + 2 v_ego v_user cos(pdof))`` at the greatest ``cos(pdof)`` over the headings within
+    22.5 degrees + ``heading_slack`` (radians, ``>= 0``; what a lane change or a swerve may add) of a direction the move table
+    leaves -- and every other user head-on as before; the result is never above the default's.  It needs the map's move table
+    (``lane_moves``) where a user is lane-bound.  ``"head_on"``, the default, is the call as it always was.
+
     Everything runs on the device and on the current stream: the pose preparation (:meth:`hidden_poses`; ``poses=`` an earlier
     :class:`HiddenPoses` of the same candidates skips it, ``theta`` may then be None), one ``hidden_clearance`` per distinct
     ``(metric, flow)`` on the device headings, and ONE launch for the walk, the harm and the fold.  The harm rows are built once per
@@ -1359,6 +1398,17 @@ def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds
     back and nobody waits; returns a :class:`HiddenBrakeImpact`."""
     fn = "hidden_brake_impact"
     users = _road_users(users, x, fn)
+    if approach not in ("head_on", "lanes"):
+        raise ValueError(f"{fn}: approach = {approach!r}: 'head_on' or 'lanes'")
+    try:
+        heading_slack = float(heading_slack)
+    except (TypeError, ValueError):
+        heading_slack = float("nan")
+    if not (heading_slack >= 0.0 and math.isfinite(heading_slack)):
+        raise ValueError(f"{fn}: heading_slack must be a finite angle >= 0 in radians")
+    dir_mask = sum(1 << c for c, u in enumerate(users) if u[2] == "lanes") if approach == "lanes" else 0
+    if dir_mask and getattr(self, "lane_moves", None) is None:
+        raise ValueError(f"{fn}: approach='lanes' with a lane-bound user needs the map's move table (lane_moves is None)")
     try:
         kinds = tuple((str(k[0]), float(k[1]), float(k[2])) for k in kinds)
     except (TypeError, ValueError, IndexError):
@@ -1392,13 +1442,22 @@ def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds
     user, at, commit, first = new(M), new(C_, M), new(C_, M), new(C_, M)
     harm = torch.empty((M, 2), dtype=torch.float64, device=dev)
     speed = torch.empty((C_, M), dtype=torch.float64, device=dev)
-    args = N.HiddenBrakeImpact(**p.fields(tv, poses.arc, dt), a_brake=a_brake, B=B, d_speed_of=N.ptr(d_speed_of),
-                               d_harm_rows=N.ptr(d_rows), harm_limit=harm_limit, d_finite_or_null=N.ptr(poses.finite),
-                               d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe), d_harm=N.ptr(harm), d_user=N.ptr(user),
-                               d_speed=N.ptr(speed), d_at=N.ptr(at), d_commit=N.ptr(commit), d_first=N.ptr(first))
-    self.ctx.call("fo_scene_hidden_brake_impact", C.byref(args), N.current_stream(self._dev_index))
+    common = dict(**p.fields(tv, poses.arc, dt), a_brake=a_brake, B=B, d_speed_of=N.ptr(d_speed_of), d_harm_rows=N.ptr(d_rows),
+                  harm_limit=harm_limit, d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe),
+                  d_harm=N.ptr(harm), d_user=N.ptr(user), d_at=N.ptr(at), d_commit=N.ptr(commit), d_first=N.ptr(first))
+    closing = cosine = None
+    if approach == "lanes":
+        closing, cosine, speed = speed, torch.empty((C_, M), dtype=torch.float64, device=dev), None
+        h = math.pi / 8.0 + heading_slack
+        cos_h, sin_h = (math.cos(h), math.sin(h)) if h < math.pi else (-1.0, 0.0)      # (cos_h = -1: every user is head-on)
+        args = N.HiddenBrakeImpactLanes(**common, d_closing=N.ptr(closing), d_cosine=N.ptr(cosine), dir_mask=dir_mask, cos_h=cos_h,
+                                        sin_h=sin_h)
+        self.ctx.call("fo_scene_hidden_brake_impact_lanes", C.byref(args), N.current_stream(self._dev_index))
+    else:
+        args = N.HiddenBrakeImpact(**common, d_speed=N.ptr(speed))
+        self.ctx.call("fo_scene_hidden_brake_impact", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
     self._hbi_inputs = (tv, poses, p.clearances, cost, safe)
     self._hbi_args = args                                   # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
     return HiddenBrakeImpact(harm, user, speed, at, commit, first, rows, speed_of, kinds, harm_limit, poses, B, users, p.map_of, p.thr,
-                             p.clearances)
+                             p.clearances, closing, cosine, approach, heading_slack)

@@ -560,7 +560,7 @@ class FOInterface:
         return (str(type_name), float(am[key]["length"]) * float(fl), float(am[key]["width"]) * float(fw))
 
     def hidden_brake_impact(self, trajectories, users, kinds=None, harm_limit=None, starts=None, a_brake=None, cost=None, safe=None,
-                            margin=None, inflate=0.0):
+                            margin=None, inflate=0.0, approach="head_on", heading_slack=0.0):
         """EXTENSION, not part of the reference: the IMPACT VERDICT against the hidden road users of :meth:`hidden_brake_users` -- the
         worst harm that remains after braking at ``a_brake`` (None: the vehicle's ``a_max``) from one of the first ``starts`` brake
         starts (None: all): the reference's MAIS3+ probability at the speed the ego has left where it is hit, head-on and at the
@@ -572,7 +572,10 @@ class FOInterface:
         Pedestrian, Bicycle, Car by ascending speed, possible only with exactly three users.  With ``cost [M, 16]`` / ``safe [M]``
         of a sweep over the same candidates the obstacle's harm and the user are folded into the two reserved columns, and
         candidates whose harm exceeds ``harm_limit`` (None: the configuration's ``metric_thresholds.harm``; ``null`` there: inf)
-        lose their safety flag.  The other defaults as for :meth:`hidden_brake_users`."""
+        lose their safety flag.  ``approach="lanes"`` prices every user with flow ``"lanes"`` at the worst closing speed the lanes'
+        driving directions allow where it meets the ego, within ``heading_slack`` radians of them, instead of head-on (``speed`` is
+        then None; ``closing``, ``cosine``, ``.closing_speed()``, ``.approach_cosine()``).  The other defaults as for
+        :meth:`hidden_brake_users`."""
         from .metrics.metric import trajectories_to_arrays
         from .sweep import _vehicle_tuple
         if self.timestep is None or self.sensor_model.window is None:
@@ -596,7 +599,8 @@ class FOInterface:
         return self.sensor_model.hidden_brake_impact(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], ego_mass=vt[3],
                                                      users=users, kinds=kinds, margin=om["margin"] if margin is None else margin,
                                                      dt=self.dt, a_brake=vt[4] if a_brake is None else a_brake, starts=starts,
-                                                     harm_limit=harm_limit, cost=cost, safe=safe, inflate=inflate)
+                                                     harm_limit=harm_limit, cost=cost, safe=safe, inflate=inflate, approach=approach,
+                                                     heading_slack=heading_slack)
 
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the

@@ -46,7 +46,7 @@ def hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_ve
     if len(given) > 1:
         raise ValueError(f"PlanningStep: {' and '.join(given)} own the same two reserved cost columns: a step runs one of them")
     return (_stage_options("hidden_ladder_verdict", hidden_ladder_verdict, _LADDER_KEYS, ("margin", "inflate", "lengths")),
-            _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths")))
+            _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths", "approach", "heading_slack")))
 
 
 def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict=None):
@@ -73,7 +73,7 @@ class PlanningStep:
 
         ``hidden_impact_verdict`` (an extension, DESIGN.md §5.10 "Impact verdict"): a dict of the keyword arguments of
         :meth:`SensorModel.hidden_brake_impact` -- ``vehicle``, ``ego_mass``, ``users``, ``kinds``, ``dt``, ``a_brake``, ``starts``,
-        ``harm_limit`` and optionally ``coeff``, ``margin``, ``inflate``, ``lengths`` -- queued where the other two stages are;
+        ``harm_limit`` and optionally ``coeff``, ``margin``, ``inflate``, ``lengths``, ``approach``, ``heading_slack`` -- queued where the other two stages are;
         ``out.hidden_impact_verdict`` is its :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeImpact`.  It owns the same two
         columns: giving two of the three stages is a ValueError.  None: nothing is queued or allocated for it, and ``out`` has no
         such attribute.

@@ -1024,7 +1024,8 @@ int fo_scene_hidden_brake_ladder_verdict(fo_ctx *ctx, const fo_hidden_brake_ladd
  *   d_first [C][M] int32.
  *  Safety of the data: as fo_scene_hidden_brake_users; finite, speed_of and the rows may hold anything, no index depends on them.
  *  Not claimed: what fo_scene_hidden_brake_users does not claim; the bound is head-on and worst-area for every user (a lane-bound
- *   vehicle that can only arrive from the side is still priced head-on); a standing ego that is reached carries no harm (the
+ *   vehicle that can only arrive from the side is still priced head-on: fo_scene_hidden_brake_impact_lanes below prices it by the
+ *   angle the lanes allow); a standing ego that is reached carries no harm (the
  *   family's "moving ego" convention), so the quantity jumps where a manoeuvre just comes to rest; brake starts b >= B are not
  *   looked at; there is no collision probability -- this is harm, not risk; that cost / safe belong to the same candidates is the
  *   caller's word.
@@ -1065,6 +1066,86 @@ typedef struct {
   int32_t *d_at, *d_commit, *d_first;       /* [C][M] */
 } fo_hidden_brake_impact_t;
 int fo_scene_hidden_brake_impact(fo_ctx *ctx, const fo_hidden_brake_impact_t *p, void *stream);
+
+/* EXTENSION, not part of the reference: hidden-traffic IMPACT VERDICT BY APPROACH ANGLE (DESIGN.md §5.10 "Impact verdict by approach
+ * angle") -- the impact verdict above with every LANE-BOUND class of road user priced at the worst closing speed the lanes' driving
+ * directions allow at the cells where it meets the ego, instead of the worst that is conceivable at all: the reference's
+ * dv = sqrt(v_ego^2 + v_obs^2 + 2 v_ego v_obs cos(pdof)), pdof = yaw_obs - theta_ego + pi (metrics/utils/harm_model.py:81-95), at the
+ * greatest cos(pdof) over the headings the map's move table (fo_scene_set_lane_moves) leaves a lane-abiding vehicle there.  Classes
+ * that are not lane-bound, off-lane cells and every byte that says nothing stay head-on: no output is above the head-on entry's, and
+ * where nothing is known every output is that entry's.  One launch; opt-in and additive like the entry above.
+ *  A move byte and a heading: bit k of a cell's byte is set iff cos(k * 45deg - yaw) >= cos(67.5deg) for a lanelet of heading yaw
+ *   that contains the cell (the union over those lanelets, 0xFF off-lane).  Direction k is CENTRAL in a byte when bits k - 1, k and
+ *   k + 1 (mod 8) are all set; every heading that generates a byte with a central direction lies within 22.5deg of a central one.
+ *   The headings a byte leaves are H = the union over its central k of [k * 45deg - h, k * 45deg + h], h = 22.5deg + heading_slack;
+ *   a byte without a central direction says nothing.
+ *  Inputs: those of fo_scene_hidden_brake_impact word for word, and: dir_mask, bit c set = class c is lane-bound; cos_h, sin_h,
+ *   float64, the cosine and sine of h as the caller's host computed them, both in [-1, 1]; cos_h <= -1 states h >= pi: every class
+ *   is head-on.  With dir_mask != 0 the context's map must have a move table.
+ *  Steps 1, 6 and 7, the commit rule, commit, first, the fail-closed rule and the fold are fo_scene_hidden_brake_impact's word for
+ *   word.  Steps 2 - 5 become:
+ *  2. The hit pose of a hit start b of class c, its sample i and its cells: if 0 <= fm[c] <= b the candidate's own pose at sample
+ *   i = fm[c]; otherwise the manoeuvre's pose at sample i = bf[c] (the pose the walk of fo_scene_hidden_brake_users held when it set
+ *   bf[c]).  The HIT CELLS are the cells the footprint scan of that pose visits -- centre inside the rectangle by the scan's float64
+ *   test -- whose key on map map_of[c] is <= thr[c][i]; outside the window a cell carries 0 on raster road and NONE elsewhere, as in
+ *   the walk.  mv(c, b) = the OR of the move bytes of the hit cells: the table's byte for a cell on the raster, 0xFF for one off it.
+ *  3. The approach cosine cm(c, b), the greatest cos(pdof) the lanes allow: cm = 1.0 exactly if class c is not in dir_mask, or mv
+ *   has no central direction, or cos_h <= -1.  Otherwise with (ct, st) the hit pose's unit heading and (ck, sk) the lattice unit
+ *   vector of direction k (0, +-1, +-sqrt(0.5)): g_k = -(ct * ck + st * sk); c_k = 1.0 if g_k >= cos_h, else
+ *   g_k * cos_h + sqrt(fmax(0, 1 - g_k * g_k)) * sin_h; cm = the greatest c_k over the central k, compared by >, starting from the
+ *   first central k.  float64, this operation order, no contraction, no trigonometric call.
+ *  4. The closing speed w(c, b): with u the ego speed at the hit exactly as step 2 of the entry above and s = speed_of[c]:
+ *   w = u + s if cm == 1.0 (bit for bit the head-on entry's), otherwise w = sqrt(fmax(0, u * u + s * s + 2 * u * s * cm)).
+ *  5. closing[c][m] = the greatest w(c, b) over the hit starts b < ends (compared by >: a NaN never wins), at[c][m] = the lowest b
+ *   that attains it, cosine[c][m] = cm at that start; without a hit start (or none whose w compares) 0.0, -1 and 1.0.  The harms
+ *   of class c are the two logistics of its row at w = closing[c][m] -- the rows still carry the mass split and the worst area of
+ *   impact.  user, harm, the non-finite rule and the fold as in the entry above.
+ *  Consequences: closing <= speed + speed_of of the head-on entry for every (c, m), hence harm <= its harm (the rows' speed
+ *   coefficients are negative); with dir_mask == 0, a table of 0xFF alone or cos_h <= -1 every output shared with the head-on entry
+ *   is that entry's bit for bit and closing == speed + speed_of bit for bit.
+ *  Outputs, every byte written by every call: d_harm [M][2] float64; d_user [M] int32; d_closing, d_cosine [C][M] float64; d_at,
+ *   d_commit, d_first [C][M] int32.
+ *  Not claimed: what fo_scene_hidden_brake_impact does not claim, but for the head-on pricing of lane-bound classes; a lane-abiding
+ *   vehicle is taken to head along its lane -- lane changes and swerves are what heading_slack is for; the area of impact stays
+ *   worst-case (the relative position at the hit is unknown); at an intersection cell the union of the lanelets widens the sector;
+ *   the maximum is over the closing speed per class, so the start `at` names can differ from the head-on entry's; the ego speed at
+ *   that start is not an output -- closing and cosine are.
+ * Refusals: those of fo_scene_hidden_brake_impact in its order (messages prefixed "fo_scene_hidden_brake_impact_lanes:"), and, after
+ * harm_limit: FO_E_ARG for a dir_mask with bits at or above C, cos_h or sin_h not finite or outside [-1, 1]; where that entry asks for
+ * d_speed: d_closing and d_cosine.  FO_E_STATE: no scene; dir_mask != 0 and the map has no move table. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;
+  int32_t win_ix0, win_iy0, win_nx, win_ny;
+  int32_t K;
+  int32_t C;
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];
+  const double *d_v;
+  const double *d_arc;
+  double a_brake, dt;
+  const int32_t *h_thr;                     /* HOST [C][T] */
+  int32_t B;
+  const double *d_speed_of;                 /* [C] */
+  const double *d_harm_rows;                /* [C][4] */
+  double harm_limit;
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC]: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  double *d_harm;                           /* [M][2] (obstacle, ego) */
+  int32_t *d_user;                          /* [M] */
+  double *d_closing;                        /* [C][M] the closing speed that is priced, m/s */
+  int32_t *d_at, *d_commit, *d_first;       /* [C][M] */
+  uint32_t dir_mask;                        /* bit c: class c is lane-bound */
+  double cos_h, sin_h;                      /* of h = 22.5deg + heading_slack */
+  double *d_cosine;                         /* [C][M] the approach cosine at `at` */
+} fo_hidden_brake_impact_lanes_t;
+int fo_scene_hidden_brake_impact_lanes(fo_ctx *ctx, const fo_hidden_brake_impact_lanes_t *p, void *stream);
 
 /* The harm row of a class of hidden road user, on the host (needs no context and no device): row = (p0, p1, p2, p3) for a road
  * user of `type` (FO_TYPE_*) and `size` = length * width in m^2 against an ego of ego_mass kg (csrc/fo_hidden_impact.hpp, where what

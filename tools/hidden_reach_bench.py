@@ -57,6 +57,10 @@ at the same B followed by the torch reduction over b, and ``hidden_brake_verdict
 is asserted (exact integers, ``decel`` bit for bit): the outputs are that reduction of the ladder-users entry's.  Also the distribution
 of ``need``.
 
+``--approach lanes`` (with ``--brake-impact B``): also ``approach="lanes"`` -- its launch next to the head-on launch in the same
+process (one profiler trace holds both kernels), and what it does to the grading: the distribution of the obstacle harm against
+head-on, the candidates whose user or start changes, the distinct values.  Every ``--brake-impact`` run asserts
+``closing <= speed + speed_of`` and ``harm <= head-on harm``.
 ``--brake-impact B``: ``hidden_brake_impact`` for the README's road users -- a pedestrian, a cyclist and a car of the dimensions the
 agent manager gives its phantoms -- over the first B brake starts (§5.10 "Impact verdict"), next to ``hidden_brake_verdict`` at the same
 B: the whole call, the call with the poses handed over, and the ONE launch of either alone (the structure a call left handed to the C
@@ -127,6 +131,9 @@ def main():
                          "and to hidden_brake_verdict at one level")
     ap.add_argument("--brake-impact", type=int, default=None, metavar="B",
                     help="time hidden_brake_impact over the first B brake starts next to hidden_brake_verdict")
+    ap.add_argument("--approach", default="head_on", choices=("head_on", "lanes"),
+                    help="with --brake-impact: lanes also times approach='lanes' and records what it does to the grading")
+    ap.add_argument("--heading-slack", type=float, default=0.0, help="with --approach lanes: heading_slack in radians")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
         ap.error("--flow lanes needs --metric road")
@@ -351,6 +358,38 @@ def main():
         res["obstacle_harm_zero"] = int((harm == 0.0).sum())
         res["candidates_by_impact_user"] = {str(c): int((i_out.user == c).sum()) for c in range(-2, len(users))}
         res["candidates_by_fail_safe"] = {str(k): int((v_out.fail_safe == k).sum()) for k in range(B + 1)}
+        # by approach angle: in every run never above head-on, per user and per candidate
+        l_out = hbi(poses=i_out.poses, approach="lanes", heading_slack=a.heading_slack)
+        w_head = torch.stack([i_out.closing_speed(c) for c in range(len(users))])
+        assert bool((l_out.closing <= w_head).all()) and bool((l_out.harm[:, 0] <= i_out.harm[:, 0]).all())
+        assert torch.equal(l_out.commit, i_out.commit) and torch.equal(l_out.first, i_out.first)
+        assert torch.equal(l_out.closing[0], w_head[0]) and bool((l_out.cosine[0] == 1.0).all())         # the pedestrian is not lane-bound
+        if a.approach == "lanes":
+            keep_l = hbi(poses=i_out.poses, cost=scratch[0], safe=scratch[1], approach="lanes", heading_slack=a.heading_slack)
+            launch_l = (C.byref(sm._hbi_args), N.current_stream(sm._dev_index))
+            res["brake_impact_lanes_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_impact_lanes", *launch_l), a.calls)
+            unbound = N.HiddenBrakeImpactLanes.from_buffer_copy(sm._hbi_args)        # the same launch with nobody lane-bound: the kernel
+            unbound.dir_mask = 0                                                    # before any further scan (the outputs are head-on's)
+            launch_u = (C.byref(unbound), N.current_stream(sm._dev_index))
+            res["brake_impact_lanes_launch_unbound_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_impact_lanes", *launch_u), a.calls)
+            sm.ctx.call("fo_scene_hidden_brake_impact_lanes", *launch_l)
+            res["brake_impact_launch_again_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_impact", *launch_i), a.calls)
+            assert torch.equal(keep_l.harm, l_out.harm)
+            res["brake_impact_lanes_call_reused_poses_ms"] = _median_ms(
+                lambda: hbi(poses=i_out.poses, approach="lanes", heading_slack=a.heading_slack), a.calls)
+            lharm = l_out.harm[:, 0].cpu().numpy()
+            cosn, lat = l_out.cosine.cpu().numpy(), l_out.at.cpu().numpy()
+            res["heading_slack"] = a.heading_slack
+            res["lanes_obstacle_harm_quantiles"] = {str(q): float(np.quantile(lharm, q)) for q in (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0)}
+            res["lanes_obstacle_harm_distinct_values"] = int(len(np.unique(lharm)))
+            res["lanes_obstacle_harm_ratio_quantiles"] = {str(q): float(np.quantile(lharm[harm > 0] / harm[harm > 0], q))
+                                                          for q in (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0)} if (harm > 0).any() else {}
+            res["lanes_candidates_below_head_on"] = int((lharm < harm).sum())
+            res["lanes_candidates_changing_user"] = int((l_out.user != i_out.user).sum())
+            res["lanes_candidates_changing_start"] = int((l_out.at != i_out.at).any(dim=0).sum())
+            res["lanes_candidates_by_impact_user"] = {str(c): int((l_out.user == c).sum()) for c in range(-2, len(users))}
+            res["lanes_hits_below_head_on_by_user"] = [int(((cosn[c] < 1.0) & (lat[c] >= 0)).sum()) for c in range(len(users))]
+            res["lanes_hits_by_user"] = [int((lat[c] >= 0).sum()) for c in range(len(users))]
     if a.brake_ladder_verdict:
         users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
         a_max = SY.VEHICLE_BMW320I[4]
