@@ -58,6 +58,9 @@
 //   fo_hidden_brake_ladder_verdict.hpp  fo_hr_brake_ladder_verdict_kernel  the ladder verdict: the ladder-users walk over the first B
 //                                            brake starts, reduced to the level the worst start needs and folded likewise
 //                                            (fo_hidden_ladder_verdict.hpp: the reduction and the fold as plain functions of values)
+//   fo_hidden_brake_harm_ladder.hpp  fo_hr_brake_harm_ladder_kernel  the harm ladder: the ladder verdict with "unclear" relaxed to "hit
+//                                            at a harm above the limit", and the greatest harm each level leaves
+//                                            (fo_hidden_harm_ladder.hpp: what is over and the curve as plain functions of values)
 // The host side of the hidden-traffic extensions -- the fo_scene_hidden_* entry points and their argument checks -- is a part too:
 // fo_scene_hidden.hpp, behind the kernel parts.
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
@@ -81,6 +84,7 @@
 #include "fo_hidden_brake_impact.hpp"
 #include "fo_hidden_brake_impact_lanes.hpp"
 #include "fo_hidden_brake_ladder_verdict.hpp"
+#include "fo_hidden_brake_harm_ladder.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
 #include "fo_future_visibility.hpp"

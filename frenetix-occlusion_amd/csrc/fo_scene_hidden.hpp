@@ -440,6 +440,74 @@ static int hidden_brake_impact_call(fo_ctx *ctx, const P *p, const char *fn, voi
   return FO_OK;
 }
 
+// The host part of the ladder verdict (fo_hidden_brake_ladder_verdict.hpp) and, HARM, of the harm ladder
+// (fo_hidden_brake_harm_ladder.hpp), which asks for the impact entry's speeds, rows and limit behind the ladder verdict's list and for
+// the curve's two outputs where that entry asks for its own: one launch; the levels, map_of and the table travel as kernel arguments.
+// Both structures name their shared members alike
+template <bool HARM, class P>
+static int hidden_brake_ladder_verdict_call(fo_ctx *ctx, const P *p, const char *fn, void *stream) {
+  int rc;
+  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
+  Scene *sc = (Scene *)ctx->scene;
+  if ((rc = hbu_check_head(ctx, *p, fn))) return rc;
+  if ((rc = hb_check_levels(ctx, p->L, p->h_levels, true, fn))) return rc;
+  if ((rc = hb_check_dt(ctx, p->dt, fn))) return rc;
+  if (!(p->a_limit >= 0.0))                                      // (NaN fails the comparison; +inf passes)
+    return fo_fail(ctx, FO_E_ARG, "%s: a_limit = %g, a deceleration >= 0 (or +inf) is needed", fn, p->a_limit);
+  if (p->M == 0) return FO_OK;
+  const int T = p->T, B = p->B, K = p->K, C = p->C, L = p->L;
+  if ((rc = hb_check_samples(ctx, T, fn))) return rc;
+  if ((rc = hb_check_starts(ctx, B, T, fn))) return rc;
+  if ((rc = hb_check_table_size(ctx, C, T, fn))) return rc;
+  if ((rc = hb_check_arg_bytes(ctx, C, T, L, fn))) return rc;
+  if ((rc = hbu_check_inputs(ctx, *p, fn))) return rc;
+  if constexpr (HARM) {
+    if (!p->d_need || !p->d_at || !p->d_blocking || !p->d_user || !p->d_decel || !p->d_need_of || !p->d_first || !p->d_harm_at || !p->d_user_at)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_need, d_at, d_blocking, d_user, d_decel [M], d_need_of and d_first [C][M], d_harm_at and d_user_at "
+                     "[M][L] are required with M > 0", fn);
+  } else {
+    if (!p->d_need || !p->d_at || !p->d_blocking || !p->d_user || !p->d_decel || !p->d_need_of || !p->d_first)
+      return fo_fail(ctx, FO_E_ARG, "%s: d_need, d_at, d_blocking, d_user, d_decel [M], d_need_of and d_first [C][M] are required with M > 0", fn);
+  }
+  if ((rc = hb_check_cost_pair(ctx, p->d_cost_or_null, p->d_safe_or_null, fn))) return rc;
+  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
+  if constexpr (HARM) {
+    if (!p->d_speed_of) return fo_fail(ctx, FO_E_ARG, "%s: d_speed_of [C] is required with M > 0", fn);
+    if (!p->d_harm_rows) return fo_fail(ctx, FO_E_ARG, "%s: d_harm_rows [C][4] is required with M > 0", fn);
+    if (!(p->harm_limit >= 0.0))                                 // (NaN fails the comparison; +inf passes)
+      return fo_fail(ctx, FO_E_ARG, "%s: harm_limit = %g, a harm >= 0 (or +inf) is needed", fn, p->harm_limit);
+  }
+  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const HbuMaps mp = hbu_maps(*p);
+  const HbluPack pk = hblu_pack(p->h_levels, L, p->h_thr, C * T);
+  const dim3 grid((unsigned)brake_ladder_verdict_blocks(p->M, T, K, L, B)), block(HB_THREADS);
+  hipStream_t s = (hipStream_t)stream;
+  if constexpr (HARM) {
+    const HrBrakeHarmLadderArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_verdict_group(L, B),
+                                  brake_ladder_verdict_per_block(T, K, L, B), p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw,
+                                  p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0,
+                                  p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2], mp.qmin[0], mp.qmin[1], mp.qmin[2],
+                                  mp.map_of, p->d_v, p->d_arc, p->dt, p->a_limit, p->d_speed_of, p->d_harm_rows, p->harm_limit,
+                                  p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null, p->d_need, p->d_at, p->d_blocking, p->d_user,
+                                  p->d_decel, p->d_need_of, p->d_first, p->d_harm_at, p->d_user_at};
+    const size_t lds = brake_harm_ladder_lds_bytes(T, K, C, L, B);
+    if (brake_users_width(C) == 4) hbhl_launch<4>(K, grid, block, lds, s, a, pk);
+    else hbhl_launch<8>(K, grid, block, lds, s, a, pk);
+  } else {
+    const HrBrakeLadderVerdictArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_verdict_group(L, B),
+                                     brake_ladder_verdict_per_block(T, K, L, B), p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw,
+                                     p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0,
+                                     p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2], mp.qmin[0], mp.qmin[1], mp.qmin[2],
+                                     mp.map_of, p->d_v, p->d_arc, p->dt, p->a_limit, p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null,
+                                     p->d_need, p->d_at, p->d_blocking, p->d_user, p->d_decel, p->d_need_of, p->d_first};
+    const size_t lds = brake_ladder_verdict_lds_bytes(T, K, C, L, B);
+    if (brake_users_width(C) == 4) hblv_launch<4>(K, grid, block, lds, s, a, pk);
+    else hblv_launch<8>(K, grid, block, lds, s, a, pk);
+  }
+  FO_HIP_TRY(ctx, hipGetLastError());
+  return FO_OK;
+}
+
 extern "C" {
 
 int fo_scene_hidden_reach(fo_ctx *ctx, const fo_hidden_reach_t *p, void *stream) {
@@ -761,46 +829,13 @@ int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_c
   return FO_OK;
 }
 
-// the ladder verdict of every trajectory over its first B brake starts against every class of road user on the key map it names --
-// the level the worst start needs, folded into the reserved cost columns and the safety flag: one launch
-// (fo_hidden_brake_ladder_verdict.hpp); the levels, map_of and the table travel as kernel arguments
+// the ladder verdict and the harm ladder: hidden_brake_ladder_verdict_call above
 int fo_scene_hidden_brake_ladder_verdict(fo_ctx *ctx, const fo_hidden_brake_ladder_verdict_t *p, void *stream) {
-  const char *fn = "fo_scene_hidden_brake_ladder_verdict";
-  int rc;
-  if ((rc = hr_check_scene(ctx, p, fn))) return rc;
-  Scene *sc = (Scene *)ctx->scene;
-  if ((rc = hbu_check_head(ctx, *p, fn))) return rc;
-  if ((rc = hb_check_levels(ctx, p->L, p->h_levels, true, fn))) return rc;
-  if ((rc = hb_check_dt(ctx, p->dt, fn))) return rc;
-  if (!(p->a_limit >= 0.0))                                      // (NaN fails the comparison; +inf passes)
-    return fo_fail(ctx, FO_E_ARG, "%s: a_limit = %g, a deceleration >= 0 (or +inf) is needed", fn, p->a_limit);
-  if (p->M == 0) return FO_OK;
-  const int T = p->T, B = p->B, K = p->K, C = p->C, L = p->L;
-  if ((rc = hb_check_samples(ctx, T, fn))) return rc;
-  if ((rc = hb_check_starts(ctx, B, T, fn))) return rc;
-  if ((rc = hb_check_table_size(ctx, C, T, fn))) return rc;
-  if ((rc = hb_check_arg_bytes(ctx, C, T, L, fn))) return rc;
-  if ((rc = hbu_check_inputs(ctx, *p, fn))) return rc;
-  if (!p->d_need || !p->d_at || !p->d_blocking || !p->d_user || !p->d_decel || !p->d_need_of || !p->d_first)
-    return fo_fail(ctx, FO_E_ARG, "%s: d_need, d_at, d_blocking, d_user, d_decel [M], d_need_of and d_first [C][M] are required with M > 0", fn);
-  if ((rc = hb_check_cost_pair(ctx, p->d_cost_or_null, p->d_safe_or_null, fn))) return rc;
-  if ((rc = hr_check_footprint(ctx, p->hl, p->hw, p->wb, fn))) return rc;
-  FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  const HbuMaps mp = hbu_maps(*p);
-  const HrBrakeLadderVerdictArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_verdict_group(L, B),
-                                   brake_ladder_verdict_per_block(T, K, L, B), p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw,
-                                   p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0,
-                                   p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2], mp.qmin[0], mp.qmin[1], mp.qmin[2],
-                                   mp.map_of, p->d_v, p->d_arc, p->dt, p->a_limit, p->d_finite_or_null, p->d_cost_or_null, p->d_safe_or_null,
-                                   p->d_need, p->d_at, p->d_blocking, p->d_user, p->d_decel, p->d_need_of, p->d_first};
-  const HbluPack pk = hblu_pack(p->h_levels, L, p->h_thr, C * T);
-  const dim3 grid((unsigned)brake_ladder_verdict_blocks(p->M, T, K, L, B)), block(HB_THREADS);
-  const size_t lds = brake_ladder_verdict_lds_bytes(T, K, C, L, B);
-  hipStream_t s = (hipStream_t)stream;
-  if (brake_users_width(C) == 4) hblv_launch<4>(K, grid, block, lds, s, a, pk);
-  else hblv_launch<8>(K, grid, block, lds, s, a, pk);
-  FO_HIP_TRY(ctx, hipGetLastError());
-  return FO_OK;
+  return hidden_brake_ladder_verdict_call<false>(ctx, p, "fo_scene_hidden_brake_ladder_verdict", stream);
+}
+
+int fo_scene_hidden_brake_harm_ladder(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_t *p, void *stream) {
+  return hidden_brake_ladder_verdict_call<true>(ctx, p, "fo_scene_hidden_brake_harm_ladder", stream);
 }
 
 }  // extern "C"

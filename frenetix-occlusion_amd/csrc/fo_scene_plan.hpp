@@ -194,6 +194,17 @@ inline size_t brake_ladder_verdict_lds_bound() {
   return (size_t)BRAKE_LADDER_ROWS_BYTES + BRAKE_LADDER_USERS_MAX_ARG_BYTES +
          (size_t)(BRAKE_LADDER_USERS_MAX_CLASSES + 1) * BRAKE_LADDER_VERDICT_WAVES * sizeof(int32_t);
 }
+// the harm ladder: the ladder verdict's lanes, grid and LDS; where a trajectory has more than a wave (G > 64) the curve's exchange
+// stands behind the ladder verdict's, aligned to 8 bytes: one float64 harm and one int32 class per lane of the workgroup.
+// brake_harm_ladder_lds_bound: no call needs more -- 39 568 bytes, under the 64 KB of a workgroup
+constexpr int BRAKE_HARM_LADDER_EXCHANGE_BYTES = HB_THREADS * (int)(sizeof(double) + sizeof(int32_t));
+inline size_t brake_harm_ladder_lds_bytes(int T, int K, int C, int L, int B) {
+  const size_t base = (brake_ladder_verdict_lds_bytes(T, K, C, L, B) + 7) / 8 * 8;
+  return base + (brake_ladder_verdict_group(L, B) > 64 ? (size_t)BRAKE_HARM_LADDER_EXCHANGE_BYTES : 0);
+}
+inline size_t brake_harm_ladder_lds_bound() {
+  return (brake_ladder_verdict_lds_bound() + 7) / 8 * 8 + (size_t)BRAKE_HARM_LADDER_EXCHANGE_BYTES;
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

@@ -56,7 +56,7 @@ EXPORTS = [
     "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
     "fo_scene_hidden_brake_ladder_users", "fo_scene_hidden_poses", "fo_scene_hidden_brake_verdict",
     "fo_scene_hidden_brake_ladder_verdict", "fo_scene_hidden_brake_impact", "fo_hidden_impact_row",
-    "fo_scene_hidden_brake_impact_lanes",
+    "fo_scene_hidden_brake_impact_lanes", "fo_scene_hidden_brake_harm_ladder",
 ]
 
 
@@ -225,7 +225,13 @@ class HiddenBrakeImpactLanes(C.Structure):      # fo_hidden_brake_impact_lanes_t
         ("dir_mask", C.c_uint32), ("cos_h", C.c_double), ("sin_h", C.c_double), ("d_cosine", C.c_void_p)]
 
 
-HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1   # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
+class HiddenBrakeHarmLadder(C.Structure):       # fo_hidden_brake_harm_ladder_t
+    _fields_ = HiddenBrakeLadderVerdict._fields_ + [
+        ("d_speed_of", C.c_void_p), ("d_harm_rows", C.c_void_p), ("harm_limit", C.c_double), ("d_harm_at", C.c_void_p),
+        ("d_user_at", C.c_void_p)]
+
+
+HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1  # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
 HIDDEN_CLEARANCE_METRIC = {"euclid": 0, "road": 1}   # FO_HIDDEN_CLEARANCE_EUCLID / _ROAD
 
 
@@ -344,6 +350,7 @@ def load():
     lib.fo_scene_hidden_brake_ladder_verdict.argtypes = [vp, C.POINTER(HiddenBrakeLadderVerdict), vp]
     lib.fo_scene_hidden_brake_impact.argtypes = [vp, C.POINTER(HiddenBrakeImpact), vp]
     lib.fo_scene_hidden_brake_impact_lanes.argtypes = [vp, C.POINTER(HiddenBrakeImpactLanes), vp]
+    lib.fo_scene_hidden_brake_harm_ladder.argtypes = [vp, C.POINTER(HiddenBrakeHarmLadder), vp]
     lib.fo_hidden_impact_row.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(HarmCoeff), C.POINTER(C.c_double)]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])

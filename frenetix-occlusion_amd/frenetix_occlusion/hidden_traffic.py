@@ -1372,6 +1372,37 @@ def _harm_limit(harm_limit, fn):
     return harm_limit
 
 
+def _impact_kinds(kinds, users, fn):
+    """``kinds`` as a tuple of ``(type_name, length, width)``, one per user, or its refusal"""
+    try:
+        kinds = tuple((str(k[0]), float(k[1]), float(k[2])) for k in kinds)
+    except (TypeError, ValueError, IndexError):
+        raise ValueError(f"{fn}: kinds must hold one (type_name, length, width) per user") from None
+    if len(kinds) != len(users):
+        raise ValueError(f"{fn}: {len(kinds)} kinds for {len(users)} users: one (type_name, length, width) per user")
+    return kinds
+
+
+def _impact_rows(self, users, kinds, ego_mass, coeff, fn):
+    """``(rows, speed_of, d_rows, d_speed_of)``: the harm rows of :func:`hidden_impact_rows` and the users' speeds, on the host and
+    on the model's device -- built once per distinct ``(users, kinds, ego_mass, coeff)`` and kept: after the first call nothing is
+    uploaded"""
+    from .metrics.metric import load_harm_coeff
+    coeff = load_harm_coeff() if coeff is None else dict(coeff)
+    try:
+        key = (tuple(s for s, _, _ in users), kinds, float(ego_mass), tuple(sorted((str(k), float(q)) for k, q in coeff.items())))
+    except (TypeError, ValueError):
+        raise ValueError(f"{fn}: ego_mass and the entries of coeff must be numbers") from None
+    cache = self.__dict__.setdefault("_hbi_rows", {})
+    if key not in cache:
+        rows = hidden_impact_rows(kinds, ego_mass, coeff, fn)
+        speed_of = np.array(key[0], dtype=np.float64)
+        if len(cache) >= 16:
+            cache.clear()
+        cache[key] = (rows, speed_of, N.on_device(rows, self.device), N.on_device(speed_of, self.device))
+    return cache[key]
+
+
 def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, a_brake, starts, harm_limit, coeff=None, cost=None,
                         safe=None, margin=None, inflate=0.0, lengths=None, poses=None, approach="head_on", heading_slack=0.0):
     """Hidden-traffic impact verdict (``fo_scene_hidden_brake_impact``; DESIGN.md §5.10 "Impact verdict"): for the hidden road
@@ -1409,27 +1440,9 @@ def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds
     dir_mask = sum(1 << c for c, u in enumerate(users) if u[2] == "lanes") if approach == "lanes" else 0
     if dir_mask and getattr(self, "lane_moves", None) is None:
         raise ValueError(f"{fn}: approach='lanes' with a lane-bound user needs the map's move table (lane_moves is None)")
-    try:
-        kinds = tuple((str(k[0]), float(k[1]), float(k[2])) for k in kinds)
-    except (TypeError, ValueError, IndexError):
-        raise ValueError(f"{fn}: kinds must hold one (type_name, length, width) per user") from None
-    if len(kinds) != len(users):
-        raise ValueError(f"{fn}: {len(kinds)} kinds for {len(users)} users: one (type_name, length, width) per user")
+    kinds = _impact_kinds(kinds, users, fn)
     harm_limit = _harm_limit(harm_limit, fn)
-    from .metrics.metric import load_harm_coeff
-    coeff = load_harm_coeff() if coeff is None else dict(coeff)
-    try:
-        key = (tuple(s for s, _, _ in users), kinds, float(ego_mass), tuple(sorted((str(k), float(q)) for k, q in coeff.items())))
-    except (TypeError, ValueError):
-        raise ValueError(f"{fn}: ego_mass and the entries of coeff must be numbers") from None
-    cache = self.__dict__.setdefault("_hbi_rows", {})
-    if key not in cache:
-        rows = hidden_impact_rows(kinds, ego_mass, coeff, fn)
-        speed_of = np.array(key[0], dtype=np.float64)
-        if len(cache) >= 16:
-            cache.clear()
-        cache[key] = (rows, speed_of, N.on_device(rows, self.device), N.on_device(speed_of, self.device))
-    rows, speed_of, d_rows, d_speed_of = cache[key]
+    rows, speed_of, d_rows, d_speed_of = _impact_rows(self, users, kinds, ego_mass, coeff, fn)
     if poses is None:
         poses = hidden_poses(self, x, y, theta, v, lengths)
     p = _users_call(self, fn, users, x, y, None, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
@@ -1461,3 +1474,127 @@ def hidden_brake_impact(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds
     self._hbi_args = args                                   # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
     return HiddenBrakeImpact(harm, user, speed, at, commit, first, rows, speed_of, kinds, harm_limit, poses, B, users, p.map_of, p.thr,
                              p.clearances, closing, cosine, approach, heading_slack)
+
+
+@dataclass
+class HiddenBrakeHarmLadder:
+    """what :meth:`SensorModel.hidden_brake_harm_ladder` returns (DESIGN.md §5.10 "Harm ladder"; device tensors): the seven tensors
+    of :class:`HiddenBrakeLadderVerdict` -- ``need``, ``at``, ``blocking``, ``user [M]`` int32, ``decel [M]`` float64, ``need_of``,
+    ``first [C, M]`` int32 -- with "unclear" read as "hit at an obstacle harm above ``harm_limit``": ``decel`` is the gentlest
+    deceleration of ``levels`` that keeps the harm of every hit within the limit from the WORST of the first ``starts`` brake starts,
+    ``+inf`` where no level does (``need == L``), 0.0 where nothing was asked; ``user`` the lowest user that keeps the worst start
+    from the next gentler level, -2 = the candidate has a non-finite pose and fails closed.  And the curve: ``harm_at [M, L]``
+    float64, the greatest obstacle harm (the reference's MAIS3+ probability, head-on and at the worst area of impact) that is left
+    at level ``l`` over the starts and users, 0.0 without a hit, 1.0 where the candidate fails closed; ``user_at [M, L]`` int32 the
+    lowest user that attains it, -1 = none, -2 = fails closed.  ``rows``, ``speed_of``, ``kinds``, ``harm_limit`` as in
+    :class:`HiddenBrakeImpact`; ``levels``, ``starts``, ``a_limit``, ``poses``, ``users``, ``map_of``, ``thr``, ``clearances`` as in
+    :class:`HiddenBrakeLadderVerdict`.
+
+    Not claimed: what the two siblings do not claim; every user is priced head-on (there is no ``approach="lanes"`` here); the
+    answer is only as fine as the ladder; harder braking is not always safer, so ``harm_at`` need not fall along ``l``."""
+    need: torch.Tensor
+    at: torch.Tensor
+    blocking: torch.Tensor
+    user: torch.Tensor
+    decel: torch.Tensor
+    need_of: torch.Tensor
+    first: torch.Tensor
+    harm_at: torch.Tensor
+    user_at: torch.Tensor
+    levels: np.ndarray
+    starts: int
+    harm_limit: float
+    a_limit: float
+    rows: np.ndarray
+    speed_of: np.ndarray
+    kinds: tuple = ()
+    users: tuple = ()
+    poses: Optional[HiddenPoses] = None
+    map_of: tuple = ()
+    thr: Optional[np.ndarray] = None
+    clearances: tuple = ()
+
+    def required_deceleration(self):
+        """``[M]`` float64 (m/s^2): ``decel`` -- what the cost row holds in its first reserved column"""
+        return self.decel
+
+    def brake_threat_number(self, a_max):
+        """``[M]`` float64: ``decel / a_max`` -- the reference's ``break_threat_number`` (metrics/be.py:56) against the hidden road
+        users, with "no collision" relaxed to "harm within ``harm_limit``".  Nothing is read back."""
+        return self.decel / float(a_max)
+
+    def critical_user(self):
+        """``[M]`` int64: the lowest user that keeps the worst brake start from the next gentler level, -1 = none, -2 where the
+        candidate has a non-finite pose.  Nothing is read back."""
+        return self.user.to(torch.int64)
+
+    def harm_curve(self):
+        """``(levels, harm_at, user_at)``: the ladder (host float64 ``[L]``) and what each of its levels leaves, ``[M, L]`` each"""
+        return self.levels, self.harm_at, self.user_at
+
+    def monotone(self):
+        """``[M]`` bool: ``harm_at`` never rises from a level to the next harder one -- where harder braking is never worse, and a
+        bisection over the deceleration would have been sound.  Nothing is read back."""
+        if self.harm_at.shape[1] < 2:
+            return torch.ones((self.harm_at.shape[0],), dtype=torch.bool, device=self.harm_at.device)
+        return (self.harm_at[:, 1:] <= self.harm_at[:, :-1]).all(dim=1)
+
+
+def hidden_brake_harm_ladder(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, levels=None, starts, harm_limit,
+                             a_limit=float("inf"), coeff=None, cost=None, safe=None, margin=None, inflate=0.0, lengths=None, poses=None):
+    """Hidden-traffic harm ladder (``fo_scene_hidden_brake_harm_ladder``; DESIGN.md §5.10 "Harm ladder"): for the hidden road
+    ``users`` of :meth:`hidden_brake_users`, of the ``kinds`` of :meth:`hidden_brake_impact`, and the ladder ``levels`` of
+    :meth:`hidden_brake_ladder_verdict` (None: 0.5, 1.0, ... up to ``a_limit``, which must then be finite), over the first ``starts``
+    brake starts alone, the gentlest deceleration of the ladder at which the obstacle harm of every hit that remains -- the
+    reference's MAIS3+ probability at the speed the ego of ``ego_mass`` kg has left where it is hit, head-on and at the worst area of
+    impact -- stays within ``harm_limit`` (``>= 0``, ``inf`` allowed) from the WORST of those starts; and per level the greatest
+    harm it leaves.  ``harm_limit = 0`` is the ladder verdict.  With ``cost [M, 16]`` float64 / ``safe [M]`` uint8 of a sweep or
+    planning step over the SAME candidates (both or neither) that deceleration and the blocking user go into the two reserved cost
+    columns, and ``safe = 0`` where no level suffices or the deceleration exceeds ``a_limit``.  The stage only ever takes safety
+    away.  It owns the same two columns as :meth:`hidden_brake_verdict`, :meth:`hidden_brake_ladder_verdict` and
+    :meth:`hidden_brake_impact`: fold one of the four into a row.
+
+    Everything runs on the device and on the current stream: the pose preparation (``poses=`` skips it), one ``hidden_clearance``
+    per distinct ``(metric, flow)``, and ONE launch for the walk, the harms, the reduction and the fold.  The harm rows are the
+    impact verdict's, built once and kept on the device.  Nothing is read back and nobody waits; returns a
+    :class:`HiddenBrakeHarmLadder`."""
+    fn = "hidden_brake_harm_ladder"
+    users = _road_users(users, x, fn)
+    try:
+        a_limit = float(a_limit)
+    except (TypeError, ValueError):
+        a_limit = float("nan")
+    if not a_limit >= 0.0:
+        raise ValueError(f"{fn}: a_limit >= 0 (inf is possible, nan is not)")
+    if levels is None:
+        if not math.isfinite(a_limit):
+            raise ValueError(f"{fn}: the default levels run up to a_limit, which is not finite: hand levels over")
+        levels = default_brake_ladder(a_limit, fn)
+    levels = _ladder_levels(levels, fn)
+    _arg_bytes(users, x, levels, "levels", fn)
+    kinds = _impact_kinds(kinds, users, fn)
+    harm_limit = _harm_limit(harm_limit, fn)
+    rows, speed_of, d_rows, d_speed_of = _impact_rows(self, users, kinds, ego_mass, coeff, fn)
+    if poses is None:
+        poses = hidden_poses(self, x, y, theta, v, lengths)
+    p = _users_call(self, fn, users, x, y, None, v, vehicle=vehicle, dt=dt, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+    B = _ladder_starts(starts, p.T, fn)
+    dev, M, C_, L_ = self.device, p.M, len(users), len(levels)
+    _cost_safe(cost, safe, M, p.x.device, fn)
+    tv = N.on_device(v, dev)
+    new = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    need, at, blocking, user, need_of, first, user_at = new(M), new(M), new(M), new(M), new(C_, M), new(C_, M), new(M, L_)
+    decel = torch.empty((M,), dtype=torch.float64, device=dev)
+    harm_at = torch.empty((M, L_), dtype=torch.float64, device=dev)
+    args = N.HiddenBrakeHarmLadder(**p.fields(tv, poses.arc, dt), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B,
+                                   a_limit=a_limit, d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost),
+                                   d_safe_or_null=N.ptr(safe), d_need=N.ptr(need), d_at=N.ptr(at), d_blocking=N.ptr(blocking),
+                                   d_user=N.ptr(user), d_decel=N.ptr(decel), d_need_of=N.ptr(need_of), d_first=N.ptr(first),
+                                   d_speed_of=N.ptr(d_speed_of), d_harm_rows=N.ptr(d_rows), harm_limit=harm_limit,
+                                   d_harm_at=N.ptr(harm_at), d_user_at=N.ptr(user_at))
+    self.ctx.call("fo_scene_hidden_brake_harm_ladder", C.byref(args), N.current_stream(self._dev_index))
+    # (stay referenced until the next call, as in hidden_brake_users)
+    self._hbhl_inputs = (tv, poses, p.clearances, cost, safe)
+    self._hbhl_args = args                                  # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
+    return HiddenBrakeHarmLadder(need, at, blocking, user, decel, need_of, first, harm_at, user_at, levels, B, harm_limit, a_limit, rows,
+                                 speed_of, kinds, users, poses, p.map_of, p.thr, p.clearances)

@@ -581,18 +581,8 @@ class FOInterface:
         if self.timestep is None or self.sensor_model.window is None:
             raise RuntimeError("hidden_brake_impact needs a previous evaluate_scenario")
         users = tuple(users)
-        if kinds is None:
-            if len(users) != 3:
-                raise ValueError("hidden_brake_impact: kinds is required unless exactly three users are given "
-                                 "(then: Pedestrian, Bicycle, Car by ascending speed)")
-            order = sorted(range(3), key=lambda c: float(users[c][0]))
-            kinds = [None] * 3
-            for name, c in zip(("Pedestrian", "Bicycle", "Car"), order):
-                kinds[c] = name
-        kinds = [self.phantom_kind(k) if isinstance(k, str) else tuple(k) for k in kinds]
-        if harm_limit is None:
-            harm_limit = ((self.config.get("metrics") or {}).get("metric_thresholds") or {}).get("harm")
-            harm_limit = float("inf") if harm_limit is None else harm_limit
+        kinds = self._hidden_kinds(users, kinds, "hidden_brake_impact")
+        harm_limit = self._hidden_harm_limit(harm_limit)
         arr = trajectories_to_arrays(trajectories)
         om = self.occlusion_memory
         vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
@@ -601,6 +591,57 @@ class FOInterface:
                                                      dt=self.dt, a_brake=vt[4] if a_brake is None else a_brake, starts=starts,
                                                      harm_limit=harm_limit, cost=cost, safe=safe, inflate=inflate, approach=approach,
                                                      heading_slack=heading_slack)
+
+    def _hidden_kinds(self, users, kinds, fn):
+        """the ``kinds`` of ``fn`` (hidden_brake_impact, hidden_brake_harm_ladder) as ``(type_name, length, width)`` per user: a name
+        alone takes the phantom's dimensions; None: Pedestrian, Bicycle, Car by ascending speed, with exactly three users"""
+        if kinds is None:
+            if len(users) != 3:
+                raise ValueError(f"{fn}: kinds is required unless exactly three users are given "
+                                 "(then: Pedestrian, Bicycle, Car by ascending speed)")
+            order = sorted(range(3), key=lambda c: float(users[c][0]))
+            kinds = [None] * 3
+            for name, c in zip(("Pedestrian", "Bicycle", "Car"), order):
+                kinds[c] = name
+        return [self.phantom_kind(k) if isinstance(k, str) else tuple(k) for k in kinds]
+
+    def _hidden_harm_limit(self, harm_limit):
+        """``harm_limit``, None: the configuration's ``metric_thresholds.harm`` (``null`` there: inf)"""
+        if harm_limit is None:
+            harm_limit = ((self.config.get("metrics") or {}).get("metric_thresholds") or {}).get("harm")
+            harm_limit = float("inf") if harm_limit is None else harm_limit
+        return harm_limit
+
+    def hidden_brake_harm_ladder(self, trajectories, users, kinds=None, harm_limit=None, levels=None, starts=None, a_limit=None, cost=None,
+                                 safe=None, margin=None, inflate=0.0):
+        """EXTENSION, not part of the reference: the HARM LADDER against the hidden road users of :meth:`hidden_brake_users` -- the
+        gentlest deceleration of the ladder ``levels`` (None: 0.5, 1.0, ... up to the vehicle's ``a_max``) at which the harm of what
+        still hits each candidate stays within ``harm_limit`` (None: the configuration's ``metric_thresholds.harm``; ``null`` there:
+        inf) from the WORST of its first ``starts`` brake starts (None: all), and per level the greatest harm it leaves
+        (:meth:`SensorModel.hidden_brake_harm_ladder`; returns its :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeHarmLadder`:
+        the tensors of :meth:`hidden_brake_ladder_verdict`, ``harm_at``, ``user_at [M, L]``; ``.required_deceleration()``,
+        ``.brake_threat_number(a_max)``, ``.critical_user()``, ``.harm_curve()``, ``.monotone()``).  ``kinds`` as for
+        :meth:`hidden_brake_impact`.  With ``cost [M, 16]`` / ``safe [M]`` of a sweep over the same candidates the deceleration and
+        the user are folded into the two reserved columns, and candidates that need more than ``a_limit`` (None: the vehicle's
+        ``a_max``) or more than the ladder holds lose their safety flag.  Every user is priced head-on.  The other defaults as for
+        :meth:`hidden_brake_users`."""
+        from .metrics.metric import trajectories_to_arrays
+        from .sweep import _vehicle_tuple
+        if self.timestep is None or self.sensor_model.window is None:
+            raise RuntimeError("hidden_brake_harm_ladder needs a previous evaluate_scenario")
+        users = tuple(users)
+        kinds = self._hidden_kinds(users, kinds, "hidden_brake_harm_ladder")
+        harm_limit = self._hidden_harm_limit(harm_limit)
+        vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
+        if levels is None:
+            levels = _default_brake_ladder(vt[4], "hidden_brake_harm_ladder")
+        arr = trajectories_to_arrays(trajectories)
+        om = self.occlusion_memory
+        return self.sensor_model.hidden_brake_harm_ladder(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], ego_mass=vt[3],
+                                                          users=users, kinds=kinds, margin=om["margin"] if margin is None else margin,
+                                                          dt=self.dt, levels=levels, starts=starts, harm_limit=harm_limit,
+                                                          a_limit=vt[4] if a_limit is None else a_limit, cost=cost, safe=safe,
+                                                          inflate=inflate)
 
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the

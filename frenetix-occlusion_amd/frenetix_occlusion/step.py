@@ -19,6 +19,7 @@ from .sweep import SweepResult
 
 _LADDER_KEYS = ("vehicle", "users", "dt", "levels", "starts", "a_limit")
 _IMPACT_KEYS = ("vehicle", "ego_mass", "users", "kinds", "dt", "a_brake", "starts", "harm_limit")
+_HARM_LADDER_KEYS = ("vehicle", "ego_mass", "users", "kinds", "dt", "starts", "harm_limit")
 
 
 def _stage_options(name, given, required, optional):
@@ -37,16 +38,26 @@ def _stage_options(name, given, required, optional):
     return opts
 
 
+def hidden_stages(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, hidden_harm_ladder_verdict):
+    """``(ladder, impact, harm_ladder)``: the ``hidden_ladder_verdict=``, ``hidden_impact_verdict=`` and
+    ``hidden_harm_ladder_verdict=`` of :class:`PlanningStep` as dicts of their own, or the refusal of the four stages together --
+    they own the same two reserved cost columns, so a step runs one of them; None stays None"""
+    given = [n for n, q in (("hidden_verdict", hidden_verdict), ("hidden_ladder_verdict", hidden_ladder_verdict),
+                            ("hidden_impact_verdict", hidden_impact_verdict),
+                            ("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict)) if q is not None]
+    if len(given) > 1:
+        raise ValueError(f"PlanningStep: {' and '.join(given)} own the same two reserved cost columns: a step runs one of them")
+    return (_stage_options("hidden_ladder_verdict", hidden_ladder_verdict, _LADDER_KEYS, ("margin", "inflate", "lengths")),
+            _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths", "approach", "heading_slack")),
+            _stage_options("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict, _HARM_LADDER_KEYS,
+                           ("levels", "a_limit", "coeff", "margin", "inflate", "lengths")))
+
+
 def hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict):
     """``(ladder, impact)``: the ``hidden_ladder_verdict=`` and ``hidden_impact_verdict=`` of :class:`PlanningStep` as dicts of their
     own, or the refusal of the three stages together -- they own the same two reserved cost columns, so a step runs one of them;
     None stays None"""
-    given = [n for n, q in (("hidden_verdict", hidden_verdict), ("hidden_ladder_verdict", hidden_ladder_verdict),
-                            ("hidden_impact_verdict", hidden_impact_verdict)) if q is not None]
-    if len(given) > 1:
-        raise ValueError(f"PlanningStep: {' and '.join(given)} own the same two reserved cost columns: a step runs one of them")
-    return (_stage_options("hidden_ladder_verdict", hidden_ladder_verdict, _LADDER_KEYS, ("margin", "inflate", "lengths")),
-            _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths", "approach", "heading_slack")))
+    return hidden_stages(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, None)[:2]
 
 
 def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict=None):
@@ -56,7 +67,8 @@ def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict, hidden_
 
 class PlanningStep:
     def __init__(self, sensor_model, spawn_locator, sweep, x, y, theta, v, a=None, mode="reduced", lists="f64", shard=None,
-                 mirror=False, hidden_verdict=None, hidden_ladder_verdict=None, hidden_impact_verdict=None):
+                 mirror=False, hidden_verdict=None, hidden_ladder_verdict=None, hidden_impact_verdict=None,
+                 hidden_harm_ladder_verdict=None):
         """``hidden_verdict`` (an extension, DESIGN.md §5.10 "Fail-safe verdict"): a dict of the keyword arguments of
         :meth:`SensorModel.hidden_brake_verdict` -- ``vehicle``, ``users``, ``dt``, ``a_brake``, ``starts``, ``commit_min`` and
         optionally ``margin``, ``inflate``, ``lengths`` -- :meth:`run` then queues the pose preparation, the clearances and the
@@ -78,6 +90,13 @@ class PlanningStep:
         columns: giving two of the three stages is a ValueError.  None: nothing is queued or allocated for it, and ``out`` has no
         such attribute.
 
+        ``hidden_harm_ladder_verdict`` (an extension, DESIGN.md §5.10 "Harm ladder"): a dict of the keyword arguments of
+        :meth:`SensorModel.hidden_brake_harm_ladder` -- ``vehicle``, ``ego_mass``, ``users``, ``kinds``, ``dt``, ``starts``,
+        ``harm_limit`` and optionally ``levels``, ``a_limit``, ``coeff``, ``margin``, ``inflate``, ``lengths`` -- queued where the other
+        three stages are; ``out.hidden_harm_ladder_verdict`` is its
+        :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeHarmLadder`.  It owns the same two columns: giving two of the four
+        stages is a ValueError.  None: nothing is queued or allocated for it, and ``out`` has no such attribute.
+
         ``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
         :class:`~frenetix_occlusion.distributed.CostGather` for the batch size -- this rank's step covers its contiguous
         block of the candidates (scene stage and phantoms replicated), writes the block's cost rows into the collective's
@@ -91,7 +110,8 @@ class PlanningStep:
             raise ValueError("PlanningStep: the three stages must share one context (one ego, one GPU)")
         if mode not in ("reduced", "pair", "full"):
             raise ValueError(f"unknown output mode '{mode}'")
-        ladder, impact = hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict)    # (refused before anything is allocated)
+        ladder, impact, harm_ladder = hidden_stages(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict,
+                                                    hidden_harm_ladder_verdict)     # (refused before anything is allocated)
         self.sm, self.sl, self.sw = sensor_model, spawn_locator, sweep
         self.ctx = sweep.ctx
         self.mode, self.lists, self.mirror = mode, lists, bool(mirror)
@@ -148,6 +168,9 @@ class PlanningStep:
         self._hidden_impact_verdict = impact
         if impact is not None and self.gather is not None and impact.get("lengths") is not None:
             impact["lengths"] = impact["lengths"][self.gather.lo:self.gather.hi]
+        self._hidden_harm_ladder_verdict = harm_ladder
+        if harm_ladder is not None and self.gather is not None and harm_ladder.get("lengths") is not None:
+            harm_ladder["lengths"] = harm_ladder["lengths"][self.gather.lo:self.gather.hi]
 
     def _fill(self, w, O):
         """everything that does not change from step to step"""
@@ -259,6 +282,11 @@ class PlanningStep:
             tx, ty, tth, tv = self.traj[:4]
             self.out.hidden_impact_verdict = sm.hidden_brake_impact(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
                                                                     **self._hidden_impact_verdict)
+        if self._hidden_harm_ladder_verdict is not None:
+            # the same place: one of the four stages owns the two columns
+            tx, ty, tth, tv = self.traj[:4]
+            self.out.hidden_harm_ladder_verdict = sm.hidden_brake_harm_ladder(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
+                                                                              **self._hidden_harm_ladder_verdict)
         if self.gather is not None:
             # the one collective of the path, queued behind the step
             self.out.cost_all = self.gather.gather(None if self._direct or self.M == 0 else self.out.cost)

@@ -1153,6 +1153,82 @@ int fo_scene_hidden_brake_impact_lanes(fo_ctx *ctx, const fo_hidden_brake_impact
  * outside the FO_TYPE_* codes), size or ego_mass not positive and finite. */
 int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_coeff_t *hc, double *row);
 
+/* EXTENSION, not part of the reference: hidden-traffic HARM LADDER (DESIGN.md §5.10 "Harm ladder") -- "how hard must the ego be
+ * prepared to brake, from the worst of the brake starts it executes before it replans, so that the harm of what still hits it stays
+ * within harm_limit?": the reference's brake threat number (metrics/be.py:56) against hidden road users with "no collision" relaxed
+ * to "harm within the threshold" (metrics/metric.py:63-68).  It lies between the two stages above: finite where the ladder verdict
+ * says "no level", graded over the decelerations where the impact verdict prices one.  The walk of
+ * fo_scene_hidden_brake_ladder_verdict; every hit is priced on the spot as fo_scene_hidden_brake_impact prices it.  Opt-in and
+ * additive: one launch on the caller's stream, behind the step whose cost rows it folds into; nothing is read back.  It writes the
+ * SAME two reserved columns as the three stages above: a step runs one of the four.
+ *  Inputs: those of fo_scene_hidden_brake_ladder_verdict word for word -- h_levels [L] strictly ascending, B, a_limit,
+ *   d_finite_or_null, d_cost_or_null / d_safe_or_null both or neither -- and, from fo_scene_hidden_brake_impact: d_speed_of [C],
+ *   d_harm_rows [C][4] (device buffers, float64) and harm_limit, float64, >= 0, +inf allowed, not NaN.
+ *  Write bf, st and fm for what fo_scene_hidden_brake_ladder_users writes on the same inputs as brake_first[c][m][b][l],
+ *   stop[m][b][l] and first[c][m], v for d_v, and ends = min(B, Lm).
+ *  1. Hit: brake start b < ends at level l is HIT by class c iff (0 <= fm <= b) or (0 <= bf < st), the family's commit rule.
+ *  2. The ego speed at the hit: u = v[m][fm] where 0 <= fm <= b, else max(v[m][b] - levels[l] * ((bf - b) * dt), 0): step 2 of
+ *   fo_scene_hidden_brake_impact at a_brake = levels[l].
+ *  3. The harm at the hit: ho(c, m, b, l) = 1 / (1 + exp(rows[c][0] + rows[c][1] * (u + speed_of[c]))): head-on, float64, plain exp,
+ *   no contraction.
+ *  4. over(c, m, b, l) = hit and ho > harm_limit.  A NaN never counts as over.
+ *  5. The ladder reduction: steps 1 - 7 of fo_scene_hidden_brake_ladder_verdict with `over` in the place of "unclear" -- ra, blk and
+ *   req are formed from `over` by the rules fo_scene_hidden_brake_ladder_users forms required_all, blocking and required by; need, at,
+ *   blocking, user, decel, need_of, first (the walk's, unchanged), the fail-closed row of a non-finite candidate and the fold
+ *   (cost[m][FO_C_RES0] = decel[m], cost[m][FO_C_RES1] = (double)user[m]; safety is lost where need[m] == L or decel[m] > a_limit)
+ *   are that entry's with their meanings unchanged.
+ *  6. The curve: harm_at[m][l] (float64) = the greatest ho(c, m, b, l) over the hit (c, b < ends), compared by > from -1.0, which is
+ *   below every harm (a NaN never wins); user_at[m][l] (int32) = the lowest class that attains it; 0.0 and -1 without a hit (or
+ *   none whose harm compares).  finite[m] == 0: harm_at[m][l] = 1.0 and user_at[m][l] = FO_HIDDEN_VERDICT_NOT_FINITE at every level.
+ *  Consequences: harm_limit = 0.0 gives fo_scene_hidden_brake_ladder_verdict bit for bit on the shared outputs (every logistic is
+ *   positive); harm_limit = +inf gives need = 0 wherever ends > 0; harm_at[m][l] <= harm_limit implies need[m] <= l, and need[m] == L
+ *   implies harm_at[m][l] > harm_limit at every l; need never rises with harm_limit and never exceeds the ladder verdict's;
+ *   harm_at[:, l] is the obstacle harm of fo_scene_hidden_brake_impact at a_brake = levels[l].
+ *  Outputs, every byte written by every call: d_need, d_at, d_blocking, d_user [M] int32; d_decel [M] float64; d_need_of, d_first
+ *   [C][M] int32; d_harm_at [M][L] float64; d_user_at [M][L] int32.
+ *  Safety of the data: as fo_scene_hidden_brake_ladder_users; finite, speed_of and the rows may hold anything, no index depends on
+ *   them.
+ *  Not claimed: what the ladder verdict and the impact verdict do not claim; every user is priced HEAD-ON and at the worst area of
+ *   impact (the approach angle of fo_scene_hidden_brake_impact_lanes is not taken); harder braking is not always safer against an
+ *   arrival map, so harm_at need not fall with l -- need is the first sufficient level of every start, not the last insufficient one.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_harm_ladder:"): those of fo_scene_hidden_brake_ladder_verdict in its order (a missing output includes
+ * d_harm_at and d_user_at), then, with M > 0: no d_speed_of; no d_harm_rows; harm_limit negative or NaN.  FO_E_STATE: no scene. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;                        /* as handed to the clearances */
+  int32_t win_ix0, win_iy0, win_nx, win_ny; /* the clearances' window */
+  int32_t K;                                /* maps */
+  int32_t C;                                /* classes */
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];   /* [win_ny][win_nx] each: the clearances' key maps (INPUT) */
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];  /* [M][T] each: the clearances' minimum per pose (INPUT) */
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];         /* the clearances' caps */
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];      /* the map of class c, in [0, K) */
+  const double *d_v;                        /* [M][T] speed at each sample, m/s */
+  const double *d_arc;                      /* [M][T] travelled chord length, m */
+  const double *h_levels;                   /* HOST [L] decelerations, m/s^2, strictly ascending */
+  int32_t L;                                /* levels */
+  int32_t B;                                /* brake starts b = 0 .. B-1 */
+  double dt;
+  const int32_t *h_thr;                     /* HOST [C][T]: 169 * R2_c[j] */
+  double a_limit;                           /* decel above it takes safety away; +inf: only "no level" does */
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC] of the step: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  int32_t *d_need, *d_at, *d_blocking, *d_user;     /* [M] */
+  double *d_decel;                          /* [M] */
+  int32_t *d_need_of, *d_first;             /* [C][M] */
+  const double *d_speed_of;                 /* [C] speed of class c, m/s */
+  const double *d_harm_rows;                /* [C][4] (p0, p1, p2, p3); p0 and p1 are read */
+  double harm_limit;                        /* a hit at a harm above it counts; 0: every hit does, +inf: none */
+  double *d_harm_at;                        /* [M][L] the greatest harm level l leaves */
+  int32_t *d_user_at;                       /* [M][L] the lowest class that attains it */
+} fo_hidden_brake_harm_ladder_t;
+int fo_scene_hidden_brake_harm_ladder(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_t *p, void *stream);
+
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least
  * min_ahead ahead of the ego and within max_dist, on the visible/occluded frontier (all_occluded = 0) or anywhere in

@@ -6,6 +6,7 @@ follows and the 720-ray first-seen future-visibility call on the same batch.
                                        [--flow any|lanes] [--clearance] [--witness] [--brake [A]]
                                        [--brake-classes v1,v2,...] [--brake-users v:metric:flow,...] [--brake-ladder K]
                                        [--brake-ladder-users] [--brake-verdict B] [--brake-ladder-verdict B]
+                                       [--brake-impact B] [--brake-harm-ladder B [--harm-limit H]]
 
 ``--flow lanes`` (with ``--metric road``): the reach follows the driving direction of the lanes (§5.10 "Lane flow").
 
@@ -67,6 +68,14 @@ B: the whole call, the call with the poses handed over, and the ONE launch of ei
 entry again).  In every run the tie is asserted: ``commit`` and ``first`` are the verdict's, ``speed`` (bit for bit) and ``at`` are steps
 1 - 3 of the definition on ``hidden_brake_users``' ``brake_first`` / ``stop`` / ``first``.  Also the distribution of the obstacle's harm
 over the candidates and how many distinct values it takes.
+
+``--brake-harm-ladder B``: ``hidden_brake_harm_ladder`` for the same road users and kinds at the default ladder 0.5, 1.0, ... 11.5 over the
+first B brake starts, at ``--harm-limit`` (§5.10 "Harm ladder") -- the whole call, the call with the poses handed over and the ONE launch
+alone, next to the launch of ``hidden_brake_ladder_verdict`` in the same process (one profiler trace holds both kernels) and to the 23
+``hidden_brake_impact`` calls it replaces.  In every run three consequences of the definition are asserted: at ``harm_limit = 0`` the
+shared outputs are the ladder verdict's bit for bit; a level whose ``harm_at`` is within the limit suffices and "no level" means every
+level is over it; ``harm_at[:, l]`` is the impact verdict's obstacle harm at ``a_brake = levels[l]`` to 1e-9.  Also the distribution of
+``need`` and ``decel`` and where ``harm_at`` rises with harder braking.
 
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
@@ -131,6 +140,11 @@ def main():
                          "and to hidden_brake_verdict at one level")
     ap.add_argument("--brake-impact", type=int, default=None, metavar="B",
                     help="time hidden_brake_impact over the first B brake starts next to hidden_brake_verdict")
+    ap.add_argument("--brake-harm-ladder", type=int, default=None, metavar="B",
+                    help="time hidden_brake_harm_ladder over the first B brake starts next to hidden_brake_ladder_verdict and to one "
+                         "hidden_brake_impact call per level")
+    ap.add_argument("--harm-limit", type=float, default=0.1,
+                    help="with --brake-harm-ladder: harm_limit (default: metric_thresholds.harm of the reference's example configuration)")
     ap.add_argument("--approach", default="head_on", choices=("head_on", "lanes"),
                     help="with --brake-impact: lanes also times approach='lanes' and records what it does to the grading")
     ap.add_argument("--heading-slack", type=float, default=0.0, help="with --approach lanes: heading_slack in radians")
@@ -449,6 +463,86 @@ def main():
         res["candidates_by_ladder_user"] = {str(c): int((v_out.user == c).sum()) for c in range(-2, len(users))}
         res["candidates_above_a_limit"] = int((v_out.decel > a_max).sum())
         res["candidates_by_at"] = {str(k): int((v_out.at == k).sum()) for k in range(-1, B)}
+    if a.brake_harm_ladder:
+        users = ((2.0, "road", "any"), (7.0, "road", "lanes"), (13.9, "road", "lanes"))
+        kinds = (("Pedestrian", 0.3 * 1.2, 0.5 * 1.3), ("Bicycle", 2.0 * 1.4, 0.9 * 2.5), ("Car", 4.8 * 1.2, 2.0 * 1.3))   # length, width x size factors
+        a_max, mass = SY.VEHICLE_BMW320I[4], SY.VEHICLE_BMW320I[3]
+        B = a.brake_harm_ladder
+        if not 1 <= B <= T:
+            ap.error(f"--brake-harm-ladder B: 1 <= B <= {T}")
+        levels = np.array(default_brake_ladder(a_max, "hidden_brake_harm_ladder"))
+        L = len(levels)
+        tv = torch.as_tensor(traj["v"]).to(dev)
+        hbhl = lambda limit=a.harm_limit, **kw: sm.hidden_brake_harm_ladder(tx, ty, tth, tv, vehicle=veh, ego_mass=mass, users=users, kinds=kinds,
+                                                                          dt=0.1, levels=levels, starts=B, harm_limit=limit, a_limit=a_max, **kw)
+        hblv = lambda **kw: sm.hidden_brake_ladder_verdict(tx, ty, tth, tv, vehicle=veh, users=users, dt=0.1, levels=levels, starts=B,
+                                                           a_limit=a_max, **kw)
+        hbi = lambda a_brake, **kw: sm.hidden_brake_impact(tx, ty, tth, tv, vehicle=veh, ego_mass=mass, users=users, kinds=kinds, dt=0.1,
+                                                           a_brake=a_brake, starts=B, harm_limit=math.inf, **kw)
+        shared = ("need", "at", "blocking", "user", "decel", "need_of", "first")
+        h_out = hbhl()
+        poses = h_out.poses
+        v_out = hblv(poses=poses)
+        # (a), in every run: at harm_limit = 0 every hit counts -- the ladder verdict bit for bit
+        zero = hbhl(0.0, poses=poses)
+        for name in shared:
+            got, want = getattr(zero, name), getattr(v_out, name)
+            assert torch.equal(got.view(torch.int64) if got.dtype == torch.float64 else got, want.view(torch.int64) if want.dtype == torch.float64 else want), name
+        assert torch.equal(zero.harm_at, h_out.harm_at) and torch.equal(zero.user_at, h_out.user_at)      # the curve does not depend on the limit
+        # (c), in every run: a level whose harm is within the limit suffices, and "no level" means every level is over it
+        below = h_out.harm_at <= a.harm_limit
+        lowest = torch.where(below.any(dim=1), below.to(torch.int8).argmax(dim=1), L)
+        asked = h_out.need >= 0
+        assert bool((h_out.need[asked] <= lowest[asked]).all()) and bool((h_out.harm_at[h_out.need == L] > a.harm_limit).all())
+        assert bool((h_out.need <= v_out.need).all())
+        # (e), in every run: level l of the curve is the impact verdict at a_brake = levels[l]
+        worst, other_user = 0.0, 0
+        for l, level in enumerate(levels):
+            i_out = hbi(float(level), poses=poses)
+            worst = max(worst, float((h_out.harm_at[:, l] - i_out.harm[:, 0]).abs().max()))
+            other_user += int((h_out.user_at[:, l] != i_out.user).sum())
+        assert worst <= 1e-9, worst
+        res["brake_harm_ladder_worst_difference_to_impact"] = worst
+        res["brake_harm_ladder_users_differing_from_impact"] = other_user
+        # the launches alone, both in this process so that one profiler trace holds both kernels: a call that folds into a scratch cost /
+        # safe pair, then the structure it left handed to the C entry again
+        scratch = (torch.zeros((M, N.NC), dtype=torch.float64, device=dev), torch.ones((M,), dtype=torch.uint8, device=dev))
+        keep_v = hblv(poses=poses, cost=scratch[0], safe=scratch[1])
+        launch_v = (C.byref(sm._hblv_args), N.current_stream(sm._dev_index))
+        res["brake_ladder_verdict_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_ladder_verdict", *launch_v), a.calls)
+        keep_h = hbhl(poses=poses, cost=scratch[0], safe=scratch[1])
+        launch_h = (C.byref(sm._hbhl_args), N.current_stream(sm._dev_index))
+        res["brake_harm_ladder_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_harm_ladder", *launch_h), a.calls)
+        res["brake_ladder_verdict_launch_again_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_ladder_verdict", *launch_v), a.calls)
+        assert torch.equal(keep_h.harm_at, h_out.harm_at) and torch.equal(keep_v.need, v_out.need)
+        sm.ctx.call("fo_scene_hidden_brake_harm_ladder", *launch_h)
+        torch.cuda.synchronize()
+        assert torch.equal(scratch[0][:, 14].view(torch.int64), h_out.decel.view(torch.int64))
+        res["brake_harm_ladder_users"] = [list(u) for u in users]
+        res["brake_harm_ladder_kinds"] = [list(k) for k in kinds]
+        res["brake_harm_ladder_levels"] = [float(v) for v in levels]
+        res["brake_harm_ladder_B"] = B
+        res["brake_harm_ladder_harm_limit"] = a.harm_limit
+        res["brake_harm_ladder_call_ms"] = _median_ms(hbhl, a.calls)
+        res["brake_harm_ladder_call_reused_poses_ms"] = _median_ms(lambda: hbhl(poses=poses), a.calls)
+        res["brake_ladder_verdict_call_reused_poses_ms"] = _median_ms(lambda: hblv(poses=poses), a.calls)
+
+        def impact_per_level():
+            for level in levels:
+                hbi(float(level), poses=poses)
+        res["brake_impact_calls_per_level_reused_poses_ms"] = _median_ms(impact_per_level, max(a.calls // 5, 3))
+        decel = h_out.decel.cpu().numpy()
+        res["decel_distinct_values"] = int(len(np.unique(decel)))
+        res["candidates_by_need"] = {str(k): int((h_out.need == k).sum()) for k in range(-1, L + 1)}
+        res["candidates_no_level"] = int((h_out.need == L).sum())
+        res["candidates_by_need_ladder_verdict"] = {str(k): int((v_out.need == k).sum()) for k in range(-1, L + 1)}
+        res["candidates_by_harm_ladder_user"] = {str(c): int((h_out.user == c).sum()) for c in range(-2, len(users))}
+        mono = h_out.monotone()
+        res["candidates_not_monotone"] = int((~mono).sum())
+        rises = (h_out.harm_at[:, 1:] > h_out.harm_at[:, :-1]).sum(dim=0).cpu().numpy()
+        res["candidates_rising_into_level"] = {str(l + 1): int(n) for l, n in enumerate(rises) if n}
+        ha = h_out.harm_at.cpu().numpy()
+        res["harm_at_quantiles_by_level"] = {str(l): [float(np.quantile(ha[:, l], q)) for q in (0.0, 0.5, 1.0)] for l in (0, L // 2, L - 1)}
     if a.brake_ladder:
         a_top = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
         levels = np.linspace(0.5, a_top, a.brake_ladder) if a.brake_ladder > 1 else np.array([a_top])
