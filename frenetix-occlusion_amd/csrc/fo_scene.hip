@@ -61,6 +61,8 @@
 //   fo_hidden_brake_harm_ladder.hpp  fo_hr_brake_harm_ladder_kernel  the harm ladder: the ladder verdict with "unclear" relaxed to "hit
 //                                            at a harm above the limit", and the greatest harm each level leaves
 //                                            (fo_hidden_harm_ladder.hpp: what is over and the curve as plain functions of values)
+//   fo_hidden_brake_harm_ladder_lanes.hpp  fo_hr_brake_harm_ladder_lanes_kernel  the harm ladder by approach angle: every hit of a
+//                                            lane-bound class priced in the walk's hit hook at the cosine the move table allows
 // The host side of the hidden-traffic extensions -- the fo_scene_hidden_* entry points and their argument checks -- is a part too:
 // fo_scene_hidden.hpp, behind the kernel parts.
 // State between calls (the static map, the per-step workspace): fo_scene_state.hpp.
@@ -85,6 +87,7 @@
 #include "fo_hidden_brake_impact_lanes.hpp"
 #include "fo_hidden_brake_ladder_verdict.hpp"
 #include "fo_hidden_brake_harm_ladder.hpp"
+#include "fo_hidden_brake_harm_ladder_lanes.hpp"
 #include "fo_scene_rays.hpp"
 #include "fo_scene_grid.hpp"
 #include "fo_future_visibility.hpp"

@@ -443,9 +443,13 @@ static int hidden_brake_impact_call(fo_ctx *ctx, const P *p, const char *fn, voi
 // The host part of the ladder verdict (fo_hidden_brake_ladder_verdict.hpp) and, HARM, of the harm ladder
 // (fo_hidden_brake_harm_ladder.hpp), which asks for the impact entry's speeds, rows and limit behind the ladder verdict's list and for
 // the curve's two outputs where that entry asks for its own: one launch; the levels, map_of and the table travel as kernel arguments.
-// Both structures name their shared members alike
-template <bool HARM, class P>
+// Both structures name their shared members alike.  HARM_LANES: the harm ladder by approach angle
+// (fo_hidden_brake_harm_ladder_lanes.hpp), which asks for everything HARM asks for and, behind harm_limit, for the impact-lanes
+// entry's mask, its two numbers and the map's move table
+enum { HBLV_VERDICT = 0, HBLV_HARM = 1, HBLV_HARM_LANES = 2 };
+template <int FORM, class P>
 static int hidden_brake_ladder_verdict_call(fo_ctx *ctx, const P *p, const char *fn, void *stream) {
+  constexpr bool HARM = FORM != HBLV_VERDICT, LANES = FORM == HBLV_HARM_LANES;
   int rc;
   if ((rc = hr_check_scene(ctx, p, fn))) return rc;
   Scene *sc = (Scene *)ctx->scene;
@@ -477,12 +481,33 @@ static int hidden_brake_ladder_verdict_call(fo_ctx *ctx, const P *p, const char 
     if (!(p->harm_limit >= 0.0))                                 // (NaN fails the comparison; +inf passes)
       return fo_fail(ctx, FO_E_ARG, "%s: harm_limit = %g, a harm >= 0 (or +inf) is needed", fn, p->harm_limit);
   }
+  if constexpr (LANES) {
+    if (p->dir_mask >> p->C != 0u)
+      return fo_fail(ctx, FO_E_ARG, "%s: dir_mask = 0x%x has bits at or above C = %d", fn, p->dir_mask, p->C);
+    if (!(fabs(p->cos_h) <= 1.0) || !(fabs(p->sin_h) <= 1.0))    // (NaN fails the comparison)
+      return fo_fail(ctx, FO_E_ARG, "%s: cos_h = %g, sin_h = %g, the cosine and sine of 22.5 deg + heading_slack in [-1, 1] are needed",
+                     fn, p->cos_h, p->sin_h);
+    if (p->dir_mask != 0u && (rc = hr_check_moves(ctx, fn))) return rc;
+  }
   FO_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const HbuMaps mp = hbu_maps(*p);
   const HbluPack pk = hblu_pack(p->h_levels, L, p->h_thr, C * T);
   const dim3 grid((unsigned)brake_ladder_verdict_blocks(p->M, T, K, L, B)), block(HB_THREADS);
   hipStream_t s = (hipStream_t)stream;
-  if constexpr (HARM) {
+  if constexpr (LANES) {
+    const uint32_t dir = p->cos_h > -1.0 ? p->dir_mask : 0u;     // h >= pi: every class is head-on, the table is not read
+    const HrBrakeHarmLadderLanesArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_verdict_group(L, B),
+                                       brake_ladder_verdict_per_block(T, K, L, B), p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl,
+                                       p->hw, p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny,
+                                       p->win_ix0, p->win_iy0, p->win_nx, p->win_ny, mp.key[0], mp.key[1], mp.key[2], mp.qmin[0],
+                                       mp.qmin[1], mp.qmin[2], mp.map_of, p->d_v, p->d_arc, p->dt, p->a_limit, p->d_speed_of,
+                                       p->d_harm_rows, p->harm_limit, sc->map->d_lane_moves, dir, p->cos_h, p->sin_h, p->d_finite_or_null,
+                                       p->d_cost_or_null, p->d_safe_or_null, p->d_need, p->d_at, p->d_blocking, p->d_user, p->d_decel,
+                                       p->d_need_of, p->d_first, p->d_harm_at, p->d_user_at};
+    const size_t lds = brake_harm_ladder_lanes_lds_bytes(T, K, C, L, B);
+    if (brake_users_width(C) == 4) hbll_launch<4>(K, grid, block, lds, s, a, pk);
+    else hbll_launch<8>(K, grid, block, lds, s, a, pk);
+  } else if constexpr (HARM) {
     const HrBrakeHarmLadderArgs a{p->M, T, B, L, C, brake_ladder_users_width(L), brake_ladder_verdict_group(L, B),
                                   brake_ladder_verdict_per_block(T, K, L, B), p->d_x, p->d_y, p->d_heading, p->d_len_or_null, p->hl, p->hw,
                                   p->wb, sc->map->x0, sc->map->y0, sc->map->cs, sc->map->d_raster, sc->map->rnx, sc->map->rny, p->win_ix0,
@@ -831,11 +856,15 @@ int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_c
 
 // the ladder verdict and the harm ladder: hidden_brake_ladder_verdict_call above
 int fo_scene_hidden_brake_ladder_verdict(fo_ctx *ctx, const fo_hidden_brake_ladder_verdict_t *p, void *stream) {
-  return hidden_brake_ladder_verdict_call<false>(ctx, p, "fo_scene_hidden_brake_ladder_verdict", stream);
+  return hidden_brake_ladder_verdict_call<HBLV_VERDICT>(ctx, p, "fo_scene_hidden_brake_ladder_verdict", stream);
 }
 
 int fo_scene_hidden_brake_harm_ladder(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_t *p, void *stream) {
-  return hidden_brake_ladder_verdict_call<true>(ctx, p, "fo_scene_hidden_brake_harm_ladder", stream);
+  return hidden_brake_ladder_verdict_call<HBLV_HARM>(ctx, p, "fo_scene_hidden_brake_harm_ladder", stream);
+}
+
+int fo_scene_hidden_brake_harm_ladder_lanes(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_lanes_t *p, void *stream) {
+  return hidden_brake_ladder_verdict_call<HBLV_HARM_LANES>(ctx, p, "fo_scene_hidden_brake_harm_ladder_lanes", stream);
 }
 
 }  // extern "C"

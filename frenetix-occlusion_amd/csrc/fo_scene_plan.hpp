@@ -205,6 +205,16 @@ inline size_t brake_harm_ladder_lds_bytes(int T, int K, int C, int L, int B) {
 inline size_t brake_harm_ladder_lds_bound() {
   return (brake_ladder_verdict_lds_bound() + 7) / 8 * 8 + (size_t)BRAKE_HARM_LADDER_EXCHANGE_BYTES;
 }
+// the harm ladder by approach angle: the harm ladder's lanes, grid and LDS; behind its last byte (a multiple of 8) stands the harm of
+// the "met" case, one float64 per class and trajectory of the workgroup ([per_block][C]), formed once behind first[c] and read in
+// every round.  brake_harm_ladder_lanes_lds_bound: no call needs more -- a workgroup holds at most HB_THREADS trajectories of 8
+// classes, 16 384 bytes on top of the harm ladder's bound: 55 952 bytes, under the 64 KB of a workgroup
+inline size_t brake_harm_ladder_lanes_lds_bytes(int T, int K, int C, int L, int B) {
+  return brake_harm_ladder_lds_bytes(T, K, C, L, B) + (size_t)brake_ladder_verdict_per_block(T, K, L, B) * (size_t)C * sizeof(double);
+}
+inline size_t brake_harm_ladder_lanes_lds_bound() {
+  return brake_harm_ladder_lds_bound() + (size_t)HB_THREADS * BRAKE_LADDER_USERS_MAX_CLASSES * sizeof(double);
+}
 // band launches of the road distance up to L (one also when the reach is 0: the sources)
 inline int reach_bands(int L) { return L > 0 ? (L + HRR_BAND - 1) / HRR_BAND : 1; }
 // the road occlusion memory's form by its halo n = road_steps(L)

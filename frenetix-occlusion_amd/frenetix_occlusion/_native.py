@@ -56,7 +56,7 @@ EXPORTS = [
     "fo_scene_hidden_brake_classes", "fo_scene_hidden_brake_users", "fo_scene_hidden_brake_ladder",
     "fo_scene_hidden_brake_ladder_users", "fo_scene_hidden_poses", "fo_scene_hidden_brake_verdict",
     "fo_scene_hidden_brake_ladder_verdict", "fo_scene_hidden_brake_impact", "fo_hidden_impact_row",
-    "fo_scene_hidden_brake_impact_lanes", "fo_scene_hidden_brake_harm_ladder",
+    "fo_scene_hidden_brake_impact_lanes", "fo_scene_hidden_brake_harm_ladder", "fo_scene_hidden_brake_harm_ladder_lanes",
 ]
 
 
@@ -231,6 +231,10 @@ class HiddenBrakeHarmLadder(C.Structure):       # fo_hidden_brake_harm_ladder_t
         ("d_user_at", C.c_void_p)]
 
 
+class HiddenBrakeHarmLadderLanes(C.Structure):  # fo_hidden_brake_harm_ladder_lanes_t
+    _fields_ = HiddenBrakeHarmLadder._fields_ + [("dir_mask", C.c_uint32), ("cos_h", C.c_double), ("sin_h", C.c_double)]
+
+
 HIDDEN_CLEARANCE_NONE = 2 ** 31 - 1  # FO_HIDDEN_CLEARANCE_NONE: the key of a cell (the clearance of a pose) nothing within the cap reaches
 HIDDEN_CLEARANCE_METRIC = {"euclid": 0, "road": 1}   # FO_HIDDEN_CLEARANCE_EUCLID / _ROAD
 
@@ -351,6 +355,7 @@ def load():
     lib.fo_scene_hidden_brake_impact.argtypes = [vp, C.POINTER(HiddenBrakeImpact), vp]
     lib.fo_scene_hidden_brake_impact_lanes.argtypes = [vp, C.POINTER(HiddenBrakeImpactLanes), vp]
     lib.fo_scene_hidden_brake_harm_ladder.argtypes = [vp, C.POINTER(HiddenBrakeHarmLadder), vp]
+    lib.fo_scene_hidden_brake_harm_ladder_lanes.argtypes = [vp, C.POINTER(HiddenBrakeHarmLadderLanes), vp]
     lib.fo_hidden_impact_row.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(HarmCoeff), C.POINTER(C.c_double)]
     lib.fo_scene_spawn.argtypes = ([vp, dp] + [C.c_int] * 4 + [D] * 6 + [C.c_int] * 3 + [ip] + [dp] * 5 + [C.c_int, dp, C.c_int]
                                    + [D] * 3 + [dp] * 12 + [vp])

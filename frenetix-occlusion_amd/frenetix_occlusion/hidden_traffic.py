@@ -1490,8 +1490,12 @@ class HiddenBrakeHarmLadder:
     :class:`HiddenBrakeImpact`; ``levels``, ``starts``, ``a_limit``, ``poses``, ``users``, ``map_of``, ``thr``, ``clearances`` as in
     :class:`HiddenBrakeLadderVerdict`.
 
-    Not claimed: what the two siblings do not claim; every user is priced head-on (there is no ``approach="lanes"`` here); the
-    answer is only as fine as the ladder; harder braking is not always safer, so ``harm_at`` need not fall along ``l``."""
+    What :meth:`SensorModel.hidden_brake_harm_ladder_lanes` returns has ``approach == "lanes"`` and its ``heading_slack``: every
+    user with ``flow == "lanes"`` is priced at the approach angle the lanes allow, and nothing is above the head-on call's.
+
+    Not claimed: what the two siblings do not claim; with ``approach == "head_on"`` every user is priced head-on
+    (:meth:`SensorModel.hidden_brake_harm_ladder_lanes` prices lane-bound users by their approach angle); the answer is only as
+    fine as the ladder; harder braking is not always safer, so ``harm_at`` need not fall along ``l``."""
     need: torch.Tensor
     at: torch.Tensor
     blocking: torch.Tensor
@@ -1513,6 +1517,8 @@ class HiddenBrakeHarmLadder:
     map_of: tuple = ()
     thr: Optional[np.ndarray] = None
     clearances: tuple = ()
+    approach: str = "head_on"
+    heading_slack: float = 0.0
 
     def required_deceleration(self):
         """``[M]`` float64 (m/s^2): ``decel`` -- what the cost row holds in its first reserved column"""
@@ -1558,8 +1564,45 @@ def hidden_brake_harm_ladder(self, x, y, theta, v, *, vehicle, ego_mass, users, 
     per distinct ``(metric, flow)``, and ONE launch for the walk, the harms, the reduction and the fold.  The harm rows are the
     impact verdict's, built once and kept on the device.  Nothing is read back and nobody waits; returns a
     :class:`HiddenBrakeHarmLadder`."""
-    fn = "hidden_brake_harm_ladder"
+    return _harm_ladder_call(self, "hidden_brake_harm_ladder", None, x, y, theta, v, vehicle=vehicle, ego_mass=ego_mass, users=users,
+                             kinds=kinds, dt=dt, levels=levels, starts=starts, harm_limit=harm_limit, a_limit=a_limit, coeff=coeff,
+                             cost=cost, safe=safe, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+
+
+def hidden_brake_harm_ladder_lanes(self, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, levels=None, starts, harm_limit,
+                                   a_limit=float("inf"), coeff=None, cost=None, safe=None, margin=None, inflate=0.0, lengths=None,
+                                   poses=None, heading_slack=0.0):
+    """Hidden-traffic harm ladder by approach angle (``fo_scene_hidden_brake_harm_ladder_lanes``; DESIGN.md §5.10 "Harm ladder by
+    approach angle"): :meth:`hidden_brake_harm_ladder` with every user with ``flow == "lanes"`` priced at the worst closing speed the
+    lanes' driving directions allow at the cells where it meets the ego -- ``dv = sqrt(v_ego^2 + v_user^2 + 2 v_ego v_user
+    cos(pdof))`` at the greatest ``cos(pdof)`` over the headings within 22.5 degrees + ``heading_slack`` (radians, ``>= 0``) of a
+    direction the move table leaves, as ``hidden_brake_impact(approach="lanes")`` prices it -- and every other user head-on as
+    before.  ``decel`` and ``harm_at`` are never above the head-on call's; without a lane-bound user, or with ``heading_slack`` at
+    or above 7 pi / 8, every output is that call's bit for bit.  It needs the map's move table (``lane_moves``) where a user is
+    lane-bound.  One launch, the same arguments, the same two reserved columns: fold one of the five stages into a row.  Returns a
+    :class:`HiddenBrakeHarmLadder` with ``approach == "lanes"``."""
+    return _harm_ladder_call(self, "hidden_brake_harm_ladder_lanes", heading_slack, x, y, theta, v, vehicle=vehicle, ego_mass=ego_mass,
+                             users=users, kinds=kinds, dt=dt, levels=levels, starts=starts, harm_limit=harm_limit, a_limit=a_limit,
+                             coeff=coeff, cost=cost, safe=safe, margin=margin, inflate=inflate, lengths=lengths, poses=poses)
+
+
+def _harm_ladder_call(self, fn, heading_slack, x, y, theta, v, *, vehicle, ego_mass, users, kinds, dt, levels, starts, harm_limit, a_limit,
+                      coeff, cost, safe, margin, inflate, lengths, poses):
+    """the ONE body of :func:`hidden_brake_harm_ladder` (``heading_slack is None``: head-on) and
+    :func:`hidden_brake_harm_ladder_lanes`: one set of checks, one set of buffers, the entry by the form"""
+    lanes = heading_slack is not None
     users = _road_users(users, x, fn)
+    dir_mask = 0
+    if lanes:
+        try:
+            heading_slack = float(heading_slack)
+        except (TypeError, ValueError):
+            heading_slack = float("nan")
+        if not (heading_slack >= 0.0 and math.isfinite(heading_slack)):
+            raise ValueError(f"{fn}: heading_slack must be a finite angle >= 0 in radians")
+        dir_mask = sum(1 << c for c, u in enumerate(users) if u[2] == "lanes")
+        if dir_mask and getattr(self, "lane_moves", None) is None:
+            raise ValueError(f"{fn}: a lane-bound user needs the map's move table (lane_moves is None)")
     try:
         a_limit = float(a_limit)
     except (TypeError, ValueError):
@@ -1586,15 +1629,22 @@ def hidden_brake_harm_ladder(self, x, y, theta, v, *, vehicle, ego_mass, users, 
     need, at, blocking, user, need_of, first, user_at = new(M), new(M), new(M), new(M), new(C_, M), new(C_, M), new(M, L_)
     decel = torch.empty((M,), dtype=torch.float64, device=dev)
     harm_at = torch.empty((M, L_), dtype=torch.float64, device=dev)
-    args = N.HiddenBrakeHarmLadder(**p.fields(tv, poses.arc, dt), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B,
-                                   a_limit=a_limit, d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost),
-                                   d_safe_or_null=N.ptr(safe), d_need=N.ptr(need), d_at=N.ptr(at), d_blocking=N.ptr(blocking),
-                                   d_user=N.ptr(user), d_decel=N.ptr(decel), d_need_of=N.ptr(need_of), d_first=N.ptr(first),
-                                   d_speed_of=N.ptr(d_speed_of), d_harm_rows=N.ptr(d_rows), harm_limit=harm_limit,
-                                   d_harm_at=N.ptr(harm_at), d_user_at=N.ptr(user_at))
-    self.ctx.call("fo_scene_hidden_brake_harm_ladder", C.byref(args), N.current_stream(self._dev_index))
+    common = dict(**p.fields(tv, poses.arc, dt), h_levels=levels.ctypes.data_as(C.POINTER(C.c_double)), L=L_, B=B, a_limit=a_limit,
+                  d_finite_or_null=N.ptr(poses.finite), d_cost_or_null=N.ptr(cost), d_safe_or_null=N.ptr(safe), d_need=N.ptr(need),
+                  d_at=N.ptr(at), d_blocking=N.ptr(blocking), d_user=N.ptr(user), d_decel=N.ptr(decel), d_need_of=N.ptr(need_of),
+                  d_first=N.ptr(first), d_speed_of=N.ptr(d_speed_of), d_harm_rows=N.ptr(d_rows), harm_limit=harm_limit,
+                  d_harm_at=N.ptr(harm_at), d_user_at=N.ptr(user_at))
+    if lanes:
+        h = math.pi / 8.0 + heading_slack
+        cos_h, sin_h = (math.cos(h), math.sin(h)) if h < math.pi else (-1.0, 0.0)      # (cos_h = -1: every user is head-on)
+        args = N.HiddenBrakeHarmLadderLanes(**common, dir_mask=dir_mask, cos_h=cos_h, sin_h=sin_h)
+        self.ctx.call("fo_scene_hidden_brake_harm_ladder_lanes", C.byref(args), N.current_stream(self._dev_index))
+    else:
+        args = N.HiddenBrakeHarmLadder(**common)
+        self.ctx.call("fo_scene_hidden_brake_harm_ladder", C.byref(args), N.current_stream(self._dev_index))
     # (stay referenced until the next call, as in hidden_brake_users)
     self._hbhl_inputs = (tv, poses, p.clearances, cost, safe)
     self._hbhl_args = args                                  # (the structure of the last call: tools/hidden_reach_bench.py replays the launch alone)
     return HiddenBrakeHarmLadder(need, at, blocking, user, decel, need_of, first, harm_at, user_at, levels, B, harm_limit, a_limit, rows,
-                                 speed_of, kinds, users, poses, p.map_of, p.thr, p.clearances)
+                                 speed_of, kinds, users, poses, p.map_of, p.thr, p.clearances, "lanes" if lanes else "head_on",
+                                 heading_slack if lanes else 0.0)

@@ -623,25 +623,40 @@ class FOInterface:
         ``.brake_threat_number(a_max)``, ``.critical_user()``, ``.harm_curve()``, ``.monotone()``).  ``kinds`` as for
         :meth:`hidden_brake_impact`.  With ``cost [M, 16]`` / ``safe [M]`` of a sweep over the same candidates the deceleration and
         the user are folded into the two reserved columns, and candidates that need more than ``a_limit`` (None: the vehicle's
-        ``a_max``) or more than the ladder holds lose their safety flag.  Every user is priced head-on.  The other defaults as for
+        ``a_max``) or more than the ladder holds lose their safety flag.  Every user is priced head-on
+        (:meth:`hidden_brake_harm_ladder_lanes` prices lane-bound users by their approach angle).  The other defaults as for
         :meth:`hidden_brake_users`."""
+        return self._hidden_harm_ladder("hidden_brake_harm_ladder", trajectories, users, kinds, harm_limit, levels, starts, a_limit, cost,
+                                        safe, margin, inflate)
+
+    def hidden_brake_harm_ladder_lanes(self, trajectories, users, kinds=None, harm_limit=None, levels=None, starts=None, a_limit=None,
+                                       cost=None, safe=None, margin=None, inflate=0.0, heading_slack=0.0):
+        """EXTENSION, not part of the reference: the HARM LADDER BY APPROACH ANGLE -- :meth:`hidden_brake_harm_ladder` with every
+        user with ``flow == "lanes"`` priced at the worst closing speed the lanes' driving directions allow where it meets the ego,
+        within 22.5 degrees + ``heading_slack`` (radians) of a direction of the move table, instead of head-on
+        (:meth:`SensorModel.hidden_brake_harm_ladder_lanes`; the same result class with ``approach == "lanes"``).  Never above the
+        head-on call; the defaults are its sibling's."""
+        return self._hidden_harm_ladder("hidden_brake_harm_ladder_lanes", trajectories, users, kinds, harm_limit, levels, starts, a_limit,
+                                        cost, safe, margin, inflate, heading_slack=heading_slack)
+
+    def _hidden_harm_ladder(self, fn, trajectories, users, kinds, harm_limit, levels, starts, a_limit, cost, safe, margin, inflate, **lanes):
+        """the one body of :meth:`hidden_brake_harm_ladder` and :meth:`hidden_brake_harm_ladder_lanes` (``lanes``: its heading_slack)"""
         from .metrics.metric import trajectories_to_arrays
         from .sweep import _vehicle_tuple
         if self.timestep is None or self.sensor_model.window is None:
-            raise RuntimeError("hidden_brake_harm_ladder needs a previous evaluate_scenario")
+            raise RuntimeError(f"{fn} needs a previous evaluate_scenario")
         users = tuple(users)
-        kinds = self._hidden_kinds(users, kinds, "hidden_brake_harm_ladder")
+        kinds = self._hidden_kinds(users, kinds, fn)
         harm_limit = self._hidden_harm_limit(harm_limit)
         vt = _vehicle_tuple(self.vehicle_params)               # length, width, wb_rear_axle, mass, a_max
         if levels is None:
-            levels = _default_brake_ladder(vt[4], "hidden_brake_harm_ladder")
+            levels = _default_brake_ladder(vt[4], fn)
         arr = trajectories_to_arrays(trajectories)
         om = self.occlusion_memory
-        return self.sensor_model.hidden_brake_harm_ladder(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], ego_mass=vt[3],
-                                                          users=users, kinds=kinds, margin=om["margin"] if margin is None else margin,
-                                                          dt=self.dt, levels=levels, starts=starts, harm_limit=harm_limit,
-                                                          a_limit=vt[4] if a_limit is None else a_limit, cost=cost, safe=safe,
-                                                          inflate=inflate)
+        return getattr(self.sensor_model, fn)(arr["x"], arr["y"], arr["theta"], arr["v"], vehicle=vt[:3], ego_mass=vt[3], users=users,
+                                              kinds=kinds, margin=om["margin"] if margin is None else margin, dt=self.dt, levels=levels,
+                                              starts=starts, harm_limit=harm_limit, a_limit=vt[4] if a_limit is None else a_limit,
+                                              cost=cost, safe=safe, inflate=inflate, **lanes)
 
     def add_witness_agents(self, witness, max_agents=8, merge_cells=4, agent_type="Car"):
         """EXTENSION, not part of the reference: puts the hidden road users behind a :meth:`hidden_witness` result in front of the

@@ -378,7 +378,7 @@ class SensorModel:
 
     # ---- extensions, not part of the reference: each body and its docstring live in the module named
     from .future_visibility import future_visibility, future_visibility_ex
-    from .hidden_traffic import hidden_brake, hidden_brake_classes, hidden_brake_harm_ladder, hidden_brake_impact, hidden_brake_ladder, hidden_brake_ladder_users, hidden_brake_ladder_verdict, hidden_brake_users, hidden_brake_verdict, hidden_clearance, hidden_poses, hidden_reach, hidden_witness
+    from .hidden_traffic import hidden_brake, hidden_brake_classes, hidden_brake_harm_ladder, hidden_brake_harm_ladder_lanes, hidden_brake_impact, hidden_brake_ladder, hidden_brake_ladder_users, hidden_brake_ladder_verdict, hidden_brake_users, hidden_brake_verdict, hidden_clearance, hidden_poses, hidden_reach, hidden_witness
 
     def calc_visible_and_occluded_area(self, timestep, ego_pos, ego_orientation, obstacles):
         """reference entry point.  obstacles: an FOObstacles (already updated to `timestep`) or None."""

@@ -42,15 +42,25 @@ def hidden_stages(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, 
     """``(ladder, impact, harm_ladder)``: the ``hidden_ladder_verdict=``, ``hidden_impact_verdict=`` and
     ``hidden_harm_ladder_verdict=`` of :class:`PlanningStep` as dicts of their own, or the refusal of the four stages together --
     they own the same two reserved cost columns, so a step runs one of them; None stays None"""
+    return hidden_stages_lanes(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, hidden_harm_ladder_verdict, None)[:3]
+
+
+def hidden_stages_lanes(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, hidden_harm_ladder_verdict,
+                        hidden_harm_ladder_lanes_verdict):
+    """``(ladder, impact, harm_ladder, harm_ladder_lanes)``: :func:`hidden_stages` with the fifth owner of the same two reserved
+    cost columns, ``hidden_harm_ladder_lanes_verdict=`` -- any two of the five are refused; None stays None"""
     given = [n for n, q in (("hidden_verdict", hidden_verdict), ("hidden_ladder_verdict", hidden_ladder_verdict),
                             ("hidden_impact_verdict", hidden_impact_verdict),
-                            ("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict)) if q is not None]
+                            ("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict),
+                            ("hidden_harm_ladder_lanes_verdict", hidden_harm_ladder_lanes_verdict)) if q is not None]
     if len(given) > 1:
         raise ValueError(f"PlanningStep: {' and '.join(given)} own the same two reserved cost columns: a step runs one of them")
+    harm_optional = ("levels", "a_limit", "coeff", "margin", "inflate", "lengths")
     return (_stage_options("hidden_ladder_verdict", hidden_ladder_verdict, _LADDER_KEYS, ("margin", "inflate", "lengths")),
             _stage_options("hidden_impact_verdict", hidden_impact_verdict, _IMPACT_KEYS, ("coeff", "margin", "inflate", "lengths", "approach", "heading_slack")),
-            _stage_options("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict, _HARM_LADDER_KEYS,
-                           ("levels", "a_limit", "coeff", "margin", "inflate", "lengths")))
+            _stage_options("hidden_harm_ladder_verdict", hidden_harm_ladder_verdict, _HARM_LADDER_KEYS, harm_optional),
+            _stage_options("hidden_harm_ladder_lanes_verdict", hidden_harm_ladder_lanes_verdict, _HARM_LADDER_KEYS,
+                           harm_optional + ("heading_slack",)))
 
 
 def hidden_stage_options(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict):
@@ -68,7 +78,7 @@ def hidden_ladder_verdict_options(hidden_verdict, hidden_ladder_verdict, hidden_
 class PlanningStep:
     def __init__(self, sensor_model, spawn_locator, sweep, x, y, theta, v, a=None, mode="reduced", lists="f64", shard=None,
                  mirror=False, hidden_verdict=None, hidden_ladder_verdict=None, hidden_impact_verdict=None,
-                 hidden_harm_ladder_verdict=None):
+                 hidden_harm_ladder_verdict=None, hidden_harm_ladder_lanes_verdict=None):
         """``hidden_verdict`` (an extension, DESIGN.md §5.10 "Fail-safe verdict"): a dict of the keyword arguments of
         :meth:`SensorModel.hidden_brake_verdict` -- ``vehicle``, ``users``, ``dt``, ``a_brake``, ``starts``, ``commit_min`` and
         optionally ``margin``, ``inflate``, ``lengths`` -- :meth:`run` then queues the pose preparation, the clearances and the
@@ -97,6 +107,13 @@ class PlanningStep:
         :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeHarmLadder`.  It owns the same two columns: giving two of the four
         stages is a ValueError.  None: nothing is queued or allocated for it, and ``out`` has no such attribute.
 
+        ``hidden_harm_ladder_lanes_verdict`` (an extension, DESIGN.md §5.10 "Harm ladder by approach angle"): a dict of the keyword
+        arguments of :meth:`SensorModel.hidden_brake_harm_ladder_lanes` -- those of ``hidden_harm_ladder_verdict`` and optionally
+        ``heading_slack`` -- queued where the other four stages are, with ``shard`` on this rank's rows before the all-gather;
+        ``out.hidden_harm_ladder_lanes_verdict`` is its :class:`~frenetix_occlusion.hidden_traffic.HiddenBrakeHarmLadder`.  It
+        owns the same two columns: giving two of the five stages is a ValueError.  None: nothing is queued or allocated for it,
+        and ``out`` has no such attribute.
+
         ``shard`` (BASELINE configs[3]: one process per GPU, every rank builds the same step): True / a process group / a
         :class:`~frenetix_occlusion.distributed.CostGather` for the batch size -- this rank's step covers its contiguous
         block of the candidates (scene stage and phantoms replicated), writes the block's cost rows into the collective's
@@ -110,8 +127,8 @@ class PlanningStep:
             raise ValueError("PlanningStep: the three stages must share one context (one ego, one GPU)")
         if mode not in ("reduced", "pair", "full"):
             raise ValueError(f"unknown output mode '{mode}'")
-        ladder, impact, harm_ladder = hidden_stages(hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict,
-                                                    hidden_harm_ladder_verdict)     # (refused before anything is allocated)
+        ladder, impact, harm_ladder, harm_ladder_lanes = hidden_stages_lanes(      # (refused before anything is allocated)
+            hidden_verdict, hidden_ladder_verdict, hidden_impact_verdict, hidden_harm_ladder_verdict, hidden_harm_ladder_lanes_verdict)
         self.sm, self.sl, self.sw = sensor_model, spawn_locator, sweep
         self.ctx = sweep.ctx
         self.mode, self.lists, self.mirror = mode, lists, bool(mirror)
@@ -171,6 +188,9 @@ class PlanningStep:
         self._hidden_harm_ladder_verdict = harm_ladder
         if harm_ladder is not None and self.gather is not None and harm_ladder.get("lengths") is not None:
             harm_ladder["lengths"] = harm_ladder["lengths"][self.gather.lo:self.gather.hi]
+        self._hidden_harm_ladder_lanes_verdict = harm_ladder_lanes
+        if harm_ladder_lanes is not None and self.gather is not None and harm_ladder_lanes.get("lengths") is not None:
+            harm_ladder_lanes["lengths"] = harm_ladder_lanes["lengths"][self.gather.lo:self.gather.hi]
 
     def _fill(self, w, O):
         """everything that does not change from step to step"""
@@ -287,6 +307,11 @@ class PlanningStep:
             tx, ty, tth, tv = self.traj[:4]
             self.out.hidden_harm_ladder_verdict = sm.hidden_brake_harm_ladder(tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe,
                                                                               **self._hidden_harm_ladder_verdict)
+        if self._hidden_harm_ladder_lanes_verdict is not None:
+            # the same place: one of the five stages owns the two columns
+            tx, ty, tth, tv = self.traj[:4]
+            self.out.hidden_harm_ladder_lanes_verdict = sm.hidden_brake_harm_ladder_lanes(
+                tx, ty, tth, tv, cost=self.out.cost, safe=self.out.safe, **self._hidden_harm_ladder_lanes_verdict)
         if self.gather is not None:
             # the one collective of the path, queued behind the step
             self.out.cost_all = self.gather.gather(None if self._direct or self.M == 0 else self.out.cost)

@@ -1189,7 +1189,8 @@ int fo_hidden_impact_row(int type, double size, double ego_mass, const fo_harm_c
  *  Safety of the data: as fo_scene_hidden_brake_ladder_users; finite, speed_of and the rows may hold anything, no index depends on
  *   them.
  *  Not claimed: what the ladder verdict and the impact verdict do not claim; every user is priced HEAD-ON and at the worst area of
- *   impact (the approach angle of fo_scene_hidden_brake_impact_lanes is not taken); harder braking is not always safer against an
+ *   impact (the approach angle of fo_scene_hidden_brake_impact_lanes is not taken here: fo_scene_hidden_brake_harm_ladder_lanes below
+ *   takes it); harder braking is not always safer against an
  *   arrival map, so harm_at need not fall with l -- need is the first sufficient level of every start, not the last insufficient one.
  * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
  * "fo_scene_hidden_brake_harm_ladder:"): those of fo_scene_hidden_brake_ladder_verdict in its order (a missing output includes
@@ -1228,6 +1229,80 @@ typedef struct {
   int32_t *d_user_at;                       /* [M][L] the lowest class that attains it */
 } fo_hidden_brake_harm_ladder_t;
 int fo_scene_hidden_brake_harm_ladder(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_t *p, void *stream);
+
+/* EXTENSION, not part of the reference: hidden-traffic HARM LADDER BY APPROACH ANGLE (DESIGN.md §5.10 "Harm ladder by approach
+ * angle") -- the harm ladder above with every LANE-BOUND class of road user priced at the worst closing speed the lanes' driving
+ * directions allow at the cells where it meets the ego, as fo_scene_hidden_brake_impact_lanes prices it, instead of head-on: the
+ * deceleration the ego must be prepared for is no longer an upper bound for a vehicle that can only arrive from the side.  One
+ * launch; opt-in and additive like the entry above.  It writes the SAME two reserved columns as the four stages above: a step runs
+ * one of the five.
+ *  Inputs: those of fo_scene_hidden_brake_harm_ladder word for word, and: dir_mask, cos_h, sin_h with the meaning they have in
+ *   fo_scene_hidden_brake_impact_lanes (bit c set = class c is lane-bound; the cosine and sine of h = 22.5deg + heading_slack from
+ *   the caller's host, both in [-1, 1]; cos_h <= -1 states h >= pi: every class is head-on).  With dir_mask != 0 the context's map
+ *   must have a move table.
+ *  Steps 1, 2, 4, 5 and 6 of fo_scene_hidden_brake_harm_ladder hold word for word.  Step 3 becomes:
+ *  3. For a hit (c, m, b, l) the hit pose, its sample i, its hit cells and mv are step 2 of fo_scene_hidden_brake_impact_lanes at
+ *   a_brake = levels[l]: where 0 <= fm[c] <= b the candidate's own pose at i = fm[c], otherwise the manoeuvre's pose at
+ *   i = bf[c][m][b][l].  cm is that entry's step 3; w is its step 4 with u from this entry's step 2; the harm at the hit is
+ *   ho(c, m, b, l) = 1 / (1 + exp(rows[c][0] + rows[c][1] * w)).  float64, this operation order, no contraction.
+ *  Consequences:
+ *   (a) with dir_mask == 0, a move table of 0xFF alone or cos_h <= -1 every output is fo_scene_hidden_brake_harm_ladder's bit for
+ *    bit (cm == 1.0 and w = u + speed_of[c] exactly); hence harm_limit = 0.0 then gives fo_scene_hidden_brake_ladder_verdict bit
+ *    for bit on the shared outputs;
+ *   (b) w <= u + speed_of[c] and the rows' speed coefficients are negative, so ho <= the head-on ho for every (c, m, b, l):
+ *    harm_at <= the head-on entry's harm_at for every (m, l), and need <= its need -- `over` is a subset per (c, m, b, l) and the
+ *    ladder reduction is monotone in it (the same argument by which need never rises with harm_limit);
+ *   (c) harm_at[:, l] is the obstacle harm of fo_scene_hidden_brake_impact_lanes at a_brake = levels[l] and the same B, user_at its
+ *    user wherever no two classes tie;
+ *   (d) harm_limit = +inf gives need = 0 wherever ends > 0; harm_at[m][l] <= harm_limit implies need[m] <= l, and need[m] == L
+ *    implies harm_at[m][l] > harm_limit at every l, as in the head-on entry.
+ *  Outputs, every byte written by every call: those of fo_scene_hidden_brake_harm_ladder.
+ *  Safety of the data: as fo_scene_hidden_brake_harm_ladder; the move table is read at cells tested against the raster alone, and
+ *   only for a class of dir_mask.
+ *  Not claimed: what fo_scene_hidden_brake_harm_ladder does not claim, but for the head-on pricing of lane-bound classes; what
+ *   fo_scene_hidden_brake_impact_lanes does not claim about a lane-abiding vehicle (it heads along its lane; the area of impact stays
+ *   worst-case; at an intersection cell the union of the lanelets widens the sector); the cosine and the closing speed of a hit
+ *   are not outputs -- fo_scene_hidden_brake_impact_lanes at a_brake = levels[l] names them for the worst start of a class.
+ * M = 0: FO_OK, nothing launched.  FO_E_ARG (nothing is launched, no byte written, messages prefixed
+ * "fo_scene_hidden_brake_harm_ladder_lanes:"): those of fo_scene_hidden_brake_harm_ladder in its order, then, behind harm_limit: a
+ * dir_mask with bits at or above C; cos_h or sin_h not finite or outside [-1, 1].  FO_E_STATE: no scene; behind those, dir_mask != 0
+ * and the map has no move table. */
+typedef struct {
+  int32_t M, T;
+  const double *d_x, *d_y;                  /* [M][T] */
+  const double *d_heading;                  /* [M][T][2] unit (cos, sin) */
+  const int32_t *d_len_or_null;             /* [M] */
+  double hl, hw, wb;
+  int32_t win_ix0, win_iy0, win_nx, win_ny;
+  int32_t K;
+  int32_t C;
+  const int32_t *d_key[FO_HIDDEN_BRAKE_MAX_MAPS];
+  const int32_t *d_qmin[FO_HIDDEN_BRAKE_MAX_MAPS];
+  int32_t r2_cap[FO_HIDDEN_BRAKE_MAX_MAPS];
+  int32_t map_of[FO_HIDDEN_BRAKE_MAX_CLASSES];
+  const double *d_v;
+  const double *d_arc;
+  const double *h_levels;                   /* HOST [L] */
+  int32_t L;
+  int32_t B;
+  double dt;
+  const int32_t *h_thr;                     /* HOST [C][T] */
+  double a_limit;
+  const uint8_t *d_finite_or_null;          /* [M] */
+  double *d_cost_or_null;                   /* [M][FO_NC]: both or neither */
+  uint8_t *d_safe_or_null;                  /* [M] */
+  int32_t *d_need, *d_at, *d_blocking, *d_user;     /* [M] */
+  double *d_decel;                          /* [M] */
+  int32_t *d_need_of, *d_first;             /* [C][M] */
+  const double *d_speed_of;                 /* [C] */
+  const double *d_harm_rows;                /* [C][4] */
+  double harm_limit;
+  double *d_harm_at;                        /* [M][L] */
+  int32_t *d_user_at;                       /* [M][L] */
+  uint32_t dir_mask;                        /* bit c: class c is lane-bound */
+  double cos_h, sin_h;                      /* of h = 22.5deg + heading_slack */
+} fo_hidden_brake_harm_ladder_lanes_t;
+int fo_scene_hidden_brake_harm_ladder_lanes(fo_ctx *ctx, const fo_hidden_brake_harm_ladder_lanes_t *p, void *stream);
 
 /* Phantom sampling in the occluded cells + constant-velocity predictions (replaces the cell-based core of
  * SpawnLocator.find_spawn_points, spawn_locator.py:80-139, and agent.py:451-536).  Candidates: occluded cells at least

@@ -77,6 +77,13 @@ shared outputs are the ladder verdict's bit for bit; a level whose ``harm_at`` i
 level is over it; ``harm_at[:, l]`` is the impact verdict's obstacle harm at ``a_brake = levels[l]`` to 1e-9.  Also the distribution of
 ``need`` and ``decel`` and where ``harm_at`` rises with harder braking.
 
+``--approach lanes`` (with ``--brake-harm-ladder B``): also ``hidden_brake_harm_ladder_lanes`` at ``--heading-slack`` (§5.10 "Harm ladder
+by approach angle") -- its launch next to the head-on launch in the same process, once with the cyclist and the car lane-bound and once
+with ``dir_mask = 0`` (the kernel before any further scan), the whole call, and the 23 ``hidden_brake_impact(approach="lanes")`` calls it
+replaces.  In every run: with ``dir_mask = 0`` every output is the head-on entry's bit for bit; nothing is above head-on; ``harm_at[:,
+l]`` is the impact verdict by approach angle at ``a_brake = levels[l]`` to 1e-9.  Also how many of the head-on stage's "no level"
+candidates get a level, the distribution of ``need`` and the ``harm_at`` quantiles against head-on.
+
 Kernel by kernel: run it under ``rocprofv3 --kernel-trace --stats -- python tools/hidden_reach_bench.py ...``."""
 import argparse
 import ctypes as C
@@ -146,7 +153,7 @@ def main():
     ap.add_argument("--harm-limit", type=float, default=0.1,
                     help="with --brake-harm-ladder: harm_limit (default: metric_thresholds.harm of the reference's example configuration)")
     ap.add_argument("--approach", default="head_on", choices=("head_on", "lanes"),
-                    help="with --brake-impact: lanes also times approach='lanes' and records what it does to the grading")
+                    help="with --brake-impact or --brake-harm-ladder: lanes also times the stage by approach angle and records what it does to the grading")
     ap.add_argument("--heading-slack", type=float, default=0.0, help="with --approach lanes: heading_slack in radians")
     a = ap.parse_args()
     if a.flow == "lanes" and a.metric != "road":
@@ -543,6 +550,69 @@ def main():
         res["candidates_rising_into_level"] = {str(l + 1): int(n) for l, n in enumerate(rises) if n}
         ha = h_out.harm_at.cpu().numpy()
         res["harm_at_quantiles_by_level"] = {str(l): [float(np.quantile(ha[:, l], q)) for q in (0.0, 0.5, 1.0)] for l in (0, L // 2, L - 1)}
+        if a.approach == "lanes":
+            # by approach angle (§5.10 "Harm ladder by approach angle"): the cyclist and the car are lane-bound
+            hbll = lambda limit=a.harm_limit, **kw: sm.hidden_brake_harm_ladder_lanes(
+                tx, ty, tth, tv, vehicle=veh, ego_mass=mass, users=users, kinds=kinds, dt=0.1, levels=levels, starts=B, harm_limit=limit,
+                a_limit=a_max, heading_slack=a.heading_slack, **kw)
+            every = shared + ("harm_at", "user_at")
+            bits = lambda t: t.view(torch.int64) if t.dtype == torch.float64 else t
+            l_out = hbll(poses=poses)
+            # (b), in every run: never above head-on
+            assert bool((l_out.harm_at <= h_out.harm_at).all()) and bool((l_out.need <= h_out.need).all()) and bool((l_out.decel <= h_out.decel).all())
+            assert bool((l_out.need_of <= h_out.need_of).all()) and torch.equal(l_out.first, h_out.first)
+            # (c), in every run: level l of the curve is the impact verdict by approach angle at a_brake = levels[l]
+            worst, other_user = 0.0, 0
+            for l, level in enumerate(levels):
+                i_out = hbi(float(level), poses=poses, approach="lanes", heading_slack=a.heading_slack)
+                worst = max(worst, float((l_out.harm_at[:, l] - i_out.harm[:, 0]).abs().max()))
+                other_user += int((l_out.user_at[:, l] != i_out.user).sum())
+            assert worst <= 1e-9, worst
+            res["brake_harm_ladder_lanes_worst_difference_to_impact_lanes"] = worst
+            res["brake_harm_ladder_lanes_users_differing_from_impact_lanes"] = other_user
+            # the launches alone, next to the head-on launch in this process: with the users' mask, and -- the same structure with
+            # dir_mask = 0, the kernel before any further scan -- (a), in every run: every output is the head-on entry's bit for bit
+            keep_l = hbll(poses=poses, cost=scratch[0], safe=scratch[1])
+            args_l = sm._hbhl_args
+            launch_l = (C.byref(args_l), N.current_stream(sm._dev_index))
+            mask = int(args_l.dir_mask)
+            assert mask == 0b110 or a.heading_slack >= 7.0 * math.pi / 8.0
+            res["brake_harm_ladder_lanes_launch_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_harm_ladder_lanes", *launch_l), a.calls)
+            res["brake_harm_ladder_launch_again_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_harm_ladder", *launch_h), a.calls)
+            args_l.dir_mask = 0
+            res["brake_harm_ladder_lanes_launch_dir_mask_0_ms"] = _median_ms(lambda: sm.ctx.call("fo_scene_hidden_brake_harm_ladder_lanes", *launch_l), a.calls)
+            torch.cuda.synchronize()
+            for name in every:
+                assert torch.equal(bits(getattr(keep_l, name)), bits(getattr(h_out, name))), name
+            args_l.dir_mask = mask
+            sm.ctx.call("fo_scene_hidden_brake_harm_ladder_lanes", *launch_l)
+            torch.cuda.synchronize()
+            for name in every:
+                assert torch.equal(bits(getattr(keep_l, name)), bits(getattr(l_out, name))), name
+            # (for whoever reads a kernel trace of this run: in launch order the new kernel's dispatches [first, last) are those with dir_mask = 0)
+            res["brake_harm_ladder_lanes_dispatches_with_dir_mask_0"] = [2 + (a.calls + 1), 2 + 2 * (a.calls + 1)]
+            res["heading_slack"] = a.heading_slack
+            res["brake_harm_ladder_lanes_call_ms"] = _median_ms(hbll, a.calls)
+            res["brake_harm_ladder_lanes_call_reused_poses_ms"] = _median_ms(lambda: hbll(poses=poses), a.calls)
+
+            def impact_lanes_per_level():
+                for level in levels:
+                    hbi(float(level), poses=poses, approach="lanes", heading_slack=a.heading_slack)
+            res["brake_impact_lanes_calls_per_level_reused_poses_ms"] = _median_ms(impact_lanes_per_level, max(a.calls // 5, 3))
+            # the grading against head-on
+            none_head = h_out.need == L
+            res["lanes_candidates_by_need"] = {str(k): int((l_out.need == k).sum()) for k in range(-1, L + 1)}
+            res["lanes_candidates_no_level"] = int((l_out.need == L).sum())
+            res["lanes_candidates_no_level_head_on_that_get_a_level"] = int((none_head & (l_out.need < L)).sum())
+            res["lanes_candidates_with_lower_need"] = int((l_out.need < h_out.need).sum())
+            res["lanes_candidates_by_harm_ladder_user"] = {str(c): int((l_out.user == c).sum()) for c in range(-2, len(users))}
+            res["lanes_candidates_not_monotone"] = int((~l_out.monotone()).sum())
+            la = l_out.harm_at.cpu().numpy()
+            res["lanes_harm_at_quantiles_by_level"] = {str(l): [float(np.quantile(la[:, l], q)) for q in (0.0, 0.5, 1.0)] for l in (0, L // 2, L - 1)}
+            hit = ha > 0
+            res["lanes_harm_at_ratio_quantiles"] = ({str(q): float(np.quantile(la[hit] / ha[hit], q)) for q in (0.0, 0.05, 0.25, 0.5, 0.75, 0.95, 1.0)}
+                                                    if hit.any() else {})
+            res["lanes_pairs_below_head_on"] = int((la < ha).sum())
     if a.brake_ladder:
         a_top = SY.VEHICLE_BMW320I[4] if a.brake is None else a.brake
         levels = np.linspace(0.5, a_top, a.brake_ladder) if a.brake_ladder > 1 else np.array([a_top])
